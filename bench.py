@@ -1,25 +1,32 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: G1 multi-scalar multiplication on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--log2n L] [--curve alt_bn128]
+  python bench.py --gpus N --steps K --warmup W [--log2n L] [--curve alt_bn128] [--full] [--dump-outputs DIR]
 
 One "step" = one full MSM (libff::multi_exp) over synthetic (scalar, base) pairs that are
-already resident in HBM.
+already resident in HBM.  A plain run sets up, runs W warm-up steps and exactly K timed steps of
+the `value` workload and prints the JSON line; everything else below (the legs, the CPU baseline,
+the exchange timing at N > 1) runs only with --full.
+
+--dump-outputs DIR writes the result of the last timed step (rank 0's at N > 1): the point the
+caller receives, normalised to libff's special form (x, y, 1) in Montgomery limbs, as
+DIR/msm_result.npy, its little-endian 32-bit words as float64 (exact).  Inputs are seeded, so
+two builds given the same arguments can be compared output for output.
 
 N = 1   `value` = BASELINE configs[1]: alt_bn128 G1, 2^20 points, one MSM after the other.
-        Inside `config.legs` (the driver keeps `config`): the 2^26-point size of the metric,
+        Inside `config.legs` (--full; the driver keeps `config`): the 2^26-point size of the metric,
         the end-to-end (scalars over PCIe, resident bases) and host-entry (everything from host
         memory) timings of SURVEY.md §8(d), back-to-back MSMs in flight, precomputed multiples.
 N > 1   one rank per GPU (started by torch.distributed.run -- by the caller, or by this script
         itself when WORLD_SIZE is unset).  `value` = BASELINE configs[3]: alt_bn128 G1, 2^26 points
         in TOTAL, range-sharded (multiexp.tcc:663-687 with rank == chunk): every rank reduces
         its 2^26/N points to one partial point, one RCCL all-gather of the partials, local sum
-        -> "scaling": "strong".  `config.legs` adds configs[4] (bw6_761 G1 + bls12_377 G2, 2^24
+        -> "scaling": "strong".  With --full, `config.legs` adds configs[4] (bw6_761 G1 + bls12_377 G2, 2^24
         points in total each, issued together on two streams per rank), the weak-scaling figure
         (2^20 points per GPU) and the same 2^26 MSM on rank 0 alone.
 
 The driver's record keeps the scalar keys of `config` and `roofline` and drops nested objects, so every figure the metric is
-quoted on is ALSO a scalar key of `config`: ms_per_step_2p26 / value_2p26 / sort_ms_2p26 / accumulate_ms_2p26 / mac_issue_frac_2p26
+quoted on is ALSO a scalar key of `config` (the leg figures with --full): ms_per_step_2p26 / value_2p26 / sort_ms_2p26 / accumulate_ms_2p26 / mac_issue_frac_2p26
 (the 2^26 half of the metric), ms_per_step_<leg> / value_<leg> for the R32 bases (the reference profiler's input shape), configs[2],
 the configs[4] shards and totals, the per-rank shards of configs[3] (2^23 / 2^24 / 2^25) and predicted_efficiency_{2,4,8}gpu (whole
 input / (N x (shard + 0.05 ms exchange)): a prediction from one GPU, never a measurement of N).
@@ -29,7 +36,7 @@ The JSON line also carries
                 (96 B per alt_bn128 G1 point x points per launch) over its
                 mean duration from HIP events on the launch stream, against the 8 TB/s
                 HBM peak.  The path is integer-ALU bound; the fraction is small by nature.
-  cpu_baseline  libff's own multi_exp (oracle/_ref, "reference") or the C restatement
+  cpu_baseline  (--full) libff's own multi_exp (oracle/_ref, "reference") or the C restatement
                 ("port") timed on the host cores of this box.
 """
 import argparse
@@ -112,7 +119,17 @@ def parse_args():
     ap.add_argument("--no-other-configs", action="store_true",
                     help="N = 1: skip the configs[2] / configs[4] legs (bls12_377 G1 2^22; bw6_761 G1 + bls12_377 G2 at 2^21 and 2^24)")
     ap.add_argument("--config4-log2n", type=int, default=24, help="N > 1: total points of the configs[4] leg; 0 disables")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the legs (other sizes, configurations and entry points), "
+                         "the CPU baseline and, at N > 1, the exchange timing; a plain run times the `value` workload only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the result of the last timed step to DIR/msm_result.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:   # a plain run: the `value` workload alone (--full lets the --no-* switches decide)
+        args.no_legs = args.no_cpu_baseline = True
+    return args
 
 
 def self_launch(args):
@@ -313,6 +330,21 @@ def timed_msm(tm, eng, msm, bases, scalars, n, steps, warmup, window_bits=0, wan
     for tk in tickets[-60:]:   # the engine keeps the last 64 tickets
         phases.append(eng.get_timings(ticket=tk))
     return elapsed, phases
+
+
+def last_result(msm):
+    """The result buffer of the last step ShardedMsm.run issued (call after msm.synchronize())."""
+    return msm.result[(msm.k - 1) % msm.depth]
+
+
+def dump_outputs(directory, eng, curve, group, result):
+    """--dump-outputs: the point the last timed step returned, normalised on the device to libff's special form
+    (x, y, 1) -- the (X, Y, Z) words a step returns are not unique, the order of the bucket sums varies from run to
+    run -- as its little-endian 32-bit words in float64 (exact), in DIR/msm_result.npy."""
+    xyz = np.ascontiguousarray(result.detach().cpu().numpy()).view(np.uint64).reshape(1, -1)
+    special = eng.group_op(curve, group, 0, xyz, np.zeros_like(xyz), out_form=libff_amd.OUT_AFFINE)   # P + zero
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "msm_result.npy"), special.reshape(-1).view(np.uint32).astype(np.float64))
 
 
 def roofline_of(curve_name, curve, group, n_launch, plan, acc_ms, log2n_for_pmc):
@@ -524,6 +556,8 @@ def single_gpu(args, tm, eng, dev, curve, group):
     msm = ShardedMsm(eng, curve, group, depth=max(1, args.pipeline))
     eng.set_timing(True)
     elapsed, phases = timed_msm(tm, eng, msm, bases, scalars, n, args.steps, args.warmup, args.window_bits)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, curve, group, last_result(msm))
     acc = float(np.mean([p["accumulate_ms"] for p in phases]))
     legs = {}
 
@@ -773,22 +807,26 @@ def multi_gpu(args, tm, eng, dev, rank, world, curve, group):
     msm = ShardedMsm(eng, curve, group, depth=1)
     eng.set_timing(True)
     elapsed, phases = timed_msm(tm, eng, msm, bases, scalars, n, args.steps, args.warmup, args.window_bits)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, curve, group, last_result(msm))
     acc = float(np.mean([p["accumulate_ms"] for p in phases]))
     legs = {}
     # What the step should cost: this rank's shard MSM alone (HIP events around its kernels, max over
-    # ranks) + the exchange (all-gather of the partial points + k_sum_points), timed on its own.
+    # ranks) + the exchange (all-gather of the partial points + k_sum_points), timed on its own (--full).
     shard_ms = tm.max_over_ranks(float(np.mean([p["total_ms"] for p in phases])) * 1e-3) * 1e3
-    kx = 20
-    for _ in range(3):
-        msm.exchange_only(libff_amd.OUT_LIBFF)
-    msm.synchronize()
-    tm.fence()
-    tx = time.perf_counter()
-    for _ in range(kx):
-        msm.exchange_only(libff_amd.OUT_LIBFF)
-    msm.synchronize()
-    tm.fence()
-    exchange_ms = tm.max_over_ranks(time.perf_counter() - tx) / kx * 1e3
+    exchange_ms = None
+    if args.full:
+        kx = 20
+        for _ in range(3):
+            msm.exchange_only(libff_amd.OUT_LIBFF)
+        msm.synchronize()
+        tm.fence()
+        tx = time.perf_counter()
+        for _ in range(kx):
+            msm.exchange_only(libff_amd.OUT_LIBFF)
+        msm.synchronize()
+        tm.fence()
+        exchange_ms = tm.max_over_ranks(time.perf_counter() - tx) / kx * 1e3
 
     # the same total on rank 0 alone (what one GPU does with the whole input), the others wait
     if not args.no_legs:
@@ -891,7 +929,7 @@ def multi_gpu(args, tm, eng, dev, rank, world, curve, group):
             "phases_ms": mean_phases(phases),
             "shard_ms": shard_ms,
             "exchange_ms": exchange_ms,
-            "predicted_ms": shard_ms + exchange_ms,
+            "predicted_ms": shard_ms + exchange_ms if exchange_ms is not None else None,
             "predicted_note": "ms_per_step should equal shard_ms (the slowest rank's MSM over its 2^log2n / N points, HIP events) "
                               "+ exchange_ms (RCCL all-gather of N partial points + k_sum_points, timed back to back on its own); "
                               "DESIGN.md section 5 states the expected strong-scaling curve",

@@ -435,7 +435,7 @@ def test_bench_multi_rank_path_rehearsal():
     env = dict(os.environ, AMDMSM_BENCH_REHEARSAL="1")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--log2n", "21", "--config4-log2n", "15"], capture_output=True, text=True, timeout=900, env=env)
+                        "--log2n", "21", "--config4-log2n", "15", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [x for x in r.stdout.splitlines() if x.startswith("{")][-1]
     d = json.loads(line)

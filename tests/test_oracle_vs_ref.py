@@ -1,6 +1,6 @@
 """Validate the C restatement directly against the reference itself on seeded inputs.
-Runs only where oracle/_ref/libff_ref.so exists (this container; it travels to the GPU
-box as a prebuilt .so, the reference sources do not).  CPU only."""
+Where oracle/_ref/libff_ref.so exists the reference is called; elsewhere its answers to these
+very calls are replayed from tests/golden/ref_calls.npz (tests/ref_recorded.py).  CPU only."""
 import numpy as np
 import pytest
 

@@ -1,10 +1,10 @@
 #!/usr/bin/env bash
-# A/B on ONE box: `python bench.py` (headline + pipelined leg only) under each of the given environment settings, twice.
+# A/B on ONE box: `python bench.py --full` (headline + pipelined leg only) under each of the given environment settings, twice.
 #   tools/ab_bench.sh "AMDMSM_OVERLAP=1" "AMDMSM_OVERLAP=0" ...
 for rep in 1 2; do
 for e in "$@"; do
   echo -n "[$rep] $e : "
-  env $e python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --extra-log2n 0 --no-other-configs --no-next-rows --precomputed-c 0 --batch 4 2>/dev/null | python3 -c "
+  env $e python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --extra-log2n 0 --no-other-configs --no-next-rows --precomputed-c 0 --batch 4 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 p=d['config']['phases_ms']
