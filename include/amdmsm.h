@@ -51,7 +51,15 @@ enum {
     AMDMSM_CURVE_ALT_BN128 = 0,
     AMDMSM_CURVE_BLS12_377 = 1,
     AMDMSM_CURVE_BW6_761 = 2,
-    AMDMSM_CURVE_BLS12_381 = 3
+    AMDMSM_CURVE_BLS12_381 = 3,
+    /* MNT4-298 / MNT6-298 (libff/algebra/curves/mnt): MNT4 G1 and G2, MNT6 G1.  (MNT6, G2) -- coordinates in
+     * Fq3 -- is unsupported everywhere.  No endomorphism: amdmsm_opts.endomorphism is ignored, amdmsm_plan_ex
+     * reports endomorphism_used = 0, amdmsm_endomorphism_info and amdmsm_endomorphism_digits_device return
+     * AMDMSM_ERR_UNSUPPORTED.  The compressed
+     * record paths (amdmsm_multi_exp_stream_compressed[_file], amdmsm_disk_decode_device with compressed = 1)
+     * return AMDMSM_ERR_UNSUPPORTED, and the FFI has no MNT names. */
+    AMDMSM_CURVE_MNT4 = 4,
+    AMDMSM_CURVE_MNT6 = 5
 };
 enum { AMDMSM_G1 = 1, AMDMSM_G2 = 2 };
 /* multi_exp_base_form, multiexp.hpp:45-51 */

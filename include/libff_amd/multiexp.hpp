@@ -602,5 +602,14 @@ LIBFF_AMD_ROUTE_GROUP(libff::bls12_381_G2, libff::bls12_381_Fr, AMDMSM_CURVE_BLS
 LIBFF_AMD_ROUTE_GROUP(libff::bw6_761_G1, libff::bw6_761_Fr, AMDMSM_CURVE_BW6_761, AMDMSM_G1)
 LIBFF_AMD_ROUTE_GROUP(libff::bw6_761_G2, libff::bw6_761_Fr, AMDMSM_CURVE_BW6_761, AMDMSM_G2)
 #endif
+// MNT4-298 / MNT6-298 (not pulled in by LIBFF_AMD_ALL_CURVES: include mnt4_pp.hpp / mnt6_pp.hpp before this header to
+// route them).  mnt6_G2 (coordinates in Fq3) has no device implementation and keeps libff's CPU code.
+#ifdef MNT4_PP_HPP_
+LIBFF_AMD_ROUTE_GROUP(libff::mnt4_G1, libff::mnt4_Fr, AMDMSM_CURVE_MNT4, AMDMSM_G1)
+LIBFF_AMD_ROUTE_GROUP(libff::mnt4_G2, libff::mnt4_Fr, AMDMSM_CURVE_MNT4, AMDMSM_G2)
+#endif
+#ifdef MNT6_PP_HPP_
+LIBFF_AMD_ROUTE_GROUP(libff::mnt6_G1, libff::mnt6_Fr, AMDMSM_CURVE_MNT6, AMDMSM_G1)
+#endif
 
 #endif // LIBFF_AMD_MULTIEXP_HPP_

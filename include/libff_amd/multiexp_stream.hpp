@@ -127,6 +127,35 @@ GroupT gpu_multi_exp_stream_with_precompute(
     }                                                                          \
     }
 
+// the uncompressed forms only (the compressed-record decoder is written for a = 0): MNT4-298 / MNT6-298
+#define LIBFF_AMD_ROUTE_STREAM_UNCOMPRESSED(GROUP_T, FIELD_T)                  \
+    namespace libff                                                            \
+    {                                                                          \
+    template<>                                                                 \
+    inline GROUP_T                                                             \
+    multi_exp_stream<form_montgomery, compression_off, GROUP_T, FIELD_T>(      \
+        std::istream & base_elements_in,                                       \
+        const std::vector<FIELD_T> &exponents)                                 \
+    {                                                                          \
+        return libff_amd::gpu_multi_exp_stream<GROUP_T, FIELD_T>(              \
+            base_elements_in, exponents);                                      \
+    }                                                                          \
+    template<>                                                                 \
+    inline GROUP_T multi_exp_stream_with_precompute<                           \
+        form_montgomery,                                                       \
+        compression_off,                                                       \
+        GROUP_T,                                                               \
+        FIELD_T>(                                                              \
+        std::istream & precomputed_elements_in,                                \
+        const std::vector<FIELD_T> &exponents,                                 \
+        const size_t precompute_c)                                             \
+    {                                                                          \
+        return libff_amd::gpu_multi_exp_stream_with_precompute<               \
+            GROUP_T,                                                           \
+            FIELD_T>(precomputed_elements_in, exponents, precompute_c);        \
+    }                                                                          \
+    }
+
 #ifdef ALT_BN128_PP_HPP_
 LIBFF_AMD_ROUTE_STREAM(libff::alt_bn128_G1, libff::alt_bn128_Fr)
 LIBFF_AMD_ROUTE_STREAM(libff::alt_bn128_G2, libff::alt_bn128_Fr)
@@ -142,6 +171,14 @@ LIBFF_AMD_ROUTE_STREAM(libff::bls12_381_G2, libff::bls12_381_Fr)
 #ifdef BW6_761_PP_HPP_
 LIBFF_AMD_ROUTE_STREAM(libff::bw6_761_G1, libff::bw6_761_Fr)
 LIBFF_AMD_ROUTE_STREAM(libff::bw6_761_G2, libff::bw6_761_Fr)
+#endif
+
+#ifdef MNT4_PP_HPP_
+LIBFF_AMD_ROUTE_STREAM_UNCOMPRESSED(libff::mnt4_G1, libff::mnt4_Fr)
+LIBFF_AMD_ROUTE_STREAM_UNCOMPRESSED(libff::mnt4_G2, libff::mnt4_Fr)
+#endif
+#ifdef MNT6_PP_HPP_
+LIBFF_AMD_ROUTE_STREAM_UNCOMPRESSED(libff::mnt6_G1, libff::mnt6_Fr)
 #endif
 
 #endif // LIBFF_AMD_MULTIEXP_STREAM_HPP_

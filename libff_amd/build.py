@@ -17,7 +17,7 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 SO_PATH = os.path.join(HERE, "libamdmsm.so")
 
 GROUPS = ["alt_bn128_g1", "alt_bn128_g2", "bls12_377_g1", "bls12_377_g2", "bw6_761_g1", "bw6_761_g2",
-          "bls12_381_g1", "bls12_381_g2"]
+          "bls12_381_g1", "bls12_381_g2", "mnt4_g1", "mnt4_g2", "mnt6_g1"]
 # per-group code-generation policy (see fp.cuh Fp<P, INL> and msm_group.hip):
 #   AMDMSM_HOT_INLINE  inline the Montgomery product inside the bucket-accumulation loop
 #   AMDMSM_BENCH_BOTH  also build the inline variants of the throughput probes
@@ -59,6 +59,13 @@ for _g in ("bls12_377_g1", "bls12_381_g1"):
 for _g, _w in (("alt_bn128_g1", 3), ("bls12_377_g1", 2), ("bls12_381_g1", 2), ("bw6_761_g1", 2), ("bw6_761_g2", 2),
                ("alt_bn128_g2", 3), ("bls12_377_g2", 2), ("bls12_381_g2", 2)):
     GROUP_FLAGS[_g] = [f for f in GROUP_FLAGS[_g] if not f.startswith("-DAMDMSM_ACC_WAVES=")] + ["-DAMDMSM_ACC_RR=1", f"-DAMDMSM_ACC_WAVES={_w}"]
+# MNT4-298 / MNT6-298 G1 (a != 0, 10-word field): the 32-bit Montgomery accumulation loop -- rr.cuh's limb shapes and
+# doublings are written for the pairing fields and a = 0 -- at three waves per SIMD, products inlined in the hot loop
+# and in the cold kernels as for the other fields of fewer than 16 words
+for _g in ("mnt4_g1", "mnt6_g1"):
+    GROUP_FLAGS[_g] = GROUP_FLAGS[_g] + ["-DAMDMSM_COLD_INLINE=1", "-DAMDMSM_ACC_WAVES=3"]
+# MNT4 G2 (Fq2 = Fq[u]/(u^2 - 17), a' = 34): the 32-bit loop with whole Fq2 elements per lane, two waves per SIMD
+GROUP_FLAGS["mnt4_g2"] = GROUP_FLAGS["mnt4_g2"] + ["-DAMDMSM_ACC_WAVES=2"]
 ARCH = "gfx950"
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I" + INCLUDE, "-I" + CSRC,
           "-Wno-unused-result"]

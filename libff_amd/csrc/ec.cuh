@@ -1,5 +1,6 @@
-// Short-Weierstrass a = 0 group arithmetic in Jacobian coordinates, generic over
-// the coordinate field (Fq or Fq2).  Device-side counterpart of libff's per-curve
+// Short-Weierstrass group arithmetic in Jacobian coordinates, generic over the
+// coordinate field (Fq or Fq2), written for a = 0 with the a x term of the MNT curves
+// (y^2 = x^3 + a x + b, a = ec_coeff_a<E>) added to every doubling at compile time.  Device-side counterpart of libff's per-curve
 // group classes on the multi_exp path:
 //   jac_madd  <- G::mixed_add   alt_bn128_g1.cpp:208-283 (madd-2007-bl), same ladder of
 //                               special cases: acc==0 -> P; P==0 -> acc; equal -> dbl;
@@ -12,11 +13,35 @@
 // coordinates are not canonical) and converts at the boundary:
 //   (X:Y:Z)_jac  ->  (X*Z : Y : Z^3)_proj        [x = X/Z^2, y = Y/Z^3]
 // Affine points are (x, y) with (0, 0) standing for the point at infinity (never
-// on y^2 = x^3 + b, b != 0).
+// on y^2 = x^3 + a x + b, since b != 0 on every supported curve).
 #pragma once
 #include "fp2.cuh"
 
 namespace amdmsm {
+
+// Coefficient a of y^2 = x^3 + a x + b for points with coordinates of type E: 0 (every pairing-friendly curve here)
+// unless the translation unit of an a != 0 group (MNT4-298: 2, MNT6-298: 11) specialises it for its coordinate
+// types.  The doublings add the a term under `if constexpr`, so the a = 0 groups compile to the code they did before.
+template <class E>
+struct ec_coeff_a {
+    static constexpr int value = 0;
+};
+
+// r = K * a for a small compile-time K >= 1 by additions and doublings (no field product)
+template <int K, class E>
+AMDMSM_DEV void el_mul_small(E& r, const E& a) {
+    static_assert(K >= 1 && K < 256, "small constant");
+    if constexpr (K == 1) {
+        r = a;
+    } else if constexpr (K % 2 == 0) {
+        el_mul_small<K / 2>(r, a);
+        el_dbl(r, r);
+    } else {
+        E t;
+        el_mul_small<K - 1>(t, a);
+        el_add(r, t, a);
+    }
+}
 
 template <class E>
 struct Aff {
@@ -73,6 +98,12 @@ AMDMSM_DEV void jac_dbl(Jac<E>& r, const Jac<E>& p) {
     el_dbl(D, D);            // D = 2((X1+B)^2 - A - C)
     el_dbl(t, A);
     el_add(A, t, A);         // E = 3A   (kept in A)
+    if constexpr (ec_coeff_a<E>::value != 0) {   // E = 3A + a Z1^4 (dbl-2007-bl's M)
+        el_sqr(t, p.z);
+        el_sqr(t, t);
+        el_mul_small<ec_coeff_a<E>::value>(t, t);
+        el_add(A, A, t);
+    }
     el_sqr(F, A);            // F = E^2
     el_mul(t, p.y, p.z);     // Y1*Z1 (before X/Y are overwritten)
     el_dbl(B, D);
@@ -211,7 +242,7 @@ AMDMSM_DEV bool xyzz_is_inf(const Xyzz<E>& p) {
     return el_is_zero(p.zz);
 }
 
-// 2 * (affine p), mdbl-2008-s-1 with a = 0: 3M + 3S... written with products only
+// 2 * (affine p), mdbl-2008-s-1 (M = 3 X1^2 + a): 3M + 3S... written with products only
 template <class E>
 AMDMSM_DEV void xyzz_dbl_affine(Xyzz<E>& r, const Aff<E>& p) {
     E u, v, w, s, m, t;
@@ -222,6 +253,11 @@ AMDMSM_DEV void xyzz_dbl_affine(Xyzz<E>& r, const Aff<E>& p) {
     el_sqr(m, p.x);
     el_dbl(t, m);
     el_add(m, t, m);           // M = 3*X1^2
+    if constexpr (ec_coeff_a<E>::value != 0) {
+        el_one(t);
+        el_mul_small<ec_coeff_a<E>::value>(t, t);
+        el_add(m, m, t);       // M = 3*X1^2 + a
+    }
     el_sqr(t, m);
     el_sub(t, t, s);
     el_sub(r.x, t, s);         // X3 = M^2 - 2S
@@ -233,7 +269,7 @@ AMDMSM_DEV void xyzz_dbl_affine(Xyzz<E>& r, const Aff<E>& p) {
     r.zzz = w;
 }
 
-// 2 * a, dbl-2008-s-1 with a = 0 (6M + 3S)
+// 2 * a, dbl-2008-s-1 (M = 3 X1^2 + a ZZ1^2; 6M + 3S for a = 0)
 template <class E>
 AMDMSM_DEV void xyzz_dbl(Xyzz<E>& r, const Xyzz<E>& a) {
     if (xyzz_is_inf(a)) {
@@ -248,6 +284,11 @@ AMDMSM_DEV void xyzz_dbl(Xyzz<E>& r, const Xyzz<E>& a) {
     el_sqr(m, a.x);
     el_dbl(t, m);
     el_add(m, t, m);
+    if constexpr (ec_coeff_a<E>::value != 0) {
+        el_sqr(t, a.zz);
+        el_mul_small<ec_coeff_a<E>::value>(t, t);
+        el_add(m, m, t);
+    }
     el_sqr(t, m);
     el_sub(t, t, s);
     el_mul(u, w, a.y);         // W*Y1 (before Y is overwritten)
@@ -427,9 +468,52 @@ AMDMSM_DEV void jac_shfl_xor(Jac<E>& r, const Jac<E>& p, int mask) {
 // lane holds the same point on entry and on exit.  Used where one point is doubled many
 // times in a row and the wave has nothing else to do (the c doublings between windows,
 // multiexp.tcc:614-616).  All 64 lanes must be active.
+// For a != 0 a fourth round: lane 3 squares Z in round 1 and ZZ in round 2, E = 3 XX + a Z^4, F = E^2 in round 3.
 template <class E>
 AMDMSM_DEV void jac_dbl_lanes3(Jac<E>& p) {
     if (jac_is_inf(p)) return;   // wave-uniform: every lane holds the same point
+    if constexpr (ec_coeff_a<E>::value != 0) {
+        const int lane = (int)(threadIdx.x & 63);
+        const bool l0 = lane == 0, l01 = lane <= 1, l3 = lane == 3;
+        E u, v, r, XX, B, YZ, ZZ, C, D, F, E3, t;
+        // round 1:  lane 0: XX = X^2   lane 1: B = Y^2   lane 2: YZ = Y*Z   lane 3: ZZ = Z^2
+        el_select(u, l0, p.x, p.y);
+        el_select(u, l3, p.z, u);
+        el_select(v, l01 || l3, u, p.z);
+        el_mul(r, u, v);
+        el_shfl(XX, r, 0);
+        el_shfl(B, r, 1);
+        el_shfl(YZ, r, 2);
+        el_shfl(ZZ, r, 3);
+        el_add(t, p.x, B);        // X + B
+        // round 2:  lane 0: C = B^2   lane 1: (X+B)^2   lane 2: ZZ^2
+        el_select(u, l0, B, t);
+        el_select(u, l01, u, ZZ);
+        el_mul(r, u, u);
+        el_shfl(C, r, 0);
+        el_shfl(D, r, 1);
+        el_shfl(F, r, 2);
+        el_mul_small<ec_coeff_a<E>::value>(F, F);
+        el_dbl(t, XX);
+        el_add(E3, t, XX);
+        el_add(E3, E3, F);        // E = 3*XX + a*Z^4
+        el_sub(D, D, XX);
+        el_sub(D, D, C);
+        el_dbl(D, D);             // D = 2((X+B)^2 - XX - C)
+        // round 3: F = E^2
+        el_sqr(F, E3);
+        el_dbl(t, D);
+        el_sub(p.x, F, t);        // X3 = F - 2D
+        // round 4: E*(D - X3)
+        el_sub(t, D, p.x);
+        el_mul(t, E3, t);
+        el_dbl(C, C);
+        el_dbl(C, C);
+        el_dbl(C, C);             // 8C
+        el_sub(p.y, t, C);        // Y3
+        el_dbl(p.z, YZ);          // Z3 = 2*Y*Z
+        return;
+    }
     const int lane = (int)(threadIdx.x & 63);
     const bool l0 = lane == 0, l01 = lane <= 1;
     E u, v, r, XX, B, YZ, C, D, F, E3, t;

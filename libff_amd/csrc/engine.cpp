@@ -127,13 +127,13 @@ struct amdmsm_ctx {
 
 namespace {
 
-// The eight group translation units are linked weakly so a development build may carry a
+// The group translation units are linked weakly so a development build may carry a
 // subset (AMDMSM_GROUPS=... python -m libff_amd.build); absent groups report UNSUPPORTED.
 using vt_getter = const group_vtable *(*)();
 const group_vtable *find_vt(int curve, int group) {
     static const vt_getter getters[] = {
         vt_alt_bn128_g1, vt_alt_bn128_g2, vt_bls12_377_g1, vt_bls12_377_g2, vt_bw6_761_g1, vt_bw6_761_g2,
-        vt_bls12_381_g1, vt_bls12_381_g2,
+        vt_bls12_381_g1, vt_bls12_381_g2, vt_mnt4_g1, vt_mnt4_g2, vt_mnt6_g1,
     };
     for (vt_getter g : getters) {
         if (!g) continue;
@@ -142,6 +142,9 @@ const group_vtable *find_vt(int curve, int group) {
     }
     return nullptr;
 }
+
+// alignment of a libff record stride: the device loads coordinates 16 bytes at a time, 8 for the 10-word fields
+size_t rec_align(const group_vtable *vt) { return vt->fq_words % 4 ? 8 : 16; }
 
 int fail(amdmsm_ctx *ctx, int code, const std::string &msg) {
     if (ctx) ctx->err = msg;
@@ -489,6 +492,7 @@ bool use_endomorphism(const group_vtable *vt, size_t n, const amdmsm_opts *opts,
                                "(off: everywhere); on / force assert that every base lies in the order-r subgroup\n", e);
         return v;
     }();
+    if (!vt->has_endomorphism) return false;   // MNT4 / MNT6: every amdmsm_opts.endomorphism value is ignored
     if (table_digits || n == 0 || n >= ((size_t)1 << 30)) return false;
     const int c_req = opts ? opts->window_bits : 0;
     if (c_req > 22) return false;
@@ -1214,7 +1218,7 @@ int amdmsm_msm_precomputed_device(amdmsm_ctx *ctx, int curve, int group, const v
 int amdmsm_import_bases_device(amdmsm_ctx *ctx, int curve, int group, const void *d_src_xyz, size_t stride_bytes,
                                int base_form, size_t n, void *d_dst_affine, void *stream) {
     GET_VT(ctx, curve, group);
-    if (stride_bytes % 16 || stride_bytes < (size_t)vt->el_words * 12) return fail(ctx, AMDMSM_ERR_BAD_ARG, "stride");
+    if (stride_bytes % rec_align(vt) || stride_bytes < (size_t)vt->el_words * 12) return fail(ctx, AMDMSM_ERR_BAD_ARG, "stride");
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     vt->import_bases(st, (const uint32_t *)d_src_xyz, stride_bytes / 4, base_form == AMDMSM_FORM_SPECIAL, n,
                      (uint32_t *)d_dst_affine);
@@ -1281,6 +1285,7 @@ int amdmsm_digits_device(amdmsm_ctx *ctx, int curve, int group, const void *d_sc
 int amdmsm_endomorphism_digits_device(amdmsm_ctx *ctx, int curve, int group, const void *d_scalars, size_t n,
                                       int scalars_plain, int c, int num_windows, int32_t *d_out) {
     GET_VT(ctx, curve, group);
+    if (!vt->has_endomorphism) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "the group has no endomorphism");
     if (c < 2 || c > 24 || num_windows < 1) return fail(ctx, AMDMSM_ERR_BAD_ARG, "c / num_windows");
     vt->glv_digits(ctx->stream, (const uint32_t *)d_scalars, n, scalars_plain ? 0 : 1, c, num_windows, d_out);
     HIP_TRY(ctx, hipGetLastError());
@@ -1290,7 +1295,7 @@ int amdmsm_endomorphism_digits_device(amdmsm_ctx *ctx, int curve, int group, con
 
 int amdmsm_endomorphism_info(int curve, int group, void *lambda_plain, int *bound_log2_x1000, int *prime_order) {
     const group_vtable *vt = find_vt(curve, group);
-    if (!vt) return AMDMSM_ERR_UNSUPPORTED;
+    if (!vt || !vt->has_endomorphism) return AMDMSM_ERR_UNSUPPORTED;
     if (lambda_plain) memcpy(lambda_plain, vt->glv_lambda, (size_t)vt->fr_words * 4);
     if (bound_log2_x1000) *bound_log2_x1000 = vt->glv_bound_log2_x1000;
     if (prime_order) *prime_order = vt->prime_order;
@@ -1602,7 +1607,7 @@ int check_host_args(amdmsm_ctx *ctx, const group_vtable *vt, const void *bases_x
     if (!out_xyz || (n && (!bases_xyz || !scalars))) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null pointer");
     const size_t xyz_bytes = (size_t)vt->el_words * 12;
     if (stride == 0) stride = xyz_bytes;
-    if (stride % 16 || stride < xyz_bytes) return fail(ctx, AMDMSM_ERR_BAD_ARG, "base stride");
+    if (stride % rec_align(vt) || stride < xyz_bytes) return fail(ctx, AMDMSM_ERR_BAD_ARG, "base stride");
     return AMDMSM_OK;
 }
 
@@ -1736,7 +1741,7 @@ int amdmsm_register_bases(amdmsm_ctx *ctx, int curve, int group, const void *bas
     if (!bases_xyz || !n) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null / empty base vector");
     const size_t xyz_bytes = (size_t)vt->el_words * 12;
     if (base_stride_bytes == 0) base_stride_bytes = xyz_bytes;
-    if (base_stride_bytes % 16 || base_stride_bytes < xyz_bytes) return fail(ctx, AMDMSM_ERR_BAD_ARG, "base stride");
+    if (base_stride_bytes % rec_align(vt) || base_stride_bytes < xyz_bytes) return fail(ctx, AMDMSM_ERR_BAD_ARG, "base stride");
     // a re-registration of the same range replaces the old copy
     for (size_t i = ctx->bases.size(); i-- > 0;) {
         const base_entry &e = ctx->bases[i];
@@ -2146,12 +2151,16 @@ int amdmsm_multi_exp_stream_file(amdmsm_ctx *ctx, int curve, int group, const ch
 int amdmsm_multi_exp_stream_compressed(amdmsm_ctx *ctx, int curve, int group, amdmsm_read_fn read, void *read_ctx,
                                        const void *scalars, size_t n, size_t chunk_points, void *out_xyz,
                                        const amdmsm_opts *opts) {
+    const group_vtable *vt = find_vt(curve, group);
+    if (vt && vt->coeff_a_nonzero) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "compressed records: a != 0 curve");
     return stream_impl(ctx, curve, group, read, read_ctx, scalars, n, chunk_points, out_xyz, opts, 1, 0, true);
 }
 
 int amdmsm_multi_exp_stream_compressed_file(amdmsm_ctx *ctx, int curve, int group, const char *path, size_t offset_bytes,
                                             const void *scalars, size_t n, size_t chunk_points, void *out_xyz,
                                             const amdmsm_opts *opts) {
+    const group_vtable *vt = find_vt(curve, group);
+    if (vt && vt->coeff_a_nonzero) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "compressed records: a != 0 curve");
     return stream_file_impl(ctx, curve, group, path, offset_bytes, scalars, n, chunk_points, out_xyz, opts, 1, 0, true);
 }
 
@@ -2160,6 +2169,7 @@ int amdmsm_multi_exp_stream_compressed_file(amdmsm_ctx *ctx, int curve, int grou
 int amdmsm_disk_decode_device(amdmsm_ctx *ctx, int curve, int group, const void *d_records, size_t n, int compressed,
                               void *d_dst_affine, unsigned *status) {
     GET_VT(ctx, curve, group);
+    if (compressed && vt->coeff_a_nonzero) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "compressed records: a != 0 curve");
     if (n && (!d_records || !d_dst_affine)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null pointer");
     hipStream_t st = ctx->stream;
     unsigned hs = 0;

@@ -580,7 +580,17 @@ AMDMSM_DEV void fp_half(Fp<P, I>& r, const Fp<P, I>& a) {
 template <class P, bool I>
 AMDMSM_DEV void fp_load(Fp<P, I>& r, const uint32_t* __restrict__ p) {
     constexpr int N = P::N;
-    static_assert(N % 4 == 0, "limb count must be a multiple of 4 for 16-byte loads");
+    if constexpr (N % 4 != 0) {   // 10 words (MNT4 / MNT6): 8-byte loads
+        static_assert(N % 2 == 0, "limb count must be even for 8-byte loads");
+        const uint2* q = reinterpret_cast<const uint2*>(p);
+#pragma unroll
+        for (int i = 0; i < N / 2; ++i) {
+            const uint2 w = q[i];
+            r.v[2 * i + 0] = w.x;
+            r.v[2 * i + 1] = w.y;
+        }
+        return;
+    }
     const uint4* q = reinterpret_cast<const uint4*>(p);
 #pragma unroll
     for (int i = 0; i < N / 4; ++i) {
@@ -595,6 +605,13 @@ AMDMSM_DEV void fp_load(Fp<P, I>& r, const uint32_t* __restrict__ p) {
 template <class P, bool I>
 AMDMSM_DEV void fp_store(uint32_t* __restrict__ p, const Fp<P, I>& a) {
     constexpr int N = P::N;
+    if constexpr (N % 4 != 0) {
+        static_assert(N % 2 == 0, "limb count must be even for 8-byte stores");
+        uint2* q = reinterpret_cast<uint2*>(p);
+#pragma unroll
+        for (int i = 0; i < N / 2; ++i) q[i] = make_uint2(a.v[2 * i + 0], a.v[2 * i + 1]);
+        return;
+    }
     uint4* q = reinterpret_cast<uint4*>(p);
 #pragma unroll
     for (int i = 0; i < N / 4; ++i) {

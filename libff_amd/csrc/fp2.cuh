@@ -18,11 +18,18 @@ struct Fp2 {
     Fp<P, I> c0, c1;
 };
 
-// x * |NR| by additions, then negate (NR < 0)
+// x * |NR| by additions, then negate (NR < 0); NR = 17 (MNT4): 16 x + x
 template <class P, int NR, bool I>
 AMDMSM_DEV void fp_mul_nr(Fp<P, I>& r, const Fp<P, I>& x) {
-    static_assert(NR == -1 || NR == -5, "unsupported non-residue");
-    if (NR == -1) {
+    static_assert(NR == -1 || NR == -5 || NR == 17, "unsupported non-residue");
+    if constexpr (NR == 17) {
+        Fp<P, I> t;
+        fp_dbl(t, x);
+        fp_dbl(t, t);
+        fp_dbl(t, t);
+        fp_dbl(t, t);
+        fp_add(r, t, x);
+    } else if (NR == -1) {
         fp_neg(r, x);
     } else {
         Fp<P, I> t;
@@ -243,7 +250,14 @@ template <class P, bool I> AMDMSM_DEV void el_canon(Fp<P, I>& a) { fp_canon(a); 
 
 template <class P, int NR, bool I>
 AMDMSM_DEV void fp_mul_nr_lz(Fp<P, I>& r, const Fp<P, I>& x) {
-    if (NR == -1) {
+    if constexpr (NR == 17) {
+        Fp<P, I> t;
+        fp_add_lz(t, x, x);
+        fp_add_lz(t, t, t);
+        fp_add_lz(t, t, t);
+        fp_add_lz(t, t, t);
+        fp_add_lz(r, t, x);
+    } else if (NR == -1) {
         fp_neg_lz(r, x);
     } else {
         Fp<P, I> t;
@@ -275,7 +289,7 @@ AMDMSM_DEV void fp_nr_factor_lz(Fp<P, I>& r, const Fp<P, I>& x) {
 // (fp2.tcc:101-114) without its six additions / subtractions and five temporaries.
 template <class P, int NR, bool I>
 AMDMSM_DEV void el_mul_lz(Fp2<P, NR, I>& r, const Fp2<P, NR, I>& x, const Fp2<P, NR, I>& y) {
-    if constexpr (I) {
+    if constexpr (I && NR < 0) {   // (NR = 17, MNT4: Karatsuba below)
         Fp<P, I> n1, c0;
         fp_nr_factor_lz<P, NR, I>(n1, x.c1);
         // factor bounds: n1 <= 2p (NR = -1) or 10p (NR = -5): products up to 4 p^2 / 20 p^2
@@ -315,7 +329,7 @@ AMDMSM_DEV void el_sqr_lz(Fp2<P, NR, I>& r, const Fp2<P, NR, I>& x) {
 template <class P, int NR, bool I>
 AMDMSM_DEV void el_mul_sub_mul_lz(Fp2<P, NR, I>& r, const Fp2<P, NR, I>& a, const Fp2<P, NR, I>& b, const Fp2<P, NR, I>& c,
                                   const Fp2<P, NR, I>& d) {
-    if constexpr (I) {
+    if constexpr (I && NR < 0) {   // (NR = 17, MNT4: two products below)
         // NR = -1:  c0 = a0 b0 + (2p - a1) b1 + (2p - c0) d0 + c1 d1
         // NR = -5:  c0 = a0 b0 + (10p - 5 a1) b1 + (2p - c0) d0 + (5 c1) d1
         Fp<P, I> na1, nc0, nc1, pc1, r0;

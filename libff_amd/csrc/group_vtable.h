@@ -187,6 +187,11 @@ struct group_vtable {
     void (*mul_bench)(hipStream_t, uint32_t* inout, size_t nthreads, int iters, int inline_variant);
     void (*madd_bench)(hipStream_t, const uint32_t* pts_affine, uint32_t* out_xyz, size_t nthreads, int iters,
                        int inline_variant);
+
+    // the group has the endomorphism phi above (0: MNT4 / MNT6, whose glv_* entries are placeholders and whose
+    // amdmsm_opts.endomorphism is ignored); the curve has a != 0 (the compressed-record decoders assume a = 0)
+    int has_endomorphism;
+    int coeff_a_nonzero;
 };
 
 const group_vtable* vt_alt_bn128_g1() __attribute__((weak));
@@ -197,5 +202,8 @@ const group_vtable* vt_bw6_761_g1() __attribute__((weak));
 const group_vtable* vt_bw6_761_g2() __attribute__((weak));
 const group_vtable* vt_bls12_381_g1() __attribute__((weak));
 const group_vtable* vt_bls12_381_g2() __attribute__((weak));
+const group_vtable* vt_mnt4_g1() __attribute__((weak));
+const group_vtable* vt_mnt4_g2() __attribute__((weak));
+const group_vtable* vt_mnt6_g1() __attribute__((weak));
 
 }  // namespace amdmsm

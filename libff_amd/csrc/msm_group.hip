@@ -41,11 +41,25 @@
 #endif
 
 namespace amdmsm {
+// the a x term of y^2 = x^3 + a x + b in the doublings of ec.cuh (0 but for the MNT groups; MNT4 G2: a' = 34 in Fq)
+template <bool I>
+struct ec_coeff_a<Fp<AMDMSM_GROUP::fq, I>> {
+    static constexpr int value = AMDMSM_GROUP::DEG == 1 ? AMDMSM_GROUP::COEFF_A : 0;
+};
+template <int NR, bool I>
+struct ec_coeff_a<Fp2<AMDMSM_GROUP::fq, NR, I>> {
+    static constexpr int value = AMDMSM_GROUP::DEG == 2 ? AMDMSM_GROUP::COEFF_A : 0;
+};
 namespace {
 
 using GP = AMDMSM_GROUP;
 using FQ = typename GP::fq;
 using FR = typename GP::fr;
+static_assert(GP::COEFF_A == 0 || (!GP::HAS_ENDO && GP::SUBGROUP_CHECK == 0 && GP::LIBFF_PROJECTIVE),
+              "a != 0 is implemented for the MNT groups: no endomorphism, no subgroup test, projective records");
+#if AMDMSM_ACC_RR || AMDMSM_ACC_SPLIT
+static_assert(GP::COEFF_A == 0, "the reduced-radix and lane-pair accumulation loops are written for a = 0");
+#endif
 
 // Montgomery products are emitted inline only where AMDMSM_HOT_INLINE asks for it (the
 // bucket-accumulation loop of narrow fields); everywhere else they are calls to one
@@ -1724,7 +1738,7 @@ AMDMSM_DEV void sum_wide_add(const WideEnv<Q>& env, const uint32_t* a, const uin
         const uint32_t wi = F::word_index(env);
         uint32_t X1 = env.valid ? a[wi] : 0u, Y1 = env.valid ? a[EW + wi] : 0u, Z1 = env.valid ? a[2 * EW + wi] : 0u;
         const uint32_t X2 = env.valid ? b[wi] : 0u, Y2 = env.valid ? b[EW + wi] : 0u, Z2 = env.valid ? b[2 * EW + wi] : 0u;
-        jac_add_seq<F, Q>(env, X1, Y1, Z1, X2, Y2, Z2);
+        jac_add_seq<F, Q, GP::COEFF_A>(env, X1, Y1, Z1, X2, Y2, Z2);
         if (((threadIdx.x & 63u) >> 4) < 2 && env.valid) {
             o[wi] = X1;
             o[EW + wi] = Y1;
@@ -1733,7 +1747,7 @@ AMDMSM_DEV void sum_wide_add(const WideEnv<Q>& env, const uint32_t* a, const uin
     } else {
         uint32_t X1 = env.valid ? a[env.j] : 0u, Y1 = env.valid ? a[EW + env.j] : 0u, Z1 = env.valid ? a[2 * EW + env.j] : 0u;
         const uint32_t X2 = env.valid ? b[env.j] : 0u, Y2 = env.valid ? b[EW + env.j] : 0u, Z2 = env.valid ? b[2 * EW + env.j] : 0u;
-        if constexpr (Q::N < 16) jac_add_wide<Q>(env, X1, Y1, Z1, X2, Y2, Z2);
+        if constexpr (Q::N < 16) jac_add_wide<Q, GP::COEFF_A>(env, X1, Y1, Z1, X2, Y2, Z2);
         else jac_add_seq<WideFq<Q>, Q>(env, X1, Y1, Z1, X2, Y2, Z2);
         if ((threadIdx.x & 63u) < (uint32_t)Q::N) {
             o[env.j] = X1;
@@ -1920,11 +1934,13 @@ AMDMSM_DEV typename std::enable_if<(P::N < 16), void>::type horner_chain(Jac<Fp<
         if (!wide_is_zero(Z)) {
             // the c doublings as one run on 28-bit limbs with lazy linear operations (wide28.cuh:
             // 0.99 instead of 1.82 us each); very short runs do not repay the two conversions
-            if (c >= 4) jac_dbl_run28<P>(env, X, Y, Z, c);
+            // (a != 0: the doublings of wide.cuh, jac_dbl_run28 is written for a = 0)
+            if constexpr (GP::COEFF_A != 0) for (int i = 0; i < c; ++i) jac_dbl_wide<P, GP::COEFF_A>(env, X, Y, Z);
+            else if (c >= 4) jac_dbl_run28<P>(env, X, Y, Z, c);
             else for (int i = 0; i < c; ++i) jac_dbl_wide<P>(env, X, Y, Z);
         }
         load(window_sums + (size_t)w * XYZW, X2, Y2, Z2);
-        jac_add_wide<P>(env, X, Y, Z, X2, Y2, Z2);
+        jac_add_wide<P, GP::COEFF_A>(env, X, Y, Z, X2, Y2, Z2);
     }
     wide_to_packed(res.x, X);
     wide_to_packed(res.y, Y);
@@ -1986,11 +2002,13 @@ AMDMSM_DEV typename std::enable_if<(P::N < 16), void>::type horner_chain(Jac<Fp2
     for (; w >= 0; --w) {
         if (!wide_is_zero(Z)) {
             // runs of doublings on 28-bit limbs with lazy linear operations (wide28.cuh)
-            if (c >= 4) jac_dbl_run28q<P, NR>(env, X, Y, Z, c);
+            // (a != 0: jac_dbl_run28q is written for a = 0)
+            if constexpr (GP::COEFF_A != 0) for (int i = 0; i < c; ++i) jac_dbl_seq<F, P, GP::COEFF_A>(env, X, Y, Z);
+            else if (c >= 4) jac_dbl_run28q<P, NR>(env, X, Y, Z, c);
             else for (int i = 0; i < c; ++i) jac_dbl_seq<F, P>(env, X, Y, Z);
         }
         load(window_sums + (size_t)w * XYZW, X2, Y2, Z2);
-        jac_add_seq<F, P>(env, X, Y, Z, X2, Y2, Z2);
+        jac_add_seq<F, P, GP::COEFF_A>(env, X, Y, Z, X2, Y2, Z2);
     }
     wide_to_packed(res.x.c0, from_row(X, 0));
     wide_to_packed(res.x.c1, from_row(X, 1));
@@ -3217,6 +3235,7 @@ const group_vtable g_vt = {
     GLV::BOUND_LOG2_X1000, GP::SUBGROUP_CHECK == 0 ? 1 : 0, GLV::LAMBDA, l_endo_points, l_glv_digits,
     l_import_bases, l_precompute_table, l_count, l_scatter, l_scalar_stats, l_sort, l_accumulate, l_accumulate_resident_lanes, (AMDMSM_OVERLAP_OK && ACC_OVERLAP_LDS) ? 1 : 0, l_accumulate_fixup, l_reduce_segments, l_sum_butterfly, l_sum_block, l_reduce_rowcol, l_horner, l_horner_batch, l_sum_points,
     l_gen_bases_seq, l_export_affine, l_ffi_decode_points, l_ffi_decode_scalars, l_ffi_encode_point, l_disk_decode, l_disk_decode_compressed, l_fixed_base_exp, l_field_op, l_group_op, l_digits, l_mul_bench, l_madd_bench,
+    GP::HAS_ENDO ? 1 : 0, GP::COEFF_A != 0 ? 1 : 0,
 };
 
 }  // namespace

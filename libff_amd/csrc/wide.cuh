@@ -180,12 +180,46 @@ struct WideFq {
     static AMDMSM_DEV uint32_t dbl(const WideEnv<P>& e, uint32_t a) { return wide_add<P>(e, a, a); }
 };
 
+// K * a for a small compile-time K >= 1 by additions and doublings
+template <class P, int K>
+AMDMSM_DEV uint32_t wide_mul_small(const WideEnv<P>& e, uint32_t a) {
+    if constexpr (K == 1) return a;
+    else if constexpr (K % 2 == 0) return wide_dbl<P>(e, wide_mul_small<P, K / 2>(e, a));
+    else return wide_add<P>(e, wide_mul_small<P, K - 1>(e, a), a);
+}
+
 // Jacobian doubling, a = 0 (dbl-2009-l, the formulas of alt_bn128_g1.cpp:293-335), on a point
 // whose coordinates are quads replicated in every row; the independent products of a stage sit
-// in different rows.  Same value as jac_dbl (ec.cuh).
-template <class P>
+// in different rows.  Same value as jac_dbl (ec.cuh).  A != 0 (curve coefficient a, MNT): E = 3 XX + a Z^4
+// with Z^2 in row 3 of stage 1 and Z^4 in row 3 of stage 2, F = E^2 in a stage of its own -- four stages.
+template <class P, int A = 0>
 AMDMSM_DEV void jac_dbl_wide(const WideEnv<P>& e, uint32_t& X, uint32_t& Y, uint32_t& Z) {
     static_assert(WideEnv<P>::ROW == 16, "four rows");
+    if constexpr (A != 0) {
+        const uint32_t row = (threadIdx.x & 63u) >> 4;
+        // stage 1:  row 0: XX = X^2   row 1: B = Y^2   row 2: YZ = Y*Z   row 3: ZZ = Z^2
+        uint32_t u = row == 0 ? X : (row == 3 ? Z : Y);
+        uint32_t v = row == 0 ? X : (row == 1 ? Y : Z);
+        uint32_t r = wide_mul<P>(e, u, v);
+        const uint32_t XX = from_row(r, 0), YZ = from_row(r, 2), ZZ = from_row(r, 3);
+        const uint32_t B2 = wide_dbl<P>(e, from_row(r, 1));            // 2 Y^2
+        // stage 2:  row 0: B2^2 = 4C   row 1: X*B2 = 2 X B   rows 2, 3: ZZ^2 = Z^4
+        u = row == 0 ? B2 : (row == 1 ? X : ZZ);
+        v = row <= 1 ? B2 : ZZ;
+        r = wide_mul<P>(e, u, v);
+        const uint32_t C8 = wide_dbl<P>(e, from_row(r, 0));            // 8C
+        const uint32_t D = wide_dbl<P>(e, from_row(r, 1));             // D = 4 X B
+        const uint32_t E3 = wide_add<P>(e, wide_add<P>(e, wide_dbl<P>(e, XX), XX),
+                                        wide_mul_small<P, A>(e, from_row(r, 3)));   // E = 3 XX + a Z^4
+        // stage 3: F = E^2
+        const uint32_t F = wide_mul<P>(e, E3, E3);
+        X = wide_sub<P>(e, F, wide_dbl<P>(e, D));                      // X3 = F - 2D
+        // stage 4: E*(D - X3)
+        const uint32_t t = wide_mul<P>(e, E3, wide_sub<P>(e, D, X));
+        Y = wide_sub<P>(e, t, C8);
+        Z = wide_dbl<P>(e, YZ);
+        return;
+    }
     // dbl-2009-l with its linear operations trimmed (each one is a cross-lane carry resolution plus a
     // conditional subtraction here, comparable to a product step): with B2 = 2 Y^2,
     //   D = 2((X+B)^2 - XX - C) = 4 X B = 2 (X B2),   8C = 8 B^2 = 2 B2^2
@@ -241,8 +275,8 @@ AMDMSM_DEV bool wide_is_zero(uint32_t w) { return __ballot(w != 0u) == 0ull; }
 // General Jacobian addition (add-2007-bl with Z3 = 2*Z1*Z2*H, the product sequence of jac_add in
 // ec.cuh / alt_bn128_g1.cpp:134-206), sixteen products in five stages of up to four rows.
 // Points at infinity and P == Q are resolved here (wave-uniform branches); P == -Q falls out
-// of the formulas as Z3 = 0.
-template <class P>
+// of the formulas as Z3 = 0.  A: curve coefficient a (jac_dbl_wide).
+template <class P, int A = 0>
 AMDMSM_DEV void jac_add_wide(const WideEnv<P>& e, uint32_t& X1, uint32_t& Y1, uint32_t& Z1, uint32_t X2, uint32_t Y2,
                              uint32_t Z2) {
     if (wide_is_zero(Z2)) return;
@@ -266,7 +300,7 @@ AMDMSM_DEV void jac_add_wide(const WideEnv<P>& e, uint32_t& X1, uint32_t& Y1, ui
     const uint32_t s1 = from_row(r, 0), s2 = from_row(r, 1), ii = from_row(r, 2), zh = from_row(r, 3);
     const uint32_t rr = wide_dbl<P>(e, wide_sub<P>(e, s2, s1));
     if (wide_is_zero(h) && wide_is_zero(rr)) {   // the same point: double it
-        jac_dbl_wide<P>(e, X1, Y1, Z1);
+        jac_dbl_wide<P, A>(e, X1, Y1, Z1);
         return;
     }
     // stage 4:  J = H*I | V = U1*I | r^2
@@ -288,10 +322,14 @@ AMDMSM_DEV uint32_t row_swap(uint32_t w) { return (uint32_t)__shfl_xor((int)w, 1
 
 template <class P, int NR>
 struct WideFq2 {
-    static_assert(NR == -1 || NR == -5, "unsupported non-residue");
+    static_assert(NR == -1 || NR == -5 || NR == 17, "unsupported non-residue");
     // (c0, c1) from the products v0 = a0 b0, v1 = a1 b1, v2 = (a0 + a1)(b0 + b1), each replicated
     static AMDMSM_DEV uint32_t combine(const WideEnv<P>& e, uint32_t v0, uint32_t v1, uint32_t v2) {
         const bool odd = ((threadIdx.x >> 4) & 1u) != 0;
+        if constexpr (NR > 0) {   // c0 = v0 + NR v1 | c1 = v2 - v0 - v1
+            const uint32_t t = wide_mul_small<P, NR>(e, v1);
+            return odd ? wide_sub<P>(e, wide_sub<P>(e, v2, v0), v1) : wide_add<P>(e, v0, t);
+        }
         uint32_t t = v1;                                    // |NR| * v1
         if (NR == -5) t = wide_add<P>(e, wide_dbl<P>(e, wide_dbl<P>(e, v1)), v1);
         uint32_t x = wide_sub<P>(e, odd ? v2 : v0, odd ? v0 : t);   // c0 = v0 + NR v1 | v2 - v0
@@ -321,19 +359,21 @@ struct WideFq2 {
 };
 
 // The same Jacobian formulas as jac_dbl_wide / jac_add_wide, one product after the other, over
-// any quad field F (used for Fq2, whose products already fill the rows).
-template <class F, class P>
+// any quad field F (used for Fq2, whose products already fill the rows).  A: curve coefficient a as a small integer
+// (MNT4 G2: a' = 34 in Fq), E = 3 XX + a Z^4.
+template <class F, class P, int A = 0>
 AMDMSM_DEV void jac_dbl_seq(const WideEnv<P>& e, uint32_t& X, uint32_t& Y, uint32_t& Z) {
     // the trimmed form of jac_dbl_wide: B2 = 2 Y^2, D = 2 (X B2), 8C = 2 B2^2
     const uint32_t XX = F::sqr(e, X), B2 = F::dbl(e, F::sqr(e, Y)), YZ = F::mul(e, Y, Z);
-    const uint32_t E3 = F::add(e, F::dbl(e, XX), XX);
+    uint32_t E3 = F::add(e, F::dbl(e, XX), XX);
+    if constexpr (A != 0) E3 = F::add(e, E3, wide_mul_small<P, A>(e, F::sqr(e, F::sqr(e, Z))));
     const uint32_t C8 = F::dbl(e, F::sqr(e, B2));
     const uint32_t D = F::dbl(e, F::mul(e, X, B2));
     X = F::sub(e, F::sqr(e, E3), F::dbl(e, D));
     Y = F::sub(e, F::mul(e, E3, F::sub(e, D, X)), C8);
     Z = F::dbl(e, YZ);
 }
-template <class F, class P>
+template <class F, class P, int A = 0>
 AMDMSM_DEV void jac_add_seq(const WideEnv<P>& e, uint32_t& X1, uint32_t& Y1, uint32_t& Z1, uint32_t X2, uint32_t Y2,
                             uint32_t Z2) {
     if (wide_is_zero(Z2)) return;
@@ -348,7 +388,7 @@ AMDMSM_DEV void jac_add_seq(const WideEnv<P>& e, uint32_t& X1, uint32_t& Y1, uin
     const uint32_t s1 = F::mul(e, Y1, F::mul(e, Z2, z2z2)), s2 = F::mul(e, Y2, F::mul(e, Z1, z1z1));
     const uint32_t h = F::sub(e, u2, u1), rr = F::dbl(e, F::sub(e, s2, s1));
     if (wide_is_zero(h) && wide_is_zero(rr)) {
-        jac_dbl_seq<F, P>(e, X1, Y1, Z1);
+        jac_dbl_seq<F, P, A>(e, X1, Y1, Z1);
         return;
     }
     const uint32_t ii = F::sqr(e, F::dbl(e, h));

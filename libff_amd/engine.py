@@ -21,9 +21,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("AMDMSM_LIBRARY") or os.path.join(HERE, "libamdmsm.so")
 
 # curve / group ids (include/amdmsm.h)
-ALT_BN128, BLS12_377, BW6_761, BLS12_381 = 0, 1, 2, 3
+ALT_BN128, BLS12_377, BW6_761, BLS12_381, MNT4, MNT6 = 0, 1, 2, 3, 4, 5   # MNT4 / MNT6: G1 only
 G1, G2 = 1, 2
-CURVE_NAMES = {ALT_BN128: "alt_bn128", BLS12_377: "bls12_377", BW6_761: "bw6_761", BLS12_381: "bls12_381"}
+CURVE_NAMES = {ALT_BN128: "alt_bn128", BLS12_377: "bls12_377", BW6_761: "bw6_761", BLS12_381: "bls12_381",
+               MNT4: "mnt4", MNT6: "mnt6"}
 
 # libff::multi_exp_method, multiexp.hpp:21-43
 multi_exp_method_naive = 0

@@ -105,6 +105,37 @@ CURVES = {
     ),
 }
 
+# MNT4-298 / MNT6-298 (libff/algebra/curves/mnt: mnt4_init.cpp, mnt6_init.cpp), a cycle: mnt4's Fr is mnt6's Fq and the
+# other way round.  y^2 = x^3 + a x + b with a != 0, homogeneous projective (X : Y : Z) in memory, no endomorphism
+# (prime-order G1, no efficiently computable phi): device header only, the C restatement does not cover them.
+MNT46_A = int("475922286169261325753349249653048451545124878552" "823515553267735739164647307408490559963137")
+MNT46_B = int("475922286169261325753349249653048451545124879242" "694725395555128576210262817955800483758081")
+MNT_CURVES = {
+    "mnt4": dict(
+        id=4, r=MNT46_A, q=MNT46_B, coords="projective",
+        g1=dict(deg=1, a=2,
+                x=[int("60760244141852568949126569781626075788424196370144486719385562" "369396875346601926534016838")],
+                y=[int("36373285070258297826390277081514578445974772235707184397110767" "4179038674942891694705904306")],
+                b=[int("42389453652668417828941601153388824002931810367" "3896002803341544124054745019340795360841685")],
+                subgroup="none"),   # mnt4_init.cpp:170-201; prime order, cofactor 1
+        # twist over Fq2 = Fq[u]/(u^2 - 17): a' = a * 17 (both components of mul_by_a), b' = (0, b * 17)
+        # (mnt4_init.cpp:144, 174-184, 263-274)
+        g2=dict(deg=2, nr=17, a=34,
+                x=[int("4383749262193500998549191000778096818427835091637909918478" "67546339851681564223481322252708"),
+                   int("3762095361550048011093551436092327860546447645971239327767" "9280819942849043649216370485641")],
+                y=[int("3743740900852896826835252103493693184297354644137066311854" "3015118291998305624025037512482"),
+                   int("4246214795988938826723931903374206805975846958923171976461" "13820787463109735345923009077489")]),
+    ),
+    "mnt6": dict(
+        id=5, r=MNT46_B, q=MNT46_A, coords="projective",
+        g1=dict(deg=1, a=11,
+                x=[int("33668575288308222810928984635393710418569820937140417834296883" "8739115829740084426881123453")],
+                y=[int("40259629013978098970933270771656892077762203207376274986234237" "4583908837063963736098549800")],
+                b=[int("10670008051085173567796731963258535225645425120" "1367587890185989362936000262606668469523074")],
+                subgroup="none"),   # mnt6_init.cpp:192-226
+    ),
+}
+
 
 def limbs(v, n, bits):
     mask = (1 << bits) - 1
@@ -124,7 +155,7 @@ def on_curve(q, g):
     deg = g["deg"]
     if deg == 1:
         x, y, b = g["x"][0] % q, g["y"][0] % q, g["b"][0] % q
-        return (y * y - x * x * x - b) % q == 0
+        return (y * y - x * x * x - g.get("a", 0) * x - b) % q == 0
     nr = g["nr"] % q
 
     def mul(a, c):
@@ -321,7 +352,8 @@ def emit_device_header():
     w("")
     w("namespace amdmsm {")
     w("")
-    w("enum curve_id : int { CURVE_ALT_BN128 = 0, CURVE_BLS12_377 = 1, CURVE_BW6_761 = 2, CURVE_BLS12_381 = 3 };")
+    w("enum curve_id : int { CURVE_ALT_BN128 = 0, CURVE_BLS12_377 = 1, CURVE_BW6_761 = 2, CURVE_BLS12_381 = 3, "
+      "CURVE_MNT4 = 4, CURVE_MNT6 = 5 };")
     w("enum group_id : int { GROUP_G1 = 1, GROUP_G2 = 2 };")
     w("")
     done_fields = {}
@@ -355,7 +387,7 @@ def emit_device_header():
         w("};")
         w("")
 
-    for cname, c in CURVES.items():
+    for cname, c in {**CURVES, **MNT_CURVES}.items():
         emit_field(f"{cname}_fr", c["r"])
         emit_field(f"{cname}_fq", c["q"])
     glv = {}
@@ -413,6 +445,8 @@ def emit_device_header():
               "  // libff in-memory coords are homogeneous projective")
             w(f"    static constexpr int NR_SMALL = {g.get('nr', 0)};     // Fq2 = Fq[u]/(u^2 - NR); 0 when DEG == 1")
             sub = g.get("subgroup", "order")
+            w(f"    static constexpr int COEFF_A = 0;       // y^2 = x^3 + COEFF_A x + b")
+            w(f"    static constexpr bool HAS_ENDO = true;   // phi(x, y) = (GLV_BETA x, y): the GLV split applies")
             w(f"    static constexpr int SUBGROUP_CHECK = {dict(none=0, order=3, endo=2)[sub]};   "
               "// 0 none, 1 [r]P == 0, 2 P + [c1]sigma(P) == 0, 3 [a]P + [b]phi(P) == 0 (glv::SUB_*; equivalent to 1)")
             if sub == "endo":
@@ -430,6 +464,58 @@ def emit_device_header():
                 w(f"    static constexpr uint32_t GEN_{coord.upper()}[{n * deg}] = {c_arr(vals, '0x%08xu')};"
                   if coord != "b" else
                   f"    static constexpr uint32_t COEFF_B[{n * deg}] = {c_arr(vals, '0x%08xu')};")
+            w("};")
+            w("")
+    for cname, c in MNT_CURVES.items():
+        fq, fr = field(c["q"]), field(c["r"])
+        n, frw = fq["n32"], fr["n32"]
+        w(f"// {cname}: no endomorphism.  Zero placeholders so that the shared GLV code compiles; the vtable reports")
+        w(f"// has_endomorphism = 0 and the engine never takes the split for this curve.")
+        w(f"struct {cname}_glv {{")
+        w("    static constexpr int HW = 1, GW = 1, CW = 1, BOUND_LOG2_X1000 = 0, SUB_BITS = 1, SUB_W = 1;")
+        w("    static constexpr uint32_t G1[1] = {0u}, G2[1] = {0u};")
+        w("    static constexpr uint32_t M[4][2] = {{0u, 0u}, {0u, 0u}, {0u, 0u}, {0u, 0u}};")
+        w(f"    static constexpr uint32_t LAMBDA[{frw}] = {c_arr([0] * frw, '%du')};")
+        w("    static constexpr uint32_t SUB_A_POS[1] = {0u}, SUB_A_NEG[1] = {0u}, SUB_B_POS[1] = {0u}, SUB_B_NEG[1] = {0u};")
+        w("};")
+        w("")
+        q = c["q"]
+        for gname in ("g1", "g2"):
+            if gname not in c:
+                continue
+            g = c[gname]
+            deg = g["deg"]
+            if deg == 1:
+                assert on_curve(q, g), cname
+                xs, ys, bs = [g["x"][0]], [g["y"][0]], [g["b"][0]]
+            else:   # the twist: b' = (0, b * NR)
+                nr = g["nr"]
+                mul = lambda u, v: ((u[0] * v[0] + nr * u[1] * v[1]) % q, (u[0] * v[1] + u[1] * v[0]) % q)
+                xs, ys, bs = g["x"], g["y"], [0, c["g1"]["b"][0] * nr % q]
+                x3 = mul(mul(xs, xs), xs)
+                y2 = mul(ys, ys)
+                assert all((y2[i] - x3[i] - g["a"] * xs[i] - bs[i]) % q == 0 for i in range(2)), cname
+            assert 0 < g["a"] < 64
+            w(f"struct {cname}_{gname} {{")
+            w(f"    using fq = {cname}_fq;")
+            w(f"    using fr = {cname}_fr;")
+            w(f"    using glv = {cname}_glv;")
+            w(f"    static constexpr uint32_t GLV_BETA[{n}] = {c_arr([0] * n, '%du')};   // unused: no endomorphism")
+            w(f"    static constexpr int CURVE = {c['id']};")
+            w(f"    static constexpr int GROUP = {1 if gname == 'g1' else 2};")
+            w(f"    static constexpr int DEG = {deg};           // coordinate field = Fq^DEG")
+            w("    static constexpr bool LIBFF_PROJECTIVE = true;  // libff in-memory coords are homogeneous projective")
+            w(f"    static constexpr int NR_SMALL = {g.get('nr', 0)};     // Fq2 = Fq[u]/(u^2 - NR); 0 when DEG == 1")
+            w(f"    static constexpr int COEFF_A = {g['a']};       // y^2 = x^3 + COEFF_A x + b (COEFF_A in Fq)")
+            w("    static constexpr bool HAS_ENDO = false;   // no efficiently computable endomorphism")
+            w("    static constexpr int SUBGROUP_CHECK = 0;   // no subgroup test (no decoder of this group validates)")
+            if deg == 2:
+                w(f"    static constexpr uint32_t NR_MONT[{n}] = {c_arr(limbs(g['nr'] * fq['R'] % q, n, 32), '0x%08xu')};")
+            for nm, vs in (("GEN_X", xs), ("GEN_Y", ys), ("COEFF_B", bs)):
+                v = []
+                for comp in vs:
+                    v += limbs(comp % q * fq["R"] % q, n, 32)
+                w(f"    static constexpr uint32_t {nm}[{n * deg}] = {c_arr(v, '0x%08xu')};")
             w("};")
             w("")
     w("} // namespace amdmsm")
