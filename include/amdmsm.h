@@ -154,13 +154,44 @@ int amdmsm_multi_exp_filter_one_zero(amdmsm_ctx *ctx, int curve, int group,
 int amdmsm_batch_to_special(amdmsm_ctx *ctx, int curve, int group, void *elems_xyz,
                             size_t stride_bytes, size_t n);
 
-/* k (<= 8) multi_exp calls of the same group, length and base form as ONE batch: what a prover that has several query
- * vectors of its proving key and their scalar vectors ready (libsnark r1cs_gg_ppzksnark_prover: A, B, L, H) hands over
- * instead of k calls of multiexp.tcc:643-688.  Same results as k amdmsm_multi_exp calls; the latency-bound tails of the
- * k MSMs run as one set of kernels (amdmsm_msm_device_batch).  Registered base vectors are honoured per MSM. */
+/* k (<= 8) multi_exp calls of the same group, length and base form as ONE batch: for a caller that has k base vectors
+ * of ONE length with a scalar vector each, instead of k calls of multiexp.tcc:643-688.  (The four G1 MSMs of libsnark's
+ * r1cs_gg_ppzksnark_prover -- A, B, L, H -- have different lengths and share the assignment as their scalar vector:
+ * that call sequence is amdmsm_multi_exp_batch_items below.)  Same results as k amdmsm_multi_exp calls; the
+ * latency-bound tails of the k MSMs run as one set of kernels (amdmsm_msm_device_batch).  Registered base vectors are
+ * honoured per MSM. */
 int amdmsm_multi_exp_batch(amdmsm_ctx *ctx, int curve, int group, int k, const void *const *bases_xyz,
                            size_t base_stride_bytes, int base_form, const void *const *scalars, size_t n,
                            void *const *out_xyz, const amdmsm_opts *opts);
+
+/* One MSM of a batch of MSMs of different lengths (amdmsm_multi_exp_batch_items / amdmsm_msm_device_batch_items).
+ * Its scalars are a vector of its own, or are taken from ONE vector the whole batch shares: a contiguous slice of it
+ * or the elements an index list names (libsnark's sparse_vector queries select the assignment's entries by index).
+ * The selection happens on the device inside the digit pass; the shared vector crosses PCIe once per call. */
+typedef struct amdmsm_batch_item {
+    uint32_t struct_size;  /* = sizeof(amdmsm_batch_item) (AMDMSM_BATCH_ITEM_INIT); an unknown size is refused */
+    const void *bases;     /* host entry: n libff (X, Y, Z) records (registered vectors are honoured);
+                              device entry: n compact affine records in HBM */
+    size_t n;              /* terms of this MSM; 0 gives the group's zero */
+    const void *scalars;   /* this MSM's own n scalars, or NULL: take them from the shared vector */
+    size_t shared_offset;  /* scalars == NULL, index == NULL: term i uses shared[shared_offset + i] */
+    const uint32_t *index; /* scalars == NULL: term i uses shared[index[i]]; any order, repeats allowed */
+    void *out_xyz;         /* one (X, Y, Z) record in opts->out_form */
+} amdmsm_batch_item;
+#define AMDMSM_BATCH_ITEM_INIT { (uint32_t)sizeof(amdmsm_batch_item) }
+
+/* k (1 .. 8) multi_exp calls of one group and base form, each of its own length, as ONE batch: one window size for the
+ * whole batch (chosen for the longest MSM), sort and accumulation MSM after MSM, the latency-bound tail once over the
+ * windows of all of them.  Same results as k amdmsm_multi_exp calls on the selected scalars.  shared_scalars (shared_n
+ * elements, may be NULL when every item brings its own) is uploaded once; own vectors and index lists per item.
+ * Everything is validated before anything is launched -- k, struct_size, a slice past shared_n, an index >= shared_n,
+ * scalars together with index, a missing shared vector, the stride rules of amdmsm_multi_exp: AMDMSM_ERR_BAD_ARG, the
+ * outputs untouched.  opts apply to the whole batch; window_bits > 22 is AMDMSM_ERR_BAD_ARG, as for
+ * amdmsm_multi_exp_batch.  A batch with sum n >= 2^30 or an item too long for one pass runs its MSMs one after the
+ * other, their scalars gathered on the device.  No filter_one_zero statistics, one group per batch, one device. */
+int amdmsm_multi_exp_batch_items(amdmsm_ctx *ctx, int curve, int group, int k, const amdmsm_batch_item *items,
+                                 size_t base_stride_bytes, int base_form, const void *shared_scalars, size_t shared_n,
+                                 const amdmsm_opts *opts);
 
 /* Resident base vectors.  A prover calls multi_exp with the same base vector (its proving key,
  * libsnark r1cs_gg_ppzksnark_proving_key) proof after proof; the reference re-reads it from host
@@ -280,6 +311,13 @@ int amdmsm_msm_device(amdmsm_ctx *ctx, int curve, int group, const void *d_bases
  * instead of once per MSM.  Same results as k single calls. */
 int amdmsm_msm_device_batch(amdmsm_ctx *ctx, int curve, int group, int k, const void *const *d_bases_affine,
                             const void *const *d_scalars, size_t n, void *const *d_out_xyz, const amdmsm_opts *opts);
+/* amdmsm_multi_exp_batch_items on device-resident inputs: every pointer inside items[] (the array itself is in host
+ * memory) and d_shared_scalars are HBM addresses, bases are compact affine.  Slices are checked on the host.  Index
+ * lists cannot be: the digit pass never dereferences an index >= shared_n -- it takes scalar 0 for it and raises a flag
+ * -- and a call that has index lists synchronises the stream to read that flag: AMDMSM_ERR_BAD_ARG names the item, the
+ * outputs of the batch are then meaningless.  Without index lists the call is asynchronous like amdmsm_msm_device. */
+int amdmsm_msm_device_batch_items(amdmsm_ctx *ctx, int curve, int group, int k, const amdmsm_batch_item *items,
+                                  const void *d_shared_scalars, size_t shared_n, const amdmsm_opts *opts);
 /* The same with the table resident in HBM (288 GB hold [2^(jc)]P for 2^26 alt_bn128 G1 bases):
  * amdmsm_precompute_bases_device fills d_table[i * num_digits + j] = [2^(j*c)] P_i (compact
  * affine, n * num_digits records) from compact affine bases -- the device-side

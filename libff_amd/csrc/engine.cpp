@@ -106,6 +106,7 @@ struct amdmsm_ctx {
     // host-buffer entry points: staging in HBM reused across calls, a second stream that brings
     // the bases in while the scalars are already being sorted, and the resident base vectors
     grow_buf hb_src, hb_aff, hb_sc, hb_out, hb_stats;
+    grow_buf hb_idx, sel_flag, sel_gather;   // batch items: index lists, out-of-range flags, scalars gathered for one MSM
     hipStream_t copy_stream = nullptr;
     hipEvent_t bases_ready = nullptr, host_done = nullptr;
     // Several MSMs in flight (pipeline depth > 1), overlap by construction: the bulk of every MSM -- bucket sort
@@ -304,10 +305,10 @@ int choose_c(const group_vtable *vt, size_t n, bool glv = false, double *cost_ou
 // table_digits > 0: every scalar contributes table_digits entries (one per digit, pointing at
 // its precomputed multiple) to a single bucket set; n is then the number of ENTRIES.
 // glv: n counts the 2 x points digit columns of the endomorphism split
-// batch > 1: workspace for `batch` MSMs of the same shape side by side -- every per-window array holds batch * W windows, MSM j
+// batch > 1: workspace for `batch` MSMs side by side, each of at most n entries -- every per-window array holds batch * W windows, MSM j
 // owning windows [j * W, (j + 1) * W), so that the tail kernels run once over all of them (amdmsm_msm_device_batch)
 int make_plan(const group_vtable *vt, size_t n, int c_req, int L_req, plan_t &p, int S_req = 0, int table_digits = 0,
-              int G_req = 0, bool glv = false, bool overlap = false, int batch = 1) {
+              int G_req = 0, bool glv = false, bool overlap = false, int batch = 1, size_t big_words_min = 0) {
     if (c_req < 0 || c_req > 24 || c_req == 1) return AMDMSM_ERR_BAD_ARG;
     if (table_digits && (c_req < 2 || c_req > 22)) return AMDMSM_ERR_BAD_ARG;
     if (glv && (table_digits || c_req > 22)) return AMDMSM_ERR_BAD_ARG;
@@ -399,7 +400,8 @@ int make_plan(const group_vtable *vt, size_t n, int c_req, int L_req, plan_t &p,
     p.off_coarse = off;
     off = align_up(off + Wt * 1025 * 4, 256);
     p.off_big = off;
-    p.big_stride = p.c <= 22 ? align_up(sort_geometry(n, p.c, p.W).big_words * 4, 256) : 256;   // per MSM of a batch
+    // (big_words_min: a batch of MSMs of different lengths passes the largest need of any of its lengths)
+    p.big_stride = p.c <= 22 ? align_up(std::max(sort_geometry(n, p.c, p.W).big_words, big_words_min) * 4, 256) : 256;   // per MSM of a batch
     off += p.big_stride * (size_t)batch;
     p.off_cursor = off;
     off = align_up(off + Wt * 1024 * 4, 256);
@@ -800,6 +802,142 @@ int msm_device_batch_impl(amdmsm_ctx *ctx, const group_vtable *vt, int k, const 
     return AMDMSM_OK;
 }
 
+int ensure_buf(amdmsm_ctx *ctx, grow_buf &b, size_t bytes);
+
+// One MSM of a ragged batch, every pointer an HBM address (amdmsm_batch_item after upload / as the device entry got it).
+struct item_dev {
+    const uint32_t *bases = nullptr;
+    size_t n = 0;
+    const uint32_t *scalars = nullptr;   // own vector; null: shared[index[i]] or shared[offset + i]
+    size_t offset = 0;
+    const uint32_t *index = nullptr;
+    uint32_t *out = nullptr;
+};
+
+// k MSMs of one group and of different lengths in one pass: msm_device_batch_impl with per-MSM n_j.
+// ONE plan for the batch -- window size, window count, endomorphism decision and lane length are those of the longest
+// MSM: sort and accumulation are linear in the entries, so the longest MSM carries most of their cost and is served
+// best by its own optimum, while the shared tail depends on (k W, B, c) only.  (Minimising the summed plan_cost would
+// also have to re-derive the measured small-size rules of choose_c for mixtures; with one long MSM beside short ones --
+// the prover's shape -- both rules pick the same c.)  Every per-MSM stride of the workspace is sized for that longest
+// MSM; a shorter one uses the front of its share, an empty one launches nothing and has its window ends and lane
+// markers cleared so that the shared tail finds empty windows.
+// flags: k words, zeroed here; word j becomes nonzero when MSM j named an element at or past shared_n.
+int msm_device_batch_items_impl(amdmsm_ctx *ctx, const group_vtable *vt, int k, const item_dev *it, const uint32_t *d_shared,
+                                size_t shared_n, uint32_t *flags, const amdmsm_opts *opts) {
+    hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : ctx->stream;
+    const int form = opts ? opts->out_form : AMDMSM_OUT_LIBFF;
+    const int mont = (opts && opts->scalars_plain) ? 0 : 1;
+    size_t n_max = 0;
+    for (int j = 0; j < k; ++j) n_max = std::max(n_max, it[j].n);
+    HIP_TRY(ctx, hipMemsetAsync(flags, 0, (size_t)k * 4, st));
+    if (n_max == 0) {
+        for (int j = 0; j < k; ++j) vt->sum_points(st, it[j].out, 0, form, it[j].out);
+        HIP_TRY(ctx, hipGetLastError());
+        return AMDMSM_OK;
+    }
+    const bool glv = use_endomorphism(vt, n_max, opts, 0);
+    const size_t entries = glv ? 2 * n_max : n_max;
+    const int c_req = opts ? opts->window_bits : 0;
+    if (c_req > 22) return fail(ctx, AMDMSM_ERR_BAD_ARG, "window_bits > 22 is not available for a batch");
+    plan_t p;
+    int rc;
+    {
+        // the sort geometry (coarse bits, chunk size, big-bin scratch) follows each MSM's own length: the scratch
+        // of every MSM is sized for the largest need of any length in the batch
+        plan_t p0;
+        rc = make_plan(vt, entries, c_req, opts ? opts->segment_len : 0, p0, 0, 0, 0, glv, false, k);
+        if (rc) return fail(ctx, rc, "bad window_bits / segment_len");
+        size_t big_words = 0;
+        for (int j = 0; j < k; ++j) {
+            if (it[j].n) big_words = std::max(big_words, sort_geometry(glv ? 2 * it[j].n : it[j].n, p0.c, p0.W).big_words);
+        }
+        rc = make_plan(vt, entries, p0.c, opts ? opts->segment_len : 0, p, 0, 0, 0, glv, false, k, big_words);
+        if (rc) return fail(ctx, rc, "bad window_bits / segment_len");
+    }
+    const int slot_idx = (int)(ctx->next++ % (unsigned)ctx->depth);
+    ws_slot &sl = ctx->slots[slot_idx];
+    ctx->last_slot = slot_idx;
+    if (sl.used) HIP_TRY(ctx, hipStreamWaitEvent(st, sl.done, 0));
+    rc = ensure_ws(ctx, sl, p.total);
+    if (rc) return rc;
+    char *ws = (char *)sl.ws;
+    const size_t zzw = (size_t)vt->bucket_words;
+    const size_t Wt = (size_t)p.W * (size_t)k;
+    uint32_t *counts = (uint32_t *)(ws + p.off_counts), *lists = (uint32_t *)(ws + p.off_lists);
+    uint32_t *buckets = (uint32_t *)(ws + p.off_buckets);
+    uint32_t *pfirst = (uint32_t *)(ws + p.off_pfirst), *plast = (uint32_t *)(ws + p.off_plast), *cont = (uint32_t *)(ws + p.off_cont);
+    record(ctx, sl, 0, st);
+    HIP_TRY(ctx, hipMemsetAsync(ws + p.off_coarse, 0, Wt * 1025 * 4, st));
+    for (int j = 0; j < k; ++j) HIP_TRY(ctx, hipMemsetAsync(ws + p.off_big + (size_t)j * p.big_stride, 0, 16, st));
+    HIP_TRY(ctx, hipMemsetAsync(buckets, 0, Wt * p.B * vt->bucket_words * 4, st));
+    HIP_TRY(ctx, hipMemsetAsync(ws + p.off_queue, 0, 8, st));
+    record(ctx, sl, 1, st);
+    bool first = true;
+    for (int j = 0; j < k; ++j) {
+        const size_t w0 = (size_t)j * p.W, n = it[j].n;
+        uint32_t *lists_j = lists + w0 * p.list_stride, *counts_j = counts + w0 * p.B;
+        if (n == 0) {
+            // no entries: every bucket of its windows ends at 0 and no lane continues a bucket (NO_BUCKET = ~0)
+            HIP_TRY(ctx, hipMemsetAsync(counts_j, 0, (size_t)p.W * p.B * 4, st));
+            HIP_TRY(ctx, hipMemsetAsync(cont + w0 * p.T, 0xff, (size_t)p.W * p.T * 4, st));
+            continue;
+        }
+        uint32_t *coarse_j = (uint32_t *)(ws + p.off_coarse) + w0 * 1025, *cursor_j = (uint32_t *)(ws + p.off_cursor) + w0 * 1024;
+        uint32_t *tmp_pay_j = (uint32_t *)(ws + p.off_tmp_payload) + w0 * p.list_stride;
+        uint32_t *tmp_key_j = (uint32_t *)(ws + p.off_tmp_key) + w0 * p.list_stride;
+        uint32_t *big_j = (uint32_t *)(ws + p.off_big + (size_t)j * p.big_stride);
+        if (it[j].scalars)
+            vt->sort(st, it[j].scalars, n, mont, p.c, p.W, coarse_j, cursor_j, (int32_t *)lists_j, tmp_pay_j, tmp_key_j, counts_j,
+                     lists_j, p.list_stride, big_j, glv ? 2 : 0, nullptr);
+        else
+            vt->sort_sel(st, d_shared, shared_n, it[j].index, it[j].offset, flags + j, n, mont, p.c, p.W, coarse_j, cursor_j,
+                         (int32_t *)lists_j, tmp_pay_j, tmp_key_j, counts_j, lists_j, p.list_stride, big_j, glv ? 2 : 0);
+        uint32_t *endo_j = glv ? (uint32_t *)(ws + p.off_endo + (size_t)j * p.endo_stride) : nullptr;
+        if (glv) vt->endo_points(st, it[j].bases, n, endo_j);
+        if (first) record(ctx, sl, 2, st);
+        first = false;
+        vt->accumulate(st, counts_j, lists_j, p.list_stride, it[j].bases, buckets + w0 * p.B * zzw, pfirst + w0 * p.T * zzw,
+                       plast + w0 * p.T * zzw, cont + w0 * p.T, p.W, p.B, p.S, p.T, endo_j, n, 0);
+    }
+    record(ctx, sl, 3, st);
+    vt->accumulate_fixup(st, counts, buckets, pfirst, plast, cont, (uint32_t *)(ws + p.off_queue), (int)Wt, p.B, p.S, p.T);
+    uint32_t *src;
+    if (p.rowcol) {
+        src = (uint32_t *)(ws + p.off_winsum);
+        vt->reduce_rowcol(st, buckets, (int)Wt, p.B, p.c, p.q_row, p.q_col, (uint32_t *)(ws + p.off_rc),
+                          (uint32_t *)(ws + p.off_planes), src);
+    } else {
+        src = (uint32_t *)(ws + p.off_lvl0);
+        uint32_t *dst = (uint32_t *)(ws + p.off_lvl1);
+        vt->reduce_segments(st, buckets, (int)Wt, p.B, p.L, src);
+        const uint32_t fold = (uint32_t)vt->reduce_fold;
+        uint32_t M = p.B / p.L;
+        M /= std::min<uint32_t>(M, fold);
+        while (M > 1) {
+            if ((size_t)M * (64 / fold) <= 256) {
+                vt->sum_block(st, src, (int)Wt, M, dst);
+                M = 1;
+            } else {
+                vt->sum_butterfly(st, src, (int)Wt, M, dst);
+                M /= std::min<uint32_t>(M, fold);
+            }
+            std::swap(src, dst);
+        }
+    }
+    record(ctx, sl, 4, st);
+    uint32_t *outs[MAX_BATCH];
+    for (int j = 0; j < k; ++j) outs[j] = it[j].out;
+    vt->horner_batch(st, src, k, p.W, p.c, form, outs);
+    record(ctx, sl, 5, st);
+    if (ctx->timing) sl.last_ticket = (long long)ctx->ticket++;
+    sl.ev_valid = ctx->timing;
+    HIP_TRY(ctx, hipEventRecord(sl.done, st));
+    sl.used = true;
+    HIP_TRY(ctx, hipGetLastError());
+    return AMDMSM_OK;
+}
+
 int ensure_partials(amdmsm_ctx *ctx) {
     if (!ctx->chunk_partials) HIP_TRY(ctx, hipMalloc(&ctx->chunk_partials, MAX_RANGES * 3 * 24 * 2 * 4));
     return AMDMSM_OK;
@@ -834,6 +972,72 @@ int msm_device_ranges(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d
     vt->sum_points(st, (const uint32_t *)ctx->chunk_partials, (int)parts, form, d_out);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(st));   // the partials buffer is shared by the context
+    return AMDMSM_OK;
+}
+
+// A ragged batch on device-resident inputs: one pass where its limits hold (k <= 8, sum n_j < 2^30, every n_j within one
+// range), otherwise the MSMs one after the other through the single-MSM path, the scalars of an MSM that selects from
+// the shared vector gathered on the device first (same selection, same guard).  flags: see msm_device_batch_items_impl.
+int run_batch_items(amdmsm_ctx *ctx, const group_vtable *vt, int k, const item_dev *it, const uint32_t *d_shared, size_t shared_n,
+                    uint32_t *flags, const amdmsm_opts *opts) {
+    size_t sum = 0, n_max = 0;
+    for (int j = 0; j < k; ++j) {
+        sum += it[j].n;
+        n_max = std::max(n_max, it[j].n);
+    }
+    if (n_max <= max_range_points() && sum < ((size_t)1 << 30))
+        return msm_device_batch_items_impl(ctx, vt, k, it, d_shared, shared_n, flags, opts);
+    if (opts && opts->window_bits > 22) return fail(ctx, AMDMSM_ERR_BAD_ARG, "window_bits > 22 is not available for a batch");
+    hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : ctx->stream;
+    const size_t fr_bytes = (size_t)vt->fr_words * 4;
+    HIP_TRY(ctx, hipMemsetAsync(flags, 0, (size_t)k * 4, st));
+    for (int j = 0; j < k; ++j) {
+        const uint32_t *sc = it[j].scalars;
+        if (!sc && it[j].n) {
+            const int rc = ensure_buf(ctx, ctx->sel_gather, it[j].n * fr_bytes);   // (growing synchronises the device)
+            if (rc) return rc;
+            vt->gather_scalars(st, d_shared, shared_n, it[j].index, it[j].offset, flags + j, it[j].n, (uint32_t *)ctx->sel_gather.p);
+            HIP_TRY(ctx, hipGetLastError());
+            sc = (const uint32_t *)ctx->sel_gather.p;
+        }
+        const int rc = msm_device_ranges(ctx, vt, it[j].bases, sc, it[j].n, it[j].out, opts);
+        if (rc) return rc;
+    }
+    return AMDMSM_OK;
+}
+
+// argument rules the two batch-items entries share; host_side: the index lists can be read here
+int check_batch_items(amdmsm_ctx *ctx, int k, const amdmsm_batch_item *items, const void *shared, size_t shared_n, bool host_side) {
+    if (k < 1 || k > MAX_BATCH || !items) return fail(ctx, AMDMSM_ERR_BAD_ARG, "batch of 1 .. 8 MSMs");
+    for (int j = 0; j < k; ++j) {
+        const amdmsm_batch_item &m = items[j];
+        const std::string who = "item " + std::to_string(j) + ": ";
+        if (m.struct_size != sizeof(amdmsm_batch_item))
+            return fail(ctx, AMDMSM_ERR_BAD_ARG, who + "amdmsm_batch_item.struct_size does not match this library: initialise with AMDMSM_BATCH_ITEM_INIT");
+        if (!m.out_xyz || (m.n && !m.bases)) return fail(ctx, AMDMSM_ERR_BAD_ARG, who + "null pointer");
+        if (m.n >= ((size_t)1 << 32)) return fail(ctx, AMDMSM_ERR_TOO_LARGE, who + "n must be < 2^32");
+        if (m.scalars && m.index) return fail(ctx, AMDMSM_ERR_BAD_ARG, who + "scalars and index are both given");
+        if (m.scalars || !m.n) continue;
+        if (!shared) return fail(ctx, AMDMSM_ERR_BAD_ARG, who + "scalars == NULL and there is no shared vector");
+        if (!m.index) {
+            if (m.shared_offset > shared_n || m.n > shared_n - m.shared_offset)
+                return fail(ctx, AMDMSM_ERR_BAD_ARG, who + "the slice [shared_offset, shared_offset + n) ends past shared_n");
+        } else if (host_side) {
+            for (size_t i = 0; i < m.n; ++i) {
+                if (m.index[i] >= shared_n)
+                    return fail(ctx, AMDMSM_ERR_BAD_ARG, who + "index[" + std::to_string(i) + "] = " + std::to_string(m.index[i]) + " >= shared_n");
+            }
+        }
+    }
+    return AMDMSM_OK;
+}
+
+// the flags of a finished batch (the stream has been synchronised): the first MSM that named a missing element
+int check_batch_flags(amdmsm_ctx *ctx, int k, const uint32_t *h_flags) {
+    for (int j = 0; j < k; ++j) {
+        if (h_flags[j])
+            return fail(ctx, AMDMSM_ERR_BAD_ARG, "item " + std::to_string(j) + ": an index >= shared_n (taken as scalar 0; the results of this batch are void)");
+    }
     return AMDMSM_OK;
 }
 
@@ -957,7 +1161,7 @@ void amdmsm_ctx_destroy(amdmsm_ctx *ctx) {
             if (ctx->ss.h_stage[b]) (void)hipHostFree(ctx->ss.h_stage[b]);
             if (ctx->ss.streams[b]) (void)hipStreamDestroy(ctx->ss.streams[b]);
         }
-        for (grow_buf *b : {&ctx->hb_src, &ctx->hb_aff, &ctx->hb_sc, &ctx->hb_out, &ctx->hb_stats, &ctx->fb.small, &ctx->fb.table,
+        for (grow_buf *b : {&ctx->hb_src, &ctx->hb_aff, &ctx->hb_sc, &ctx->hb_out, &ctx->hb_stats, &ctx->hb_idx, &ctx->sel_flag, &ctx->sel_gather, &ctx->fb.small, &ctx->fb.table,
                             &ctx->fb.table_aff, &ctx->fb.out, &ctx->ss.d_raw[0], &ctx->ss.d_raw[1], &ctx->ss.d_aff[0],
                             &ctx->ss.d_aff[1], &ctx->ss.d_sc[0], &ctx->ss.d_sc[1], &ctx->ss.partials, &ctx->ss.status}) {
             if (b->p) (void)hipFree(b->p);
@@ -1137,6 +1341,35 @@ int amdmsm_msm_device_batch(amdmsm_ctx *ctx, int curve, int group, int k, const 
     }
     return msm_device_batch_impl(ctx, vt, k, (const uint32_t *const *)d_bases_affine, (const uint32_t *const *)d_scalars, n,
                                  (uint32_t *const *)d_out_xyz, opts);
+}
+
+int amdmsm_msm_device_batch_items(amdmsm_ctx *ctx, int curve, int group, int k, const amdmsm_batch_item *items,
+                                  const void *d_shared_scalars, size_t shared_n, const amdmsm_opts *opts) {
+    GET_VT(ctx, curve, group);
+    CHECK_OPTS(ctx, opts);
+    int rc = check_batch_items(ctx, k, items, d_shared_scalars, shared_n, false);
+    if (rc) return rc;
+    rc = ensure_buf(ctx, ctx->sel_flag, MAX_BATCH * 4);
+    if (rc) return rc;
+    item_dev it[MAX_BATCH];
+    bool indexed = false;
+    for (int j = 0; j < k; ++j) {
+        it[j].bases = (const uint32_t *)items[j].bases;
+        it[j].n = items[j].n;
+        it[j].scalars = (const uint32_t *)items[j].scalars;
+        it[j].offset = items[j].shared_offset;
+        it[j].index = items[j].scalars ? nullptr : items[j].index;
+        it[j].out = (uint32_t *)items[j].out_xyz;
+        indexed = indexed || (it[j].index && it[j].n);
+    }
+    rc = run_batch_items(ctx, vt, k, it, (const uint32_t *)d_shared_scalars, shared_n, (uint32_t *)ctx->sel_flag.p, opts);
+    if (rc || !indexed) return rc;
+    // index lists live in HBM: whether one of them named a missing element is known once the digit passes have run
+    hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : ctx->stream;
+    uint32_t h_flags[MAX_BATCH] = {};
+    HIP_TRY(ctx, hipMemcpyAsync(h_flags, ctx->sel_flag.p, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return check_batch_flags(ctx, k, h_flags);
 }
 
 size_t amdmsm_precompute_num_digits(int curve, size_t c) {
@@ -1732,6 +1965,110 @@ int amdmsm_multi_exp_batch(amdmsm_ctx *ctx, int curve, int group, int k, const v
     }
     for (int j = 0; j < k; ++j) HIP_TRY(ctx, hipMemcpyAsync(out_xyz[j], d_o[j], xyz_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
+    return AMDMSM_OK;
+}
+
+// k multi_exp calls of one group, each of its own length, as one batch (amdmsm_msm_device_batch_items over host vectors).
+// The shared scalar vector crosses PCIe once, own vectors and index lists per item; bases as in amdmsm_multi_exp_batch.
+int amdmsm_multi_exp_batch_items(amdmsm_ctx *ctx, int curve, int group, int k, const amdmsm_batch_item *items,
+                                 size_t base_stride_bytes, int base_form, const void *shared_scalars, size_t shared_n,
+                                 const amdmsm_opts *opts) {
+    GET_VT(ctx, curve, group);
+    CHECK_OPTS(ctx, opts);
+    int rc = check_batch_items(ctx, k, items, shared_scalars, shared_n, true);
+    if (rc) return rc;
+    const size_t xyz_bytes = (size_t)vt->el_words * 12, aff_bytes = (size_t)vt->el_words * 8, fr_bytes = (size_t)vt->fr_words * 4;
+    size_t stride = base_stride_bytes ? base_stride_bytes : xyz_bytes;
+    if (stride % rec_align(vt) || stride < xyz_bytes) return fail(ctx, AMDMSM_ERR_BAD_ARG, "base stride");
+    if (opts && opts->window_bits > 22) return fail(ctx, AMDMSM_ERR_BAD_ARG, "window_bits > 22 is not available for a batch");
+    // staging: [shared | own vectors] in hb_sc, the index lists in hb_idx, imported bases of unregistered vectors in hb_aff
+    bool any_shared = false;
+    size_t sc_bytes = 0, idx_bytes = 0, max_src = 0;
+    for (int j = 0; j < k; ++j) {
+        const amdmsm_batch_item &m = items[j];
+        if (m.scalars) sc_bytes += align_up(m.n * fr_bytes, 256);
+        else if (m.n) any_shared = true;
+        if (!m.scalars && m.index) idx_bytes += align_up(m.n * 4, 256);
+    }
+    const size_t shared_bytes = any_shared ? align_up(shared_n * fr_bytes, 256) : 0;
+    hipStream_t st = ctx->stream;
+    rc = ensure_buf(ctx, ctx->hb_out, (size_t)MAX_BATCH * xyz_bytes);
+    if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->hb_sc, shared_bytes + sc_bytes);
+    if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->hb_idx, idx_bytes);
+    if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->sel_flag, MAX_BATCH * 4);
+    if (rc) return rc;
+    item_dev it[MAX_BATCH];
+    size_t aff_need = 0;
+    // resident vectors are pinned until the call returns (see amdmsm_multi_exp_batch)
+    struct unpin_all {
+        amdmsm_ctx *c;
+        ~unpin_all() {
+            for (auto &e : c->bases) e.pinned = false;
+        }
+    } unpin{ctx};
+    for (int j = 0; j < k; ++j) {
+        const amdmsm_batch_item &m = items[j];
+        it[j].n = m.n;
+        if (!m.n) continue;
+        base_entry *be = nullptr;
+        it[j].bases = (const uint32_t *)find_resident_bases(ctx, vt, m.bases, stride, base_form, m.n, &be);
+        if (!it[j].bases && auto_cache_bases(ctx, vt, m.bases, stride, base_form, m.n))
+            it[j].bases = (const uint32_t *)find_resident_bases(ctx, vt, m.bases, stride, base_form, m.n, &be);
+        if (it[j].bases && be) be->pinned = true;
+        if (!it[j].bases) {
+            aff_need += align_up(m.n * aff_bytes, 256);
+            max_src = std::max(max_src, m.n * stride);
+        }
+    }
+    if (aff_need) {
+        rc = ensure_buf(ctx, ctx->hb_src, max_src);
+        if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->hb_aff, aff_need);
+        if (rc) return rc;
+    }
+    if (any_shared) HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_sc.p, shared_scalars, shared_n * fr_bytes, hipMemcpyHostToDevice, st));
+    size_t sc_off = shared_bytes, idx_off = 0, aff_off = 0;
+    for (int j = 0; j < k; ++j) {
+        const amdmsm_batch_item &m = items[j];
+        it[j].out = (uint32_t *)((char *)ctx->hb_out.p + (size_t)j * xyz_bytes);
+        if (!m.n) continue;
+        if (m.scalars) {
+            it[j].scalars = (const uint32_t *)((char *)ctx->hb_sc.p + sc_off);
+            sc_off += align_up(m.n * fr_bytes, 256);
+            HIP_TRY(ctx, hipMemcpyAsync((void *)it[j].scalars, m.scalars, m.n * fr_bytes, hipMemcpyHostToDevice, st));
+        } else if (m.index) {
+            it[j].index = (const uint32_t *)((char *)ctx->hb_idx.p + idx_off);
+            idx_off += align_up(m.n * 4, 256);
+            HIP_TRY(ctx, hipMemcpyAsync((void *)it[j].index, m.index, m.n * 4, hipMemcpyHostToDevice, st));
+        } else {
+            it[j].offset = m.shared_offset;
+        }
+        if (!it[j].bases) {
+            uint32_t *aff = (uint32_t *)((char *)ctx->hb_aff.p + aff_off);
+            aff_off += align_up(m.n * aff_bytes, 256);
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_src.p, m.bases, m.n * stride, hipMemcpyHostToDevice, st));
+            vt->import_bases(st, (const uint32_t *)ctx->hb_src.p, stride / 4, base_form == AMDMSM_FORM_SPECIAL, m.n, aff);
+            HIP_TRY(ctx, hipGetLastError());
+            it[j].bases = aff;
+        }
+    }
+    amdmsm_opts o = AMDMSM_OPTS_INIT;
+    if (opts) o = *opts;
+    else o.out_form = AMDMSM_OUT_LIBFF;
+    o.stream = st;
+    rc = run_batch_items(ctx, vt, k, it, (const uint32_t *)ctx->hb_sc.p, shared_n, (uint32_t *)ctx->sel_flag.p, &o);
+    if (rc) {
+        (void)hipDeviceSynchronize();
+        return rc;
+    }
+    // results and flags back after one synchronisation; the outputs are written only when the whole batch is good
+    std::vector<char> h_out((size_t)k * xyz_bytes);
+    uint32_t h_flags[MAX_BATCH] = {};
+    HIP_TRY(ctx, hipMemcpyAsync(h_out.data(), ctx->hb_out.p, (size_t)k * xyz_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(h_flags, ctx->sel_flag.p, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    rc = check_batch_flags(ctx, k, h_flags);
+    if (rc) return rc;
+    for (int j = 0; j < k; ++j) memcpy(items[j].out_xyz, h_out.data() + (size_t)j * xyz_bytes, xyz_bytes);
     return AMDMSM_OK;
 }
 

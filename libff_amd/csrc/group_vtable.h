@@ -192,6 +192,18 @@ struct group_vtable {
     // amdmsm_opts.endomorphism is ignored); the curve has a != 0 (the compressed-record decoders assume a = 0)
     int has_endomorphism;
     int coeff_a_nonzero;
+
+    // `sort` with the scalar of base i taken from a vector of shared_n scalars that several MSMs share: element
+    // index[i] of it (index != null; any order, repeats allowed), else element offset + i.  Lists, payloads and every
+    // scratch argument are those of `sort` for n bases.  An element at or past shared_n is not read: it counts as
+    // scalar 0 and sets *flag (one word, cleared by the caller) to nonzero.
+    void (*sort_sel)(hipStream_t, const uint32_t* shared, size_t shared_n, const uint32_t* index, size_t offset,
+                     uint32_t* flag, size_t n, int mont, int c, int W, uint32_t* coarse, uint32_t* cursor, int32_t* digits,
+                     uint32_t* tmp_payload, uint32_t* tmp_key, uint32_t* ends, uint32_t* lists, size_t stride, uint32_t* big,
+                     int mode);
+    // out[i] = the scalar base i selects, copied as it is stored (same selection and guard as sort_sel)
+    void (*gather_scalars)(hipStream_t, const uint32_t* shared, size_t shared_n, const uint32_t* index, size_t offset,
+                           uint32_t* flag, size_t n, uint32_t* out);
 };
 
 const group_vtable* vt_alt_bn128_g1() __attribute__((weak));

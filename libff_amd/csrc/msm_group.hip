@@ -657,6 +657,90 @@ __global__ void __launch_bounds__(SORT_TPB) k_sort_digits(const uint32_t* __rest
     }
 }
 
+// Scalar selection (amdmsm_*_batch_items): the scalar of base i comes from a vector shared by several MSMs --
+// element index[i] of it (index list: any order, repeats allowed) or element offset + i (slice).  Only the load is
+// redirected; digit columns and payloads stay indexed by the base i.  An element at or past shared_n is never
+// dereferenced: it counts as scalar 0 and raises *flag, which the engine turns into AMDMSM_ERR_BAD_ARG.
+// Every lane still loads one whole scalar with 16-byte (10-word fields: 8-byte) loads, as the streaming form does.
+struct scalar_sel {
+    const uint32_t* index;   // null: slice
+    size_t offset, shared_n;
+    uint32_t* flag;
+};
+AMDMSM_DEV void load_scalar_sel(uint32_t (&s)[FRW], const uint32_t* shared, const scalar_sel& sel, size_t i, int mont) {
+    const size_t idx = sel.index ? (size_t)sel.index[i] : sel.offset + i;
+    if (idx >= sel.shared_n) {
+#pragma unroll
+        for (int j = 0; j < FRW; ++j) s[j] = 0;
+        atomicOr(sel.flag, 1u);
+        return;
+    }
+    load_scalar(s, shared, idx, mont);
+}
+
+// k_sort_digits with the selecting load.  A kernel of its own, body and all: sharing the body with k_sort_digits through
+// a template changed that kernel's register allocation, and the code of the existing call paths is to stay as it is.
+__global__ void __launch_bounds__(SORT_TPB) k_sort_digits_sel(const uint32_t* __restrict__ shared, size_t n, int mont, int c,
+                                                              int W, int hb, uint32_t per_block, int32_t* __restrict__ digits,
+                                                              size_t stride, uint32_t* __restrict__ coarse_counts, int mode,
+                                                              const uint32_t* __restrict__ index, size_t offset,
+                                                              size_t shared_n, uint32_t* __restrict__ flag) {
+    const scalar_sel sel{index, offset, shared_n, flag};
+    // mode 1 (flat): the W digits of scalar i are entries i*W .. i*W+W-1 of ONE list (they index a
+    // table of precomputed multiples [2^(jc)]P_i and share a single bucket set)
+    // mode 2 (endomorphism): scalar i gives two columns of W digits, i (k1, for P_i) and n + i
+    // (k2, for phi(P_i))
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];   // [W][2^hb]   (flat: [2^hb])
+    const bool flat = mode == 1;
+    const uint32_t nbin = 1u << hb;
+    const int fb = c - 1 - hb;
+    const uint32_t nctr = flat ? nbin : (uint32_t)W * nbin;
+    for (uint32_t j = threadIdx.x; j < nctr; j += SORT_TPB) smem[j] = 0;
+    __syncthreads();
+    const size_t base = (size_t)blockIdx.x * per_block;
+    for (uint32_t k = threadIdx.x; k < per_block; k += SORT_TPB) {
+        const size_t i = base + k;
+        if (i >= n) break;
+        uint32_t s[FRW];
+        load_scalar_sel(s, shared, sel, i, mont);
+        if (mode == 2) {
+            for_each_glv_digit(s, c, W, [&](int h, int w, int32_t d) {
+                digits[(size_t)w * stride + (h ? n + i : i)] = d;
+                if (d != 0) {
+                    const uint32_t idx = (uint32_t)(d < 0 ? -d : d) - 1u;
+                    atomicAdd(&smem[(uint32_t)w * nbin + (idx >> fb)], 1u);
+                }
+            });
+        } else {
+            for_each_signed_digit(s, c, W, [&](int w, int32_t d) {
+                digits[flat ? i * (size_t)W + w : (size_t)w * stride + i] = d;
+                if (d != 0) {
+                    const uint32_t idx = (uint32_t)(d < 0 ? -d : d) - 1u;
+                    atomicAdd(&smem[(flat ? 0u : (uint32_t)w * nbin) + (idx >> fb)], 1u);
+                }
+            });
+        }
+    }
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < nctr; j += SORT_TPB) {
+        const uint32_t v = smem[j];
+        if (v) atomicAdd(&coarse_counts[(j / nbin) * (nbin + 1) + (j % nbin)], v);
+    }
+}
+// out[i] = the scalar base i selects (the one-after-the-other route of a batch outside the limits of one pass)
+__global__ void __launch_bounds__(TPB) k_gather_scalars(const uint32_t* __restrict__ shared, size_t n,
+                                                        const uint32_t* __restrict__ index, size_t offset, size_t shared_n,
+                                                        uint32_t* __restrict__ flag, uint32_t* __restrict__ out) {
+    const size_t i = gtid();
+    if (i >= n) return;
+    uint32_t s[FRW];
+    load_scalar_sel(s, shared, scalar_sel{index, offset, shared_n, flag}, i, 0);
+    Fp<FR> x;
+#pragma unroll
+    for (int j = 0; j < FRW; ++j) x.v[j] = s[j];
+    fp_store(out + i * FRW, x);
+}
+
 // counts[w][0..nbin] -> exclusive starts (entry nbin = window total); cursor = copy of the starts
 __global__ void __launch_bounds__(SORT_TPB) k_sort_scan(uint32_t* __restrict__ coarse, uint32_t* __restrict__ cursor,
                                                         uint32_t nbin) {
@@ -2954,9 +3038,10 @@ void l_scatter(hipStream_t st, const uint32_t* scalars, size_t n, int mont, int 
     hipLaunchKernelGGL(k_scatter, dim3(blocks_for(n)), dim3(TPB), 0, st, scalars, n, mont, c, W, cursor, lists, list_stride);
 }
 // digits / lists may alias (digits are dead once k_sort_coarse has run)
-void l_sort(hipStream_t st, const uint32_t* scalars, size_t n, int mont, int c, int W, uint32_t* coarse,
-            uint32_t* cursor, int32_t* digits, uint32_t* tmp_payload, uint32_t* tmp_key, uint32_t* ends, uint32_t* lists,
-            size_t stride, uint32_t* big, int mode, hipEvent_t after_coarse) {
+// sel != null: the selecting form of the digit pass (group_vtable::sort_sel); everything behind it is the same
+void sort_launch(hipStream_t st, const uint32_t* scalars, size_t n, int mont, int c, int W, uint32_t* coarse,
+                 uint32_t* cursor, int32_t* digits, uint32_t* tmp_payload, uint32_t* tmp_key, uint32_t* ends, uint32_t* lists,
+                 size_t stride, uint32_t* big, int mode, hipEvent_t after_coarse, const scalar_sel* sel) {
     if (!n) return;
     // mode 1 (flat): one list of n*W entries (entry i*W + j = digit j of scalar i), one bucket set
     // mode 2 (endomorphism split): 2n columns of W digits
@@ -2969,8 +3054,13 @@ void l_sort(hipStream_t st, const uint32_t* scalars, size_t n, int mont, int c, 
     // scalars per k_sort_digits workgroup: enough workgroups for every CU, few enough global atomics
     uint32_t per_block = 8192;
     while (per_block > SORT_TPB && (n + per_block - 1) / per_block < 1024) per_block >>= 1;
-    hipLaunchKernelGGL(k_sort_digits, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(SORT_TPB),
-                       (size_t)(flat ? 1 : W) * nbin * 4, st, scalars, n, mont, c, W, hb, per_block, digits, stride, coarse, mode);
+    if (sel)
+        hipLaunchKernelGGL(k_sort_digits_sel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(SORT_TPB),
+                           (size_t)(flat ? 1 : W) * nbin * 4, st, scalars, n, mont, c, W, hb, per_block, digits, stride, coarse,
+                           mode, sel->index, sel->offset, sel->shared_n, sel->flag);
+    else
+        hipLaunchKernelGGL(k_sort_digits, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(SORT_TPB),
+                           (size_t)(flat ? 1 : W) * nbin * 4, st, scalars, n, mont, c, W, hb, per_block, digits, stride, coarse, mode);
     hipLaunchKernelGGL(k_sort_scan, dim3(We), dim3(SORT_TPB), 0, st, coarse, cursor, nbin);
     sort_key_t* tmp_key16 = reinterpret_cast<sort_key_t*>(tmp_key);   // W * stride fine keys
     hipLaunchKernelGGL(k_sort_coarse, dim3((unsigned)((ne + SORT_TILE - 1) / SORT_TILE), We), dim3(SORT_TPB), 0, st, digits,
@@ -2992,6 +3082,24 @@ void l_sort(hipStream_t st, const uint32_t* scalars, size_t n, int mont, int c, 
     const size_t big_lds = ((size_t)4 << sg.fb) * 4 + (size_t)SORT_TILE * 6;
     hipLaunchKernelGGL(k_sort_big_scatter, dim3(512), dim3(SORT_TPB), big_lds, st, tmp_payload, tmp_key16, coarse, stride, c,
                        hb, sg.big_cap, big, lists);
+}
+void l_sort(hipStream_t st, const uint32_t* scalars, size_t n, int mont, int c, int W, uint32_t* coarse,
+            uint32_t* cursor, int32_t* digits, uint32_t* tmp_payload, uint32_t* tmp_key, uint32_t* ends, uint32_t* lists,
+            size_t stride, uint32_t* big, int mode, hipEvent_t after_coarse) {
+    sort_launch(st, scalars, n, mont, c, W, coarse, cursor, digits, tmp_payload, tmp_key, ends, lists, stride, big, mode,
+                after_coarse, nullptr);
+}
+void l_sort_sel(hipStream_t st, const uint32_t* shared, size_t shared_n, const uint32_t* index, size_t offset, uint32_t* flag,
+                size_t n, int mont, int c, int W, uint32_t* coarse, uint32_t* cursor, int32_t* digits, uint32_t* tmp_payload,
+                uint32_t* tmp_key, uint32_t* ends, uint32_t* lists, size_t stride, uint32_t* big, int mode) {
+    const scalar_sel sel{index, offset, shared_n, flag};
+    sort_launch(st, shared, n, mont, c, W, coarse, cursor, digits, tmp_payload, tmp_key, ends, lists, stride, big, mode,
+                nullptr, &sel);
+}
+void l_gather_scalars(hipStream_t st, const uint32_t* shared, size_t shared_n, const uint32_t* index, size_t offset,
+                      uint32_t* flag, size_t n, uint32_t* out) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_gather_scalars, dim3(blocks_for(n)), dim3(TPB), 0, st, shared, n, index, offset, shared_n, flag, out);
 }
 size_t l_accumulate_resident_lanes(int overlap);
 // dynamic LDS that keeps one workgroup per CU out in overlap mode: with k workgroups resident by registers the
@@ -3235,7 +3343,7 @@ const group_vtable g_vt = {
     GLV::BOUND_LOG2_X1000, GP::SUBGROUP_CHECK == 0 ? 1 : 0, GLV::LAMBDA, l_endo_points, l_glv_digits,
     l_import_bases, l_precompute_table, l_count, l_scatter, l_scalar_stats, l_sort, l_accumulate, l_accumulate_resident_lanes, (AMDMSM_OVERLAP_OK && ACC_OVERLAP_LDS) ? 1 : 0, l_accumulate_fixup, l_reduce_segments, l_sum_butterfly, l_sum_block, l_reduce_rowcol, l_horner, l_horner_batch, l_sum_points,
     l_gen_bases_seq, l_export_affine, l_ffi_decode_points, l_ffi_decode_scalars, l_ffi_encode_point, l_disk_decode, l_disk_decode_compressed, l_fixed_base_exp, l_field_op, l_group_op, l_digits, l_mul_bench, l_madd_bench,
-    GP::HAS_ENDO ? 1 : 0, GP::COEFF_A != 0 ? 1 : 0,
+    GP::HAS_ENDO ? 1 : 0, GP::COEFF_A != 0 ? 1 : 0, l_sort_sel, l_gather_scalars,
 };
 
 }  // namespace

@@ -45,7 +45,8 @@ EXPORTED_SYMBOLS = [
     "amdmsm_abi_version", "amdmsm_device_count", "amdmsm_ctx_create", "amdmsm_ctx_destroy", "amdmsm_strerror",
     "amdmsm_last_error", "amdmsm_sizes", "amdmsm_plan", "amdmsm_plan_ex", "amdmsm_endomorphism_info",
     "amdmsm_endomorphism_digits_device", "amdmsm_pippenger_optimal_c",
-    "amdmsm_bdlo12_signed_optimal_c", "amdmsm_multi_exp", "amdmsm_multi_exp_batch", "amdmsm_multi_exp_filter_one_zero",
+    "amdmsm_bdlo12_signed_optimal_c", "amdmsm_multi_exp", "amdmsm_multi_exp_batch", "amdmsm_multi_exp_batch_items",
+    "amdmsm_msm_device_batch_items", "amdmsm_multi_exp_filter_one_zero",
     "amdmsm_multi_exp_multi", "amdmsm_multi_exp_filter_one_zero_multi", "amdmsm_msm_device_multi", "amdmsm_register_bases", "amdmsm_unregister_bases",
     "amdmsm_invalidate_bases",
     "amdmsm_batch_to_special", "amdmsm_batch_exp", "amdmsm_get_batch_exp_timings", "amdmsm_multi_exp_stream", "amdmsm_multi_exp_stream_file",
@@ -71,6 +72,22 @@ class _Opts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("window_bits", ctypes.c_int), ("segment_len", ctypes.c_int),
                 ("out_form", ctypes.c_int), ("scalars_plain", ctypes.c_int), ("endomorphism", ctypes.c_int),
                 ("stream", ctypes.c_void_p)]
+
+
+class BatchItemStruct(ctypes.Structure):
+    # include/amdmsm.h amdmsm_batch_item
+    _fields_ = [("struct_size", ctypes.c_uint32), ("bases", ctypes.c_void_p), ("n", ctypes.c_size_t),
+                ("scalars", ctypes.c_void_p), ("shared_offset", ctypes.c_size_t), ("index", ctypes.c_void_p),
+                ("out_xyz", ctypes.c_void_p)]
+
+
+class BatchItem:
+    """One MSM of ``Engine.multi_exp_batch_items``: ``bases`` and exactly one source of scalars -- ``scalars`` (its own
+    vector), ``index`` (a uint32 array into the shared vector; any order, repeats allowed) or ``offset`` (the slice
+    ``shared[offset : offset + len(bases)]``; the default is the prefix)."""
+
+    def __init__(self, bases, scalars=None, offset=0, index=None):
+        self.bases, self.scalars, self.offset, self.index = bases, scalars, offset, index
 
 
 _lib = None
@@ -317,6 +334,49 @@ class Engine:
         self._check(rc, "amdmsm_multi_exp_batch")
         return outs
 
+    def multi_exp_batch_items(self, curve, group, items, shared_scalars=None, base_form=multi_exp_base_form_normal,
+                              out_form=OUT_AFFINE, window_bits=0, scalars_plain=False):
+        """amdmsm_multi_exp_batch_items: up to 8 multi_exp calls of one group, each of its own length, as one batch.
+
+        ``items``: ``BatchItem`` objects or dicts with ``bases`` and one of ``scalars`` / ``offset`` / ``index``.  Items
+        without ``scalars`` take theirs from ``shared_scalars`` (uploaded once), selected on the device.  ``bases`` that
+        were registered must be passed as the very arrays (or row ranges of them).  Returns the list of results.
+        """
+        its = [BatchItem(**it) if isinstance(it, dict) else it for it in items]
+        k = len(its)
+        s = sizes(curve, group)
+        fr_limbs = s["fr_bytes"] // 8
+        shared = None if shared_scalars is None else np.ascontiguousarray(shared_scalars, dtype=np.uint64)
+        shared_n = 0 if shared is None else shared.shape[0]
+        if shared is not None and shared_n:
+            assert shared.shape == (shared_n, fr_limbs), "shared_scalars must be (shared_n, fr_limbs) uint64"
+        arr = (BatchItemStruct * max(k, 1))()
+        keep, outs = [], []
+        for j, it in enumerate(its):
+            b = np.ascontiguousarray(it.bases, dtype=np.uint64)   # (a contiguous uint64 array is passed through as it is)
+            n = b.shape[0] if b.ndim == 2 else 0
+            if n:
+                assert b.shape[1] * 8 == s["g_bytes"], "bases must be (n, 3*coord_limbs) uint64"
+            out = np.zeros(s["g_bytes"] // 8, dtype=np.uint64)
+            sc = idx = None
+            if it.scalars is not None:
+                sc = np.ascontiguousarray(it.scalars, dtype=np.uint64)
+                assert n == 0 or sc.shape == (n, fr_limbs), "scalars must be (n, fr_limbs) uint64"
+            if it.index is not None:
+                idx = np.ascontiguousarray(it.index, dtype=np.uint32)
+                assert idx.shape == (n,), "index must hold one uint32 per base"
+            keep += [b, sc, idx]
+            outs.append(out)
+            arr[j] = BatchItemStruct(ctypes.sizeof(BatchItemStruct), _np_ptr(b) if n else None, n,
+                                     _np_ptr(sc) if sc is not None and n else None, int(it.offset),
+                                     _np_ptr(idx) if idx is not None and n else None, _np_ptr(out))
+        o = self._opts(window_bits=window_bits, out_form=out_form, scalars_plain=scalars_plain)
+        rc = self.lib.amdmsm_multi_exp_batch_items(self.h, curve, group, k, arr, ctypes.c_size_t(s["g_bytes"]), base_form,
+                                                   _np_ptr(shared) if shared_n else None, ctypes.c_size_t(shared_n),
+                                                   ctypes.byref(o))
+        self._check(rc, "amdmsm_multi_exp_batch_items")
+        return outs
+
     def register_bases(self, curve, group, bases, base_form=multi_exp_base_form_normal):
         """amdmsm_register_bases: keep ``bases`` (the very numpy buffer -- the registry is keyed on its
         address) resident in HBM; later host-buffer calls on it or on row ranges of it skip the base
@@ -551,6 +611,23 @@ class Engine:
         o = self._opts(window_bits, 0, out_form, scalars_plain, stream)
         self._check(self.lib.amdmsm_msm_device_batch(self.h, curve, group, k, pb, ps, ctypes.c_size_t(n), po, ctypes.byref(o)),
                     "amdmsm_msm_device_batch")
+
+    def msm_device_batch_items(self, curve, group, items, d_shared_scalars=None, shared_n=0, out_form=OUT_LIBFF,
+                               window_bits=0, scalars_plain=False, stream=None):
+        """amdmsm_msm_device_batch_items: ``items`` are dicts of device pointers -- ``bases`` (compact affine), ``n``,
+        ``out`` and one of ``scalars`` / ``offset`` / ``index`` (a device array of n uint32).  A call with index lists
+        synchronises to learn whether an index was out of range (AmdMsmError)."""
+        k = len(items)
+        arr = (BatchItemStruct * max(k, 1))()
+        for j, it in enumerate(items):
+            arr[j] = BatchItemStruct(ctypes.sizeof(BatchItemStruct), _vp(it["bases"]) if it.get("bases") else None, int(it["n"]),
+                                     _vp(it["scalars"]) if it.get("scalars") else None, int(it.get("offset", 0)),
+                                     _vp(it["index"]) if it.get("index") else None, _vp(it["out"]))
+        o = self._opts(window_bits, 0, out_form, scalars_plain, stream)
+        self._check(self.lib.amdmsm_msm_device_batch_items(self.h, curve, group, k, arr,
+                                                           _vp(d_shared_scalars) if d_shared_scalars else None,
+                                                           ctypes.c_size_t(shared_n), ctypes.byref(o)),
+                    "amdmsm_msm_device_batch_items")
 
     def precompute_bases_device(self, curve, group, d_bases_affine, n, c, num_digits, d_table, stream=None):
         self._check(self.lib.amdmsm_precompute_bases_device(
