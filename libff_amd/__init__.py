@@ -3,6 +3,7 @@
 Only what the path needs lives here:
   csrc/            hand-written HIP kernels (gfx950) + the C-ABI engine (include/amdmsm.h)
   engine.py        host-side mirror of libff's multi_exp interface over the C ABI (ctypes)
+  ffi.py           the FFI-convention entry points (include/libff_amd_ffi.h) over byte buffers
   distributed.py   range-sharded multi-GPU MSM (one process per GPU, RCCL all-gather of partials)
   build.py         hipcc build of libamdmsm.so (in-tree)
 
@@ -15,6 +16,7 @@ from .engine import (  # noqa: F401
     multi_exp_method_BDLO12, multi_exp_method_BDLO12_signed, multi_exp_method_bos_coster,
     multi_exp_method_naive, multi_exp_method_naive_plain, multi_exp_multi, multi_exp_filter_one_zero_multi, msm_device_multi, pippenger_optimal_c, plan, precompute_num_digits, sizes,
     endomorphism_info)
+from . import ffi  # noqa: F401
 
 __all__ = [
     "ALT_BN128", "BLS12_377", "BLS12_381", "BW6_761", "MNT4", "MNT6", "G1", "G2", "OUT_AFFINE", "OUT_JACOBIAN", "OUT_LIBFF",
@@ -22,5 +24,5 @@ __all__ = [
     "multi_exp_base_form_special", "multi_exp_method_BDLO12", "multi_exp_method_BDLO12_signed",
     "multi_exp_method_bos_coster", "multi_exp_method_naive", "multi_exp_method_naive_plain", "multi_exp_multi",
     "multi_exp_filter_one_zero_multi", "msm_device_multi",
-    "pippenger_optimal_c", "plan", "precompute_num_digits", "sizes", "endomorphism_info",
+    "pippenger_optimal_c", "plan", "precompute_num_digits", "sizes", "endomorphism_info", "ffi",
 ]

@@ -55,8 +55,9 @@ namespace {
 using GP = AMDMSM_GROUP;
 using FQ = typename GP::fq;
 using FR = typename GP::fr;
-static_assert(GP::COEFF_A == 0 || (!GP::HAS_ENDO && GP::SUBGROUP_CHECK == 0 && GP::LIBFF_PROJECTIVE),
-              "a != 0 is implemented for the MNT groups: no endomorphism, no subgroup test, projective records");
+static_assert(GP::COEFF_A == 0 || (!GP::HAS_ENDO && (GP::SUBGROUP_CHECK == 0 || GP::SUBGROUP_CHECK == 1) && GP::LIBFF_PROJECTIVE),
+              "a != 0 is implemented for the MNT groups: no endomorphism, no subgroup test or [r]P == 0 on the plain "
+              "Jacobian ladder (the endomorphism and reduced-radix tests are a = 0 only), projective records");
 #if AMDMSM_ACC_RR || AMDMSM_ACC_SPLIT
 static_assert(GP::COEFF_A == 0, "the reduced-radix and lane-pair accumulation loops are written for a = 0");
 #endif
@@ -2812,13 +2813,18 @@ __global__ void __launch_bounds__(TPB, AMDMSM_FFI_WAVES) k_ffi_decode_points(con
     } else if (!bad) {
         el_to_mont(a.x, a.x);
         el_to_mont(a.y, a.y);
-        // is_well_formed: y^2 = x^3 + b (e.g. bls12_377_g1.cpp:367-385 with Z = 1)
+        // is_well_formed: y^2 = x^3 + a x + b (e.g. bls12_377_g1.cpp:367-385, mnt4_g2.cpp:430-452 with Z = 1)
         E y2, x3, b;
         el_sqr(y2, a.y);
         el_sqr(x3, a.x);
         el_mul(x3, x3, a.x);
         el_set_words(b, GP::COEFF_B);
         el_add(x3, x3, b);
+        if constexpr (GP::COEFF_A != 0) {   // a lies in Fq (MNT4 G2: a' = 34 scales both components), as in the doublings
+            E ax;
+            el_mul_small<ec_coeff_a<E>::value>(ax, a.x);
+            el_add(x3, x3, ax);
+        }
         if (!el_eq(y2, x3)) bad |= 2u;
         else if (!in_safe_subgroup(a)) bad |= 4u;
     }

@@ -120,7 +120,8 @@ MNT_CURVES = {
                 subgroup="none"),   # mnt4_init.cpp:170-201; prime order, cofactor 1
         # twist over Fq2 = Fq[u]/(u^2 - 17): a' = a * 17 (both components of mul_by_a), b' = (0, b * 17)
         # (mnt4_init.cpp:144, 174-184, 263-274)
-        g2=dict(deg=2, nr=17, a=34,
+        # is_in_safe_subgroup: zero() == scalar_field::mod * P (mnt4_g2.cpp:454-457; the twist has a cofactor)
+        g2=dict(deg=2, nr=17, a=34, subgroup="order",
                 x=[int("4383749262193500998549191000778096818427835091637909918478" "67546339851681564223481322252708"),
                    int("3762095361550048011093551436092327860546447645971239327767" "9280819942849043649216370485641")],
                 y=[int("3743740900852896826835252103493693184297354644137066311854" "3015118291998305624025037512482"),
@@ -508,7 +509,10 @@ def emit_device_header():
             w(f"    static constexpr int NR_SMALL = {g.get('nr', 0)};     // Fq2 = Fq[u]/(u^2 - NR); 0 when DEG == 1")
             w(f"    static constexpr int COEFF_A = {g['a']};       // y^2 = x^3 + COEFF_A x + b (COEFF_A in Fq)")
             w("    static constexpr bool HAS_ENDO = false;   // no efficiently computable endomorphism")
-            w("    static constexpr int SUBGROUP_CHECK = 0;   // no subgroup test (no decoder of this group validates)")
+            sub = g.get("subgroup", "none")
+            w(f"    static constexpr int SUBGROUP_CHECK = {dict(none=0, order=1)[sub]};   "
+              + ("// no subgroup test: is_in_safe_subgroup() is true (prime order, cofactor 1)" if sub == "none" else
+                 "// 1: [r]P == 0 on the plain Jacobian ladder with the a != 0 doubling (the FFI decoder)"))
             if deg == 2:
                 w(f"    static constexpr uint32_t NR_MONT[{n}] = {c_arr(limbs(g['nr'] * fq['R'] % q, n, 32), '0x%08xu')};")
             for nm, vs in (("GEN_X", xs), ("GEN_Y", ys), ("COEFF_B", bs)):
