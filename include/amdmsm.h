@@ -135,6 +135,11 @@ int amdmsm_plan(int curve, int group, size_t n, int window_bits, int *c, int *nu
 int amdmsm_plan_ex(int curve, int group, size_t n, int window_bits, int endomorphism, int *c, int *num_windows,
                    uint32_t *num_buckets, size_t *workspace_bytes, int *endomorphism_used);
 
+/* read-only: geometry of the two-level bucket sort the plan above would run (c <= 22).  out[0] = columns per window
+   (2n with the split), out[1] = coarse bits, out[2] = fine bits, out[3] = entries of a coarse bin the fine pass sorts in
+   one piece (longer bins go chunk by chunk), out[4] = entries above which a coarse bin is spread over the whole grid */
+int amdmsm_plan_sort(int curve, int group, size_t n, int window_bits, int endomorphism, size_t out[5]);
+
 /* libff's own window heuristics, kept for API parity (multiexp.hpp:53-57) */
 size_t amdmsm_pippenger_optimal_c(size_t num_elements);
 size_t amdmsm_bdlo12_signed_optimal_c(size_t num_elements);

@@ -395,16 +395,16 @@ int make_plan(const group_vtable *vt, size_t n, int c_req, int L_req, plan_t &p,
     p.off_partial = off;
     off = align_up(off + (size_t)MAX_GROUPS * xyz_bytes, 256);
     // two-level sort scratch
-    // (the coarse counters and the header of the big-bin scratch are cleared by ONE memset: the
-    // scratch follows the counters directly)
+    // (the coarse counters, the cursors of the coarse pass and the header of the big-bin scratch are cleared by ONE
+    // memset: cursors and scratch follow the counters directly)
     p.off_coarse = off;
     off = align_up(off + Wt * 1025 * 4, 256);
+    p.off_cursor = off;
+    off = align_up(off + Wt * 1024 * 4, 256);
     p.off_big = off;
     // (big_words_min: a batch of MSMs of different lengths passes the largest need of any of its lengths)
     p.big_stride = p.c <= 22 ? align_up(std::max(sort_geometry(n, p.c, p.W).big_words, big_words_min) * 4, 256) : 256;   // per MSM of a batch
     off += p.big_stride * (size_t)batch;
-    p.off_cursor = off;
-    off = align_up(off + Wt * 1024 * 4, 256);
     p.off_tmp_payload = off;
     off = align_up(off + Wt * p.list_stride * 4, 256);
     p.off_tmp_key = off;
@@ -612,7 +612,7 @@ int msm_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_b
         record(ctx, sl, 1, st);
         vt->scatter(st, d_scalars, n, mont, p.c, p.W, counts, lists, p.list_stride);
     } else {
-        HIP_TRY(ctx, hipMemsetAsync(ws + p.off_coarse, 0, p.off_big + 16 - p.off_coarse, st));   // counters + big-bin header
+        HIP_TRY(ctx, hipMemsetAsync(ws + p.off_coarse, 0, p.off_big + 16 - p.off_coarse, st));   // counters + cursors + big-bin header
         record(ctx, sl, 1, st);
         vt->sort(st, d_scalars, n, mont, p.c, table_digits ? table_digits : p.W, (uint32_t *)(ws + p.off_coarse),
                  (uint32_t *)(ws + p.off_cursor), (int32_t *)lists, (uint32_t *)(ws + p.off_tmp_payload),
@@ -746,7 +746,7 @@ int msm_device_batch_impl(amdmsm_ctx *ctx, const group_vtable *vt, int k, const 
     uint32_t *buckets = (uint32_t *)(ws + p.off_buckets);
     uint32_t *pfirst = (uint32_t *)(ws + p.off_pfirst), *plast = (uint32_t *)(ws + p.off_plast), *cont = (uint32_t *)(ws + p.off_cont);
     record(ctx, sl, 0, st);
-    HIP_TRY(ctx, hipMemsetAsync(ws + p.off_coarse, 0, Wt * 1025 * 4, st));
+    HIP_TRY(ctx, hipMemsetAsync(ws + p.off_coarse, 0, p.off_big - p.off_coarse, st));   // counters + cursors
     for (int j = 0; j < k; ++j) HIP_TRY(ctx, hipMemsetAsync(ws + p.off_big + (size_t)j * p.big_stride, 0, 16, st));
     HIP_TRY(ctx, hipMemsetAsync(buckets, 0, Wt * p.B * vt->bucket_words * 4, st));
     HIP_TRY(ctx, hipMemsetAsync(ws + p.off_queue, 0, 8, st));
@@ -868,7 +868,7 @@ int msm_device_batch_items_impl(amdmsm_ctx *ctx, const group_vtable *vt, int k, 
     uint32_t *buckets = (uint32_t *)(ws + p.off_buckets);
     uint32_t *pfirst = (uint32_t *)(ws + p.off_pfirst), *plast = (uint32_t *)(ws + p.off_plast), *cont = (uint32_t *)(ws + p.off_cont);
     record(ctx, sl, 0, st);
-    HIP_TRY(ctx, hipMemsetAsync(ws + p.off_coarse, 0, Wt * 1025 * 4, st));
+    HIP_TRY(ctx, hipMemsetAsync(ws + p.off_coarse, 0, p.off_big - p.off_coarse, st));   // counters + cursors
     for (int j = 0; j < k; ++j) HIP_TRY(ctx, hipMemsetAsync(ws + p.off_big + (size_t)j * p.big_stride, 0, 16, st));
     HIP_TRY(ctx, hipMemsetAsync(buckets, 0, Wt * p.B * vt->bucket_words * 4, st));
     HIP_TRY(ctx, hipMemsetAsync(ws + p.off_queue, 0, 8, st));
@@ -1206,6 +1206,26 @@ int amdmsm_plan_ex(int curve, int group, size_t n, int window_bits, int endomorp
     if (num_buckets) *num_buckets = p.B;
     if (workspace_bytes) *workspace_bytes = p.total;
     if (endomorphism_used) *endomorphism_used = glv ? 1 : 0;
+    return AMDMSM_OK;
+}
+
+int amdmsm_plan_sort(int curve, int group, size_t n, int window_bits, int endomorphism, size_t out[5]) {
+    const group_vtable *vt = find_vt(curve, group);
+    if (!vt || !out) return AMDMSM_ERR_UNSUPPORTED;
+    amdmsm_opts o = AMDMSM_OPTS_INIT;
+    o.window_bits = window_bits;
+    o.endomorphism = endomorphism;
+    const bool glv = use_endomorphism(vt, n, &o, 0);
+    plan_t p;
+    const int rc = make_plan(vt, glv ? 2 * n : n, window_bits, 0, p, 0, 0, 0, glv);
+    if (rc) return rc;
+    if (p.c > 22) return AMDMSM_ERR_UNSUPPORTED;
+    const sort_geom g = sort_geometry(glv ? 2 * n : n, p.c, p.W);
+    out[0] = glv ? 2 * n : n;
+    out[1] = (size_t)g.hb;
+    out[2] = (size_t)g.fb;
+    out[3] = g.chunk_cap;
+    out[4] = g.big_thresh;
     return AMDMSM_OK;
 }
 

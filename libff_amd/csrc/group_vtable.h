@@ -39,9 +39,17 @@ inline sort_geom sort_geometry(size_t n, int c, int W) {
     if (g.hb < 1) g.hb = 1;
     if (c - 1 - g.hb > 11) g.hb = c - 1 - 11;   // the fine pass handles at most 11 bits
     g.fb = c - 1 - g.hb;
-    g.chunk_cap = 1024;   // about twice the expected bin size, 1K .. 16K entries
+    // The fine pass sorts a bin of up to chunk_cap entries in one piece and a longer one chunk by chunk; its LDS is
+    // 6 bytes per entry of chunk_cap, and two of its 1024-thread workgroups share a CU up to about 13000.  So the cap
+    // is the expected bin length mu = n / 2^hb plus a margin, not the next power of two above 2 mu: mu / 8 + 256 is at
+    // least 8 standard deviations (sqrt(mu)) of a bin of a uniformly random input for every mu <= 16384, rounded up to
+    // a multiple of 1024 (2^20 points, split: mu = 8192, cap 10240 = mu + 22 sigma).  1K .. 16K entries.
     static const uint32_t chunk_max = getenv("AMDMSM_SORT_CHUNK_MAX") ? (uint32_t)atoi(getenv("AMDMSM_SORT_CHUNK_MAX")) : 16384u;
-    while (g.chunk_cap < chunk_max && g.chunk_cap < 2 * (n >> g.hb)) g.chunk_cap <<= 1;
+    {
+        const size_t mu = n >> g.hb;
+        const size_t want = (mu + mu / 8 + 256 + 1023) / 1024 * 1024;
+        g.chunk_cap = (uint32_t)(want < 1024 ? 1024 : want > chunk_max ? chunk_max : want);
+    }
     g.big_thresh = 16 * g.chunk_cap;
     g.big_cap = (uint32_t)((size_t)W * n / g.big_thresh + 1);
     g.big_words = 4 + (size_t)g.big_cap * 4 + ((size_t)g.big_cap << g.fb);
@@ -95,7 +103,7 @@ struct group_vtable {
     // classification, multiexp.tcc:713-733); mont: the scalars are Montgomery residues
     void (*scalar_stats)(hipStream_t, const uint32_t* scalars, size_t n, int mont, uint32_t* stats);
     // LDS-staged two-level sort (same result as count + scatter): ends[w][b] and lists[w][...].
-    // coarse: W*(2^hb+1) words zeroed, cursor: W*2^hb words, digits/tmp_payload/lists:
+    // coarse: W*(2^hb+1) words zeroed, cursor: W*2^hb words zeroed, digits/tmp_payload/lists:
     // W*stride words each (digits may alias lists), tmp_key: W*stride 16-bit fine keys; big: sort_geometry().big_words words, the
     // first 4 zeroed (oversized coarse bins, sorted cooperatively); needs c <= 22
     void (*sort)(hipStream_t, const uint32_t* scalars, size_t n, int mont, int c, int W, uint32_t* coarse,

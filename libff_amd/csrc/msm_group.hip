@@ -547,10 +547,10 @@ __global__ void __launch_bounds__(SCAN_TPB) k_scan(uint32_t* __restrict__ counts
 //   k_sort_digits   one pass over the scalars: signed digits to digits[w][i] (coalesced) and a
 //                   histogram over the top HB bits of the bucket index ("coarse bin"), per
 //                   workgroup in LDS, merged with one global atomic per (workgroup, bin)
-//   k_sort_scan     exclusive scan of the coarse histogram (2^HB + 1 entries per window)
-//   k_sort_coarse   workgroup (tile, w): LDS counting sort of a tile's nonzero digits by coarse
-//                   bin, one global atomic per (tile, bin) to reserve space, runs written to
-//                   tmp[w] as (payload, bucket) pairs
+//   k_sort_coarse   workgroup (tile, w): exclusive scan of the window's coarse histogram (2^HB counts),
+//                   LDS counting sort of a tile's nonzero digits by coarse bin, one global atomic
+//                   per (tile, bin) to reserve space, runs written to tmp[w] as (payload, fine
+//                   key) pairs
 //   k_sort_fine     workgroup (bin, w): LDS histogram of the bin by the low FB bits -> ends[],
 //                   then chunk-wise LDS counting sort -> lists[w] (runs per fine bucket)
 // bucket index = |digit| - 1 = (coarse << FB) | fine, HB = min(10, c-1), FB = c-1-HB.
@@ -574,16 +574,17 @@ constexpr int SORT_MAX_FB = 11;     // c <= 22
 AMDMSM_DEV uint32_t digit_payload(size_t i, int32_t d) { return (uint32_t)i | (d < 0 ? 0x80000000u : 0u); }
 
 // exclusive scan of cnt[0..len) (LDS) into out[0..len) by one workgroup of NT threads;
-// len <= 8 * NT.  tmp: NT/64 + 1 words of LDS.  Returns the total in every thread.
-template <int NT = SORT_TPB>
+// len <= MP * NT (MP: entries per thread, 8 unless the caller knows better and wants the registers).  tmp: NT/64 + 1
+// words of LDS.  Returns the total in every thread.
+template <int NT = SORT_TPB, int MP = 8>
 AMDMSM_DEV uint32_t block_exclusive_scan(const uint32_t* cnt, uint32_t* out, uint32_t len, uint32_t* tmp) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t per = (len + NT - 1) / NT;   // <= 8
+    const uint32_t per = (len + NT - 1) / NT;   // <= MP
     const uint32_t i0 = tid * per;
-    uint32_t v[8];
+    uint32_t v[MP];
     uint32_t tsum = 0;
 #pragma unroll
-    for (uint32_t k = 0; k < 8; ++k) {
+    for (uint32_t k = 0; k < MP; ++k) {
         v[k] = (k < per && i0 + k < len) ? cnt[i0 + k] : 0u;
         tsum += v[k];
     }
@@ -605,7 +606,7 @@ AMDMSM_DEV uint32_t block_exclusive_scan(const uint32_t* cnt, uint32_t* out, uin
     }
     uint32_t excl = wave_off + inc - tsum;
 #pragma unroll
-    for (uint32_t k = 0; k < 8; ++k) {
+    for (uint32_t k = 0; k < MP; ++k) {
         if (k < per && i0 + k < len) out[i0 + k] = excl;
         excl += v[k];
     }
@@ -742,75 +743,116 @@ __global__ void __launch_bounds__(TPB) k_gather_scalars(const uint32_t* __restri
     fp_store(out + i * FRW, x);
 }
 
-// counts[w][0..nbin] -> exclusive starts (entry nbin = window total); cursor = copy of the starts
-__global__ void __launch_bounds__(SORT_TPB) k_sort_scan(uint32_t* __restrict__ coarse, uint32_t* __restrict__ cursor,
-                                                        uint32_t nbin) {
-    __shared__ uint32_t cnt[1 << SORT_MAX_HB], out[1 << SORT_MAX_HB], tmp[SORT_TPB / 64 + 1];
-    uint32_t* g = coarse + (size_t)blockIdx.x * (nbin + 1);
-    for (uint32_t j = threadIdx.x; j < nbin; j += SORT_TPB) cnt[j] = g[j];
-    __syncthreads();
-    const uint32_t total = block_exclusive_scan(cnt, out, nbin, tmp);
-    for (uint32_t j = threadIdx.x; j < nbin; j += SORT_TPB) {
-        g[j] = out[j];
-        cursor[(size_t)blockIdx.x * nbin + j] = out[j];
-    }
-    if (threadIdx.x == 0) g[nbin] = total;
-}
-
-__global__ void __launch_bounds__(SORT_TPB) k_sort_coarse(const int32_t* __restrict__ digits, size_t n, size_t stride, int c,
-                                                          int hb, uint32_t* __restrict__ cursor,
-                                                          uint32_t* __restrict__ tmp_payload,
-                                                          sort_key_t* __restrict__ tmp_key) {
+// Workgroup (tile, w) of the coarse pass.  Two of them share a CU (profiles/r05_sort_two_workgroups.txt: one workgroup
+// per CU spent three quarters of its wave-cycles waiting on the phase in front), so a tile costs 64 KiB of staging and
+// at most 64 registers per lane:
+//   * the staged key is the bucket index, 16 bits wide where c <= 17 (SK = unsigned short; 32 bits beyond, where the
+//     96 KiB of staging leave one workgroup per CU as before),
+//   * the staged payload is the entry's position inside the tile (14 bits) with the digit's sign in bit 15 -- the 32-bit
+//     payload digit_payload(tile0 + position, d) is rebuilt at write-out (flat and split modes number their entries by
+//     the column index too, so this holds for every mode),
+//   * rank, sign and bucket index of an entry wait in ONE register for the run starts.
+// The scan of the window's coarse counts is done here too, by every workgroup for itself in LDS (a launch of its own
+// before): coarse[w][0..nbin) holds the COUNTS while this kernel runs, cursor[] starts at zero and hands out offsets
+// inside a bin, and the workgroup that draws the last ticket of its window (coarse[w][nbin], zero on entry) replaces
+// the counts by their exclusive starts and the ticket by the window total -- what k_sort_fine / k_sort_big_* read.
+static_assert(SORT_TILE <= 16384 && SORT_TILE % SORT_TPB == 0, "a tile position is staged in 14 bits");
+// the second argument of __launch_bounds__ counts waves per SIMD: two workgroups of SORT_TPB threads on the four SIMDs
+// of a CU are 8, i.e. at most 64 registers per lane
+constexpr int SORT_WAVES_2WG = 2 * SORT_TPB / 256;
+constexpr uint32_t SORT_NONE = 0xffffffffu;
+template <typename SK>
+__global__ void __launch_bounds__(SORT_TPB, sizeof(SK) == 2 ? SORT_WAVES_2WG : SORT_TPB / 256)
+    k_sort_coarse(const int32_t* __restrict__ digits, size_t n, size_t stride, int c, int hb, uint32_t* __restrict__ coarse,
+                  uint32_t* __restrict__ cursor, uint32_t* __restrict__ tmp_payload, sort_key_t* __restrict__ tmp_key) {
     // tmp_key: the fine part of the bucket index (fb <= 11 bits) -- all the second level needs
-    __shared__ uint32_t hist[1 << SORT_MAX_HB], lstart[1 << SORT_MAX_HB], tmp[SORT_TPB / 64 + 1];
-    __shared__ uint32_t st_payload[SORT_TILE], st_key[SORT_TILE];
+    constexpr bool WIDE = sizeof(SK) != 2;
+    __shared__ uint32_t hist[1 << SORT_MAX_HB], lstart[1 << SORT_MAX_HB], wbase[1 << SORT_MAX_HB], tmp[SORT_TPB / 64 + 1];
+    __shared__ uint32_t last;
+    __shared__ SK st_key[SORT_TILE];
+    __shared__ unsigned short st_pos[SORT_TILE];
     uint32_t* gbase = hist;   // hist[j] is dead once slot j's global base has been reserved
     const uint32_t nbin = 1u << hb;
     const int fb = c - 1 - hb;
     const uint32_t w = blockIdx.y;
     const size_t tile0 = (size_t)blockIdx.x * SORT_TILE;
-    for (uint32_t j = threadIdx.x; j < nbin; j += SORT_TPB) hist[j] = 0;
+    uint32_t* cw = coarse + (size_t)w * (nbin + 1);
+    for (uint32_t j = threadIdx.x; j < nbin; j += SORT_TPB) {
+        hist[j] = 0;
+        wbase[j] = cw[j];
+    }
     __syncthreads();
     constexpr int PER = SORT_TILE / SORT_TPB;
     // ONE LDS atomic per entry: the histogram update returns the entry's rank inside its (tile, bin) run, kept in a
     // register until the run starts are known (a second, returning atomic on a cursor array used to hand the ranks out)
-    uint32_t idx[PER], pay[PER], rank[PER];
+    // ent: rank (14 bits) | sign << 14 | bucket index << 15 (16-bit keys only), or SORT_NONE for a zero digit
+    uint32_t ent[PER], idx[WIDE ? PER : 1];
+    // (uniform base, 32-bit position: no 64-bit address per load in flight)
+    const int32_t* dt = digits + ((size_t)w * stride + tile0);
+    const uint32_t cnt = tile0 >= n ? 0u : (n - tile0 < (size_t)SORT_TILE ? (uint32_t)(n - tile0) : (uint32_t)SORT_TILE);
 #pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        const size_t i = tile0 + (size_t)k * SORT_TPB + threadIdx.x;
-        const int32_t d = (i < n) ? digits[(size_t)w * stride + i] : 0;
-        idx[k] = d ? (uint32_t)(d < 0 ? -d : d) - 1u : 0xffffffffu;
-        pay[k] = digit_payload(i, d);
-        rank[k] = d ? atomicAdd(&hist[idx[k] >> fb], 1u) : 0u;
+    for (int k = 0; k < PER; ++k) {   // all the loads first: the digit waits in the register its entry word takes
+        const uint32_t loc = (uint32_t)k * SORT_TPB + threadIdx.x;
+        ent[k] = (loc < cnt) ? (uint32_t)dt[loc] : 0u;
     }
-    __syncthreads();
-    const uint32_t total = block_exclusive_scan(hist, lstart, nbin, tmp);
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
-        if (idx[k] != 0xffffffffu) {
-            const uint32_t r = lstart[idx[k] >> fb] + rank[k];
-            st_payload[r] = pay[k];
-            st_key[r] = idx[k];
+        const int32_t d = (int32_t)ent[k];
+        const uint32_t b = (uint32_t)(d < 0 ? -d : d) - 1u;
+        const uint32_t r = d ? atomicAdd(&hist[b >> fb], 1u) : 0u;
+        if constexpr (WIDE) {
+            idx[k] = b;
+            ent[k] = d ? (r | (d < 0 ? 0x4000u : 0u)) : SORT_NONE;
+        } else {
+            ent[k] = d ? (r | (d < 0 ? 0x4000u : 0u) | (b << 15)) : SORT_NONE;
         }
     }
+    __syncthreads();
+    const uint32_t total = block_exclusive_scan<SORT_TPB, (1 << SORT_MAX_HB) / SORT_TPB>(hist, lstart, nbin, tmp);
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        if (ent[k] != SORT_NONE) {
+            uint32_t b;
+            if constexpr (WIDE)
+                b = idx[k];
+            else
+                b = ent[k] >> 15;
+            const uint32_t r = lstart[b >> fb] + (ent[k] & 0x3fffu);
+            st_key[r] = (SK)b;
+            st_pos[r] = (unsigned short)(((uint32_t)k * SORT_TPB + threadIdx.x) | ((ent[k] & 0x4000u) << 1));
+        }
+    }
+    const uint32_t wtotal = block_exclusive_scan<SORT_TPB, (1 << SORT_MAX_HB) / SORT_TPB>(wbase, wbase, nbin, tmp);   // in place: it reads before it writes
     for (uint32_t j = threadIdx.x; j < nbin; j += SORT_TPB) {
         const uint32_t h = hist[j];
-        gbase[j] = h ? atomicAdd(&cursor[(size_t)w * nbin + j], h) : 0u;
+        gbase[j] = h ? wbase[j] + atomicAdd(&cursor[(size_t)w * nbin + j], h) : 0u;
     }
+    // every thread's read of the counts lies before the first barrier, so the last ticket of a window is drawn after
+    // the last read of its counts
+    if (threadIdx.x == 0) last = atomicAdd(&cw[nbin], 1u) == gridDim.x - 1u;
     __syncthreads();
+    if (last) {
+        for (uint32_t j = threadIdx.x; j < nbin; j += SORT_TPB) cw[j] = wbase[j];
+        if (threadIdx.x == 0) cw[nbin] = wtotal;
+    }
+    uint32_t* out_pay = tmp_payload + (size_t)w * stride;
+    sort_key_t* out_key = tmp_key + (size_t)w * stride;
     for (uint32_t k = threadIdx.x; k < total; k += SORT_TPB) {
-        const uint32_t key = st_key[k];
+        const uint32_t key = st_key[k], p = st_pos[k];
         const uint32_t bin = key >> fb;
-        const size_t pos = (size_t)w * stride + gbase[bin] + (k - lstart[bin]);
-        tmp_payload[pos] = st_payload[k];
-        tmp_key[pos] = (sort_key_t)(key & ((1u << fb) - 1u));
+        const uint32_t pos = gbase[bin] + (k - lstart[bin]);
+        out_pay[pos] = ((uint32_t)tile0 + (p & 0x3fffu)) | ((p & 0x8000u) << 16);   // = digit_payload(i, d)
+        out_key[pos] = (sort_key_t)(key & ((1u << fb) - 1u));
     }
 }
 
 // NT threads per workgroup: 1024 for bins of tens of thousands of entries, 256 when a bin holds
-// a few thousand at most (2^20-point inputs), where barriers between 16 waves would dominate
-template <int NT>
-__global__ void __launch_bounds__(NT) k_sort_fine(const uint32_t* __restrict__ tmp_payload,
+// a few thousand at most (2^20-point inputs), where barriers between 16 waves would dominate.
+// PER: entries per thread of a one-chunk bin, chunk_cap <= PER * NT.  The 1024-thread forms with PER < 16 (chunk_cap <=
+// 12288: 72 KiB of staging at most) are built for two workgroups per CU (64 registers); with PER = 16 the staging leaves
+// room for one.
+template <int NT, int PER>
+__global__ void __launch_bounds__(NT, NT == SORT_TPB ? (PER < 16 ? SORT_WAVES_2WG : SORT_TPB / 256) : 1) k_sort_fine(const uint32_t* __restrict__ tmp_payload,
                                                         const sort_key_t* __restrict__ tmp_key,
                                                         const uint32_t* __restrict__ coarse, size_t stride, int c, int hb,
                                                         uint32_t chunk_cap, uint32_t big_thresh, uint32_t big_cap,
@@ -830,7 +872,8 @@ __global__ void __launch_bounds__(NT) k_sort_fine(const uint32_t* __restrict__ t
     unsigned short* st_fine = reinterpret_cast<unsigned short*>(st_payload + chunk_cap);
     const uint32_t bin = blockIdx.x, w = blockIdx.y;
     const uint32_t* cs = coarse + (size_t)w * (nbin + 1);
-    const uint32_t b0 = cs[bin], m = cs[bin + 1] - b0;
+    // (the same in every lane: as scalars they make key / pay / out uniform bases, and a load costs one offset register)
+    const uint32_t b0 = __builtin_amdgcn_readfirstlane(cs[bin]), m = __builtin_amdgcn_readfirstlane(cs[bin + 1]) - b0;
     const sort_key_t* key = tmp_key + (size_t)w * stride + b0;
     const uint32_t* pay = tmp_payload + (size_t)w * stride + b0;
     uint32_t* out = lists + (size_t)w * stride + b0;
@@ -856,25 +899,36 @@ __global__ void __launch_bounds__(NT) k_sort_fine(const uint32_t* __restrict__ t
     // (the fine pass is bound by them: 6.2 ms of a 2^26-point MSM).
     if (m <= chunk_cap) {
         // The bin is one chunk (every bin of a uniformly random input up to ~2^22 points): ONE LDS atomic per entry -- the
-        // histogram update returns the entry's rank inside its bucket, kept in a register (at most chunk_cap / NT = 16 per
-        // thread) until the bucket starts are known -- one read of the key, and the staged chunk IS the bin's list.
-        constexpr int PER = 16;
-        uint32_t fk[PER], rk[PER];
+        // histogram update returns the entry's rank inside its bucket, kept in a register with the fine key (rank < chunk_cap
+        // <= 2^14 | key << 14; PER per thread) until the
+        // bucket starts are known -- one read of the key, and the staged chunk IS the bin's list.
+        uint32_t fr[PER];
+        if (m == 0) {
+            for (uint32_t j = threadIdx.x; j < nfine; j += NT) e[j] = b0;
+            return;
+        }
         for (uint32_t j = threadIdx.x; j < nfine; j += NT) chist[j] = 0;
+        // all the loads first, unconditional (a position past the bin reads the bin's last entry and is dropped below) and
+        // with no early exit from these loops: the arrays must stay registers
+#pragma unroll
+        for (int q = 0; q < PER; ++q) {
+            const uint32_t k = threadIdx.x + (uint32_t)q * NT;
+            fr[q] = (uint32_t)key[k < m ? k : m - 1u] & fmask;
+        }
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < PER; ++q) {
             const uint32_t k = threadIdx.x + (uint32_t)q * NT;
-            fk[q] = k < m ? (uint32_t)(key[k] & fmask) : 0u;
-            rk[q] = k < m ? atomicAdd(&chist[fk[q]], 1u) : 0u;
+            const uint32_t r = k < m ? atomicAdd(&chist[fr[q]], 1u) : 0u;
+            fr[q] = r | (fr[q] << 14);
         }
         __syncthreads();
-        block_exclusive_scan<NT>(chist, fstart, nfine, tmp);
+        block_exclusive_scan<NT, (1 << SORT_MAX_FB) / NT>(chist, fstart, nfine, tmp);
         for (uint32_t j = threadIdx.x; j < nfine; j += NT) e[j] = b0 + fstart[j] + chist[j];
 #pragma unroll
         for (int q = 0; q < PER; ++q) {
             const uint32_t k = threadIdx.x + (uint32_t)q * NT;
-            if (k < m) st_payload[fstart[fk[q]] + rk[q]] = pay[k];
+            if (k < m) st_payload[fstart[fr[q] >> 14] + (fr[q] & 0x3fffu)] = pay[k];
         }
         __syncthreads();
         for (uint32_t k = threadIdx.x; k < m; k += NT) out[k] = st_payload[k];
@@ -885,11 +939,12 @@ __global__ void __launch_bounds__(NT) k_sort_fine(const uint32_t* __restrict__ t
     uint32_t* ch = reinterpret_cast<uint32_t*>(st_fine + chunk_cap);   // [nch][nfine]
     const bool split_hist = !single && (size_t)nch * nfine <= perchunk_words;
     if (split_hist) {
-        int sh = 0;
-        while ((1u << sh) < chunk_cap) ++sh;   // chunk_cap is a power of two
         for (uint32_t j = threadIdx.x; j < nch * nfine; j += NT) ch[j] = 0;
         __syncthreads();
-        for (uint32_t k = threadIdx.x; k < m; k += NT) atomicAdd(&ch[(k >> sh) * nfine + (key[k] & fmask)], 1u);
+        for (uint32_t q = 0, c0 = 0; q < nch; ++q, c0 += chunk_cap) {   // chunk_cap: any multiple of NT
+            const uint32_t cm = (m - c0 < chunk_cap) ? m - c0 : chunk_cap;
+            for (uint32_t k = threadIdx.x; k < cm; k += NT) atomicAdd(&ch[q * nfine + (key[c0 + k] & fmask)], 1u);
+        }
         __syncthreads();
         for (uint32_t j = threadIdx.x; j < nfine; j += NT) {
             uint32_t t = 0;
@@ -1019,12 +1074,13 @@ __global__ void __launch_bounds__(SORT_TPB) k_sort_big_scan(const uint32_t* __re
     }
 }
 
-__global__ void __launch_bounds__(SORT_TPB) k_sort_big_scatter(const uint32_t* __restrict__ tmp_payload,
+__global__ void __launch_bounds__(SORT_TPB, SORT_WAVES_2WG) k_sort_big_scatter(const uint32_t* __restrict__ tmp_payload,
                                                                const sort_key_t* __restrict__ tmp_key,
                                                                const uint32_t* __restrict__ coarse, size_t stride, int c,
                                                                int hb, uint32_t big_cap, uint32_t* __restrict__ big,
                                                                uint32_t* __restrict__ lists) {
-    // dynamic LDS: hist / lstart / lcur / gbase of 2^fb words, SORT_TILE payloads, SORT_TILE fine keys (u16)
+    // dynamic LDS: hist / lstart / lcur / gbase of 2^fb words, then SORT_TILE source positions and SORT_TILE fine keys,
+    // 16 bits each as in k_sort_coarse: the payload is fetched at write-out from the tile the position names
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     __shared__ uint32_t tmp[SORT_TPB / 64 + 1], sh[1];
     const uint32_t nbin = 1u << hb;
@@ -1034,8 +1090,8 @@ __global__ void __launch_bounds__(SORT_TPB) k_sort_big_scatter(const uint32_t* _
     uint32_t* lstart = hist + nfine;
     uint32_t* lcur = lstart + nfine;
     uint32_t* gbase = lcur + nfine;
-    uint32_t* st_payload = gbase + nfine;
-    unsigned short* st_fine = reinterpret_cast<unsigned short*>(st_payload + SORT_TILE);
+    unsigned short* st_src = reinterpret_cast<unsigned short*>(gbase + nfine);
+    unsigned short* st_fine = st_src + SORT_TILE;
     const uint32_t tiles = big[1];
     for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         big_tile bt;
@@ -1058,14 +1114,14 @@ __global__ void __launch_bounds__(SORT_TPB) k_sort_big_scatter(const uint32_t* _
         for (uint32_t k = threadIdx.x; k < bt.cm; k += SORT_TPB) {
             const uint32_t f = key[k] & fmask;
             const uint32_t r = atomicAdd(&lcur[f], 1u);
-            st_payload[r] = pay[k];
+            st_src[r] = (unsigned short)k;
             st_fine[r] = (unsigned short)f;
         }
         __syncthreads();
         uint32_t* out = lists + (size_t)bt.w * stride;
         for (uint32_t k = threadIdx.x; k < bt.cm; k += SORT_TPB) {
             const uint32_t f = st_fine[k];
-            out[gbase[f] + (k - lstart[f])] = st_payload[k];
+            out[gbase[f] + (k - lstart[f])] = pay[st_src[k]];
         }
         __syncthreads();
     }
@@ -3067,25 +3123,54 @@ void sort_launch(hipStream_t st, const uint32_t* scalars, size_t n, int mont, in
     else
         hipLaunchKernelGGL(k_sort_digits, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(SORT_TPB),
                            (size_t)(flat ? 1 : W) * nbin * 4, st, scalars, n, mont, c, W, hb, per_block, digits, stride, coarse, mode);
-    hipLaunchKernelGGL(k_sort_scan, dim3(We), dim3(SORT_TPB), 0, st, coarse, cursor, nbin);
     sort_key_t* tmp_key16 = reinterpret_cast<sort_key_t*>(tmp_key);   // W * stride fine keys
-    hipLaunchKernelGGL(k_sort_coarse, dim3((unsigned)((ne + SORT_TILE - 1) / SORT_TILE), We), dim3(SORT_TPB), 0, st, digits,
-                       ne, stride, c, hb, cursor, tmp_payload, tmp_key16);
+    const dim3 coarse_grid((unsigned)((ne + SORT_TILE - 1) / SORT_TILE), We);
+    if (c <= 17)   // the bucket index has c - 1 bits
+        hipLaunchKernelGGL(k_sort_coarse<unsigned short>, coarse_grid, dim3(SORT_TPB), 0, st, digits, ne, stride, c, hb, coarse,
+                           cursor, tmp_payload, tmp_key16);
+    else
+        hipLaunchKernelGGL(k_sort_coarse<uint32_t>, coarse_grid, dim3(SORT_TPB), 0, st, digits, ne, stride, c, hb, coarse,
+                           cursor, tmp_payload, tmp_key16);
     if (after_coarse) (void)hipEventRecord(after_coarse, st);
     // per-chunk histograms of a bin of up to 16 chunks, where they fit beside the staging area (<= 32 KiB)
     static const bool split_hist = !(getenv("AMDMSM_SORT_SPLIT_HIST") && atoi(getenv("AMDMSM_SORT_SPLIT_HIST")) == 0);
     uint32_t perchunk_words = 0;
     if (split_hist && sg.chunk_cap >= 16384 && ((size_t)16 << sg.fb) * 4 <= 32768) perchunk_words = 16u << sg.fb;
     const size_t fine_lds = ((size_t)4 << sg.fb) * 4 + (size_t)sg.chunk_cap * 6 + (size_t)perchunk_words * 4;
+    const size_t big_lds = ((size_t)4 << sg.fb) * 4 + (size_t)SORT_TILE * 4;
+    // AMDMSM_SORT_REPORT=1: workgroups per CU the runtime grants the 1024-thread passes, asked once, at the first call's sizes
+    static const bool reported = [&] {
+        if (!(getenv("AMDMSM_SORT_REPORT") && atoi(getenv("AMDMSM_SORT_REPORT")))) return false;
+        int k16 = 0, k32 = 0, kf = 0, kb = 0;
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&k16, k_sort_coarse<unsigned short>, SORT_TPB, 0);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&k32, k_sort_coarse<uint32_t>, SORT_TPB, 0);
+        if (sg.chunk_cap <= 8192)
+            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&kf, k_sort_fine<SORT_TPB, 8>, SORT_TPB, fine_lds);
+        else if (sg.chunk_cap <= 12288)
+            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&kf, k_sort_fine<SORT_TPB, 12>, SORT_TPB, fine_lds);
+        else
+            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&kf, k_sort_fine<SORT_TPB, 16>, SORT_TPB, fine_lds);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&kb, k_sort_big_scatter, SORT_TPB, big_lds);
+        fprintf(stderr, "[amdmsm sort] workgroups per CU: k_sort_coarse 16-bit keys %d, 32-bit keys %d; k_sort_fine<1024> "
+                        "(chunk_cap %u, %zu B of LDS) %d; k_sort_big_scatter (%zu B) %d\n",
+                k16, k32, sg.chunk_cap, fine_lds, kf, big_lds, kb);
+        return true;
+    }();
+    (void)reported;
+#define AMDMSM_LAUNCH_FINE(NT, PER)                                                                                          \
+    hipLaunchKernelGGL((k_sort_fine<NT, PER>), dim3(nbin, We), dim3(NT), fine_lds, st, tmp_payload, tmp_key16, coarse, stride, c, \
+                       hb, sg.chunk_cap, sg.big_thresh, sg.big_cap, perchunk_words, big, ends, lists)
     if (sg.chunk_cap <= 4096)
-        hipLaunchKernelGGL(k_sort_fine<256>, dim3(nbin, We), dim3(256), fine_lds, st, tmp_payload, tmp_key16, coarse, stride,
-                           c, hb, sg.chunk_cap, sg.big_thresh, sg.big_cap, perchunk_words, big, ends, lists);
+        AMDMSM_LAUNCH_FINE(256, 16);
+    else if (sg.chunk_cap <= 8192)
+        AMDMSM_LAUNCH_FINE(SORT_TPB, 8);
+    else if (sg.chunk_cap <= 12288)
+        AMDMSM_LAUNCH_FINE(SORT_TPB, 12);
     else
-        hipLaunchKernelGGL(k_sort_fine<SORT_TPB>, dim3(nbin, We), dim3(SORT_TPB), fine_lds, st, tmp_payload, tmp_key16, coarse,
-                           stride, c, hb, sg.chunk_cap, sg.big_thresh, sg.big_cap, perchunk_words, big, ends, lists);
+        AMDMSM_LAUNCH_FINE(SORT_TPB, 16);
+#undef AMDMSM_LAUNCH_FINE
     hipLaunchKernelGGL(k_sort_big_hist, dim3(512), dim3(SORT_TPB), 0, st, tmp_key16, coarse, stride, c, hb, big, ends);
     hipLaunchKernelGGL(k_sort_big_scan, dim3(256), dim3(SORT_TPB), 0, st, coarse, c, hb, sg.big_cap, big, ends);
-    const size_t big_lds = ((size_t)4 << sg.fb) * 4 + (size_t)SORT_TILE * 6;
     hipLaunchKernelGGL(k_sort_big_scatter, dim3(512), dim3(SORT_TPB), big_lds, st, tmp_payload, tmp_key16, coarse, stride, c,
                        hb, sg.big_cap, big, lists);
 }

@@ -43,7 +43,7 @@ MAX_PHASES = 8
 
 EXPORTED_SYMBOLS = [
     "amdmsm_abi_version", "amdmsm_device_count", "amdmsm_ctx_create", "amdmsm_ctx_destroy", "amdmsm_strerror",
-    "amdmsm_last_error", "amdmsm_sizes", "amdmsm_plan", "amdmsm_plan_ex", "amdmsm_endomorphism_info",
+    "amdmsm_last_error", "amdmsm_sizes", "amdmsm_plan", "amdmsm_plan_ex", "amdmsm_plan_sort", "amdmsm_endomorphism_info",
     "amdmsm_endomorphism_digits_device", "amdmsm_pippenger_optimal_c",
     "amdmsm_bdlo12_signed_optimal_c", "amdmsm_multi_exp", "amdmsm_multi_exp_batch", "amdmsm_multi_exp_batch_items",
     "amdmsm_msm_device_batch_items", "amdmsm_multi_exp_filter_one_zero",
@@ -154,6 +154,17 @@ def plan(curve, group, n, window_bits=0, endomorphism=0):
         raise AmdMsmError(f"amdmsm_plan_ex: {rc}")
     return {"c": c.value, "num_windows": w.value, "num_buckets": b.value, "workspace_bytes": ws.value,
             "endomorphism": bool(used.value)}
+
+
+def plan_sort(curve, group, n, window_bits=0, endomorphism=0):
+    """Geometry of the bucket sort behind ``plan`` (read-only): columns per window, coarse / fine bits of the bucket
+    index, the longest coarse bin the fine pass sorts in one piece and the length above which a bin is spread over
+    the whole grid."""
+    out = (ctypes.c_size_t * 5)()
+    rc = load_library().amdmsm_plan_sort(curve, group, ctypes.c_size_t(n), window_bits, endomorphism, out)
+    if rc:
+        raise AmdMsmError(f"amdmsm_plan_sort: {rc}")
+    return {"columns": out[0], "coarse_bits": out[1], "fine_bits": out[2], "chunk_cap": out[3], "big_thresh": out[4]}
 
 
 def endomorphism_info(curve, group):
