@@ -198,6 +198,50 @@ int amdmsm_multi_exp_batch_items(amdmsm_ctx *ctx, int curve, int group, int k, c
                                  size_t base_stride_bytes, int base_form, const void *shared_scalars, size_t shared_n,
                                  const amdmsm_opts *opts);
 
+/* ---- scalars known to be short ----
+ * libff's multi_exp sizes its rounds by num_bits = max_i bi_exponents[i].num_bits() (multiexp.tcc:297-304, :577-586): a
+ * vector of bytes or 32-bit words costs it an eighth of a vector of full-length scalars.  The entries below do the same:
+ * the windows cover the scalars' bit length, and packed integers are read as they are -- n * width bytes cross PCIe and
+ * pass through the digit kernel instead of n Fr records.  They return the group element amdmsm_multi_exp /
+ * amdmsm_msm_device return for the same values widened to Fr.
+ *   kind  AMDMSM_SCALAR_FR: Fr records as everywhere else (Montgomery, or plain with opts->scalars_plain).
+ *         AMDMSM_SCALAR_U8 / U16 / U32 / U64: packed little-endian unsigned integers; the pointer needs the element's
+ *         own alignment only, and opts->scalars_plain is ignored.
+ *   bits  0: the kind's full width (Fr::num_bits, or 8 * width) -- the type bounds the value, nothing is tested;
+ *         N > 0: the caller's promise that every scalar is < 2^N.  It is tested on the device; a scalar that breaks it
+ *           makes the call return AMDMSM_ERR_BAD_ARG with the output untouched.  The call synchronises to learn that.
+ *         -1: the bit length is measured on the device (amdmsm_scalar_bits_device) before the plan is made: the call
+ *           reads 4 bytes back first and is therefore synchronous; all scalars zero gives the group's zero.
+ * num_windows = (bits + 2 + c - 1) / c; c comes from the cost model with bits in place of Fr::num_bits and is never
+ * larger than bits + 2.  The endomorphism split is used only where amdmsm_plan_ex would use it and bits exceeds the
+ * split's own bound (amdmsm_endomorphism_info); bits >= Fr::num_bits is the ordinary plan.  amdmsm_plan_short tells
+ * (scalar_bits = 0: full width).  opts->window_bits > 22 is AMDMSM_ERR_BAD_ARG, as for the batch calls.  Everything is
+ * validated before anything is launched.  Signed integers, batches, the precomputed-table and streaming paths and
+ * several GPUs are not covered. */
+enum { AMDMSM_SCALAR_FR = 0, AMDMSM_SCALAR_U8 = 1, AMDMSM_SCALAR_U16 = 2, AMDMSM_SCALAR_U32 = 4, AMDMSM_SCALAR_U64 = 8 };
+typedef struct amdmsm_scalar_desc {
+    uint32_t struct_size; /* = sizeof(amdmsm_scalar_desc) (AMDMSM_SCALAR_DESC_INIT); an unknown size is refused */
+    int kind;             /* AMDMSM_SCALAR_* */
+    int bits;             /* 0, N > 0 or -1, see above */
+} amdmsm_scalar_desc;
+#define AMDMSM_SCALAR_DESC_INIT { (uint32_t)sizeof(amdmsm_scalar_desc) }
+int amdmsm_plan_short(int curve, int group, size_t n, int window_bits, int endomorphism, int scalar_bits, int *c,
+                      int *num_windows, uint32_t *num_buckets, size_t *workspace_bytes, int *endomorphism_used);
+/* *bits = bit length of the longest of the n device-resident scalars (0: all zero); desc->bits is not read.
+ * Runs on the context stream and synchronises it. */
+int amdmsm_scalar_bits_device(amdmsm_ctx *ctx, int curve, int group, const void *d_scalars, size_t n,
+                              const amdmsm_scalar_desc *desc, int scalars_plain, int *bits);
+/* amdmsm_multi_exp on short scalars: registered bases and AMDMSM_BASE_CACHE_MB are honoured in the same way, inputs above
+ * AMDMSM_MAX_RANGE_POINTS run as ranges with one bit length for all of them */
+int amdmsm_multi_exp_short(amdmsm_ctx *ctx, int curve, int group, const void *bases_xyz, size_t base_stride_bytes,
+                           int base_form, const void *scalars, const amdmsm_scalar_desc *desc, size_t n, void *out_xyz,
+                           const amdmsm_opts *opts);
+/* amdmsm_msm_device on short scalars.  Asynchronous like amdmsm_msm_device only with bits = 0; with a promise
+ * (synchronises to read the flag, the result is written after that) or bits = -1 (synchronises to read the measured
+ * length) the call returns when the result is in d_out_xyz. */
+int amdmsm_msm_device_short(amdmsm_ctx *ctx, int curve, int group, const void *d_bases_affine, const void *d_scalars,
+                            const amdmsm_scalar_desc *desc, size_t n, void *d_out_xyz, const amdmsm_opts *opts);
+
 /* Resident base vectors.  A prover calls multi_exp with the same base vector (its proving key,
  * libsnark r1cs_gg_ppzksnark_proving_key) proof after proof; the reference re-reads it from host
  * memory every time (multiexp.tcc:643-688 takes const iterators).  amdmsm_register_bases imports

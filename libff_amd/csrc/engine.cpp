@@ -106,6 +106,7 @@ struct amdmsm_ctx {
     // host-buffer entry points: staging in HBM reused across calls, a second stream that brings
     // the bases in while the scalars are already being sorted, and the resident base vectors
     grow_buf hb_src, hb_aff, hb_sc, hb_out, hb_stats;
+    grow_buf short_word, short_out;          // short scalars: [0] promise flag, [1] measured bit length; result held back until the flag is read
     grow_buf hb_idx, sel_flag, sel_gather;   // batch items: index lists, out-of-range flags, scalars gathered for one MSM
     hipStream_t copy_stream = nullptr;
     hipEvent_t bases_ready = nullptr, host_done = nullptr;
@@ -203,7 +204,11 @@ int glv_windows(const group_vtable *vt, int c) {
     while ((double)(c * W - 1) + std::log2(1.0 - std::ldexp(1.0, 1 - c)) < lb) ++W;
     return W;
 }
-int num_windows(const group_vtable *vt, int c, bool glv) { return glv ? glv_windows(vt, c) : (vt->fr_bits + 2 + c - 1) / c; }
+// sbits > 0: every scalar is known to be below 2^sbits (amdmsm_*_short), so the windows cover sbits + 2 bits -- what
+// libff does with num_bits = max_i bi_exponents[i].num_bits() (multiexp.tcc:577-586)
+int num_windows(const group_vtable *vt, int c, bool glv, int sbits = 0) {
+    return glv ? glv_windows(vt, c) : ((sbits > 0 ? sbits : vt->fr_bits) + 2 + c - 1) / c;
+}
 
 // Window size.  Cost model fitted to measurements on MI355X (alt_bn128 G1, tools/sweep_c.py; the other
 // fields scale every term alike, the wide ones pay more per bucket because their reduction
@@ -229,9 +234,9 @@ int num_windows(const group_vtable *vt, int c, bool glv) { return glv ? glv_wind
 // more above, where bases plus phi(P) records (2 x 64 B x n) no longer fit the 256 MB Infinity
 // Cache, so from 2^22 points up the plain path is level or ahead again (2^22: 7.78 vs 7.84,
 // 2^23: 14.0 vs 13.7, 2^26: 87.4 vs 87.6 ms; profiles/r02_endomorphism_sweep.txt).
-double plan_cost(const group_vtable *vt, size_t n, int c, bool glv) {
-    const int bits = glv ? (vt->glv_bound_log2_x1000 + 999) / 1000 : vt->fr_bits;
-    const int W = num_windows(vt, c, glv);
+double plan_cost(const group_vtable *vt, size_t n, int c, bool glv, int sbits = 0) {
+    const int bits = glv ? (vt->glv_bound_log2_x1000 + 999) / 1000 : (sbits > 0 ? sbits : vt->fr_bits);
+    const int W = num_windows(vt, c, glv, sbits);
     const double cols = glv ? 2.0 * (double)n : (double)n;   // digit columns
     const double B = (double)((size_t)1 << (c - 1));
     // (24 limbs: the reduction kernels run one wave per SIMD; ~10 ns per bucket against 0.8 for 8 limbs,
@@ -267,8 +272,23 @@ double plan_cost(const group_vtable *vt, size_t n, int c, bool glv) {
 }
 
 // n: points
-int choose_c(const group_vtable *vt, size_t n, bool glv = false, double *cost_out = nullptr) {
+int choose_c(const group_vtable *vt, size_t n, bool glv = false, double *cost_out = nullptr, int sbits = 0) {
     if (n == 0) return 2;
+    if (sbits > 0) {
+        // short scalars: the measured table below was fitted to full-length scalars and does not apply; the model
+        // alone decides, and a window wider than sbits + 2 bits would only add empty buckets
+        double best = 1e300;
+        int best_c = 2;
+        for (int c = 2; c <= 22 && c <= sbits + 2; ++c) {
+            const double cost = plan_cost(vt, n, c, false, sbits);
+            if (cost < best) {
+                best = cost;
+                best_c = c;
+            }
+        }
+        if (cost_out) *cost_out = best;
+        return best_c;
+    }
     // Small and medium inputs are launch and chain latency, which the model does not describe; the choice there is measured
     // (profiles/r04_experiments.txt, every group, c = 2 .. 16 at 2^2 .. 2^17 points).  Since the bucket reduction became plain sums
     // (row / column sums, bit planes: c >= 10) the short Horner of few wide windows wins over few buckets: c = 10 up to 2^10
@@ -308,14 +328,14 @@ int choose_c(const group_vtable *vt, size_t n, bool glv = false, double *cost_ou
 // batch > 1: workspace for `batch` MSMs side by side, each of at most n entries -- every per-window array holds batch * W windows, MSM j
 // owning windows [j * W, (j + 1) * W), so that the tail kernels run once over all of them (amdmsm_msm_device_batch)
 int make_plan(const group_vtable *vt, size_t n, int c_req, int L_req, plan_t &p, int S_req = 0, int table_digits = 0,
-              int G_req = 0, bool glv = false, bool overlap = false, int batch = 1, size_t big_words_min = 0) {
+              int G_req = 0, bool glv = false, bool overlap = false, int batch = 1, size_t big_words_min = 0, int sbits = 0) {
     if (c_req < 0 || c_req > 24 || c_req == 1) return AMDMSM_ERR_BAD_ARG;
     if (table_digits && (c_req < 2 || c_req > 22)) return AMDMSM_ERR_BAD_ARG;
     if (glv && (table_digits || c_req > 22)) return AMDMSM_ERR_BAD_ARG;
     p.glv = glv;
-    p.c = c_req ? c_req : choose_c(vt, glv ? n / 2 : n, glv);
+    p.c = c_req ? c_req : choose_c(vt, glv ? n / 2 : n, glv, nullptr, sbits);
     // field_get_signed_digit needs room for bits + 2 (multiexp.tcc:584-586)
-    p.W = table_digits ? 1 : num_windows(vt, p.c, glv);
+    p.W = table_digits ? 1 : num_windows(vt, p.c, glv, sbits);
     p.D = table_digits;
     p.B = (uint32_t)1 << (p.c - 1);
     // buckets per reduction lane.  k_reduce_segments is bound by the dependent chain of one wave
@@ -547,15 +567,29 @@ struct msm_hook {
     int (*fn)(void *arg, hipEvent_t *wait_for) = nullptr;
     void *arg = nullptr;
 };
+// Scalars known to be short (amdmsm_*_short), once the entry point has settled how the call runs: the digit pass reads
+// elements of `kind`, the plan's windows cover `bits` + 2 bits, no endomorphism split.
+struct short_spec {
+    int kind = 0;               // AMDMSM_SCALAR_*
+    int bits = 0;               // 1 .. below Fr::num_bits
+    uint32_t *flag = nullptr;   // device word the digit pass raises for a scalar >= 2^bits; null: nothing to test
+    bool uploaded = false;      // host entry: the scalars are already in ctx->hb_sc (the measuring pass brought them)
+    size_t elem_bytes(const group_vtable *vt) const { return kind ? (size_t)kind : (size_t)vt->fr_words * 4; }
+};
+// bits the digit pass tests against: the kind's full width where there is nothing to test
+int short_limit_bits(const group_vtable *vt, const short_spec &ss) {
+    return ss.flag ? ss.bits : (ss.kind ? 8 * ss.kind : 32 * vt->fr_words);
+}
 int msm_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_bases, const uint32_t *d_scalars,
                     size_t n, uint32_t *d_out, const amdmsm_opts *opts, int table_digits = 0,
-                    const msm_hook *hook = nullptr, const uint32_t *d_endo_resident = nullptr) {
+                    const msm_hook *hook = nullptr, const uint32_t *d_endo_resident = nullptr, const short_spec *ss = nullptr) {
     hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : ctx->stream;
     hipStream_t const user_st = st;
     const int form = opts ? opts->out_form : AMDMSM_OUT_LIBFF;
     const int mont = (opts && opts->scalars_plain) ? 0 : 1;
-    static const bool atomic_sort = getenv("AMDMSM_SORT") && !strcmp(getenv("AMDMSM_SORT"), "atomic");
-    const bool glv = use_endomorphism(vt, n, opts, table_digits) && !atomic_sort;
+    static const bool atomic_env = getenv("AMDMSM_SORT") && !strcmp(getenv("AMDMSM_SORT"), "atomic");
+    const bool atomic_sort = atomic_env && !ss;   // the short digit pass exists for the two-level sort only
+    const bool glv = !ss && use_endomorphism(vt, n, opts, table_digits) && !atomic_sort;
     const size_t entries = table_digits ? n * (size_t)table_digits : (glv ? 2 * n : n);   // per sorted list
     if (entries >= ((size_t)1 << 31)) return fail(ctx, AMDMSM_ERR_TOO_LARGE, "n (times table digits) must be < 2^31 per call");
     if (n == 0) {
@@ -576,8 +610,9 @@ int msm_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_b
     static const bool overlap_env = getenv("AMDMSM_OVERLAP") && atoi(getenv("AMDMSM_OVERLAP")) != 0;
     const bool overlap = overlap_env && ctx->depth > 1 && ctx->bulk_stream && vt->accumulate_overlap_ok && !groups_env;
     int rc = make_plan(vt, entries, opts ? opts->window_bits : 0, opts ? opts->segment_len : 0, p, acc_s_env, table_digits,
-                       groups_env, glv, overlap);
+                       groups_env, glv, overlap, 1, 0, ss ? ss->bits : 0);
     if (rc) return fail(ctx, rc, "bad window_bits / segment_len");
+    if (ss && p.c > 22) return fail(ctx, AMDMSM_ERR_BAD_ARG, "window_bits > 22 is not available for short scalars");
     const int slot_idx = (int)(ctx->next++ % (unsigned)ctx->depth);
     ws_slot &sl = ctx->slots[slot_idx];
     ctx->last_slot = slot_idx;
@@ -614,6 +649,12 @@ int msm_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_b
     } else {
         HIP_TRY(ctx, hipMemsetAsync(ws + p.off_coarse, 0, p.off_big + 16 - p.off_coarse, st));   // counters + cursors + big-bin header
         record(ctx, sl, 1, st);
+        if (ss)
+            vt->sort_short(st, d_scalars, ss->kind, short_limit_bits(vt, *ss), ss->flag, n, mont, p.c, p.W,
+                           (uint32_t *)(ws + p.off_coarse), (uint32_t *)(ws + p.off_cursor), (int32_t *)lists,
+                           (uint32_t *)(ws + p.off_tmp_payload), (uint32_t *)(ws + p.off_tmp_key), counts, lists, p.list_stride,
+                           (uint32_t *)(ws + p.off_big));
+        else
         vt->sort(st, d_scalars, n, mont, p.c, table_digits ? table_digits : p.W, (uint32_t *)(ws + p.off_coarse),
                  (uint32_t *)(ws + p.off_cursor), (int32_t *)lists, (uint32_t *)(ws + p.off_tmp_payload),
                  (uint32_t *)(ws + p.off_tmp_key), counts, lists, p.list_stride, (uint32_t *)(ws + p.off_big),
@@ -947,13 +988,14 @@ int ensure_partials(amdmsm_ctx *ctx) {
 // reference's chunk loop (multiexp.tcc:655-687: `one = total / chunks`, the last range takes the
 // remainder, partial results summed) with ranges run one after the other on the caller's stream.
 int msm_device_ranges(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_bases, const uint32_t *d_scalars, size_t n,
-                      uint32_t *d_out, const amdmsm_opts *opts) {
+                      uint32_t *d_out, const amdmsm_opts *opts, const short_spec *ss = nullptr) {
     const size_t maxr = max_range_points();
-    if (n <= maxr) return msm_device_impl(ctx, vt, d_bases, d_scalars, n, d_out, opts);
+    if (n <= maxr) return msm_device_impl(ctx, vt, d_bases, d_scalars, n, d_out, opts, 0, nullptr, nullptr, ss);
     const size_t parts = (n + maxr - 1) / maxr;
     if (parts > MAX_RANGES) return fail(ctx, AMDMSM_ERR_TOO_LARGE, "input too large for one call");
     const size_t one = (n + parts - 1) / parts;   // <= maxr: no range exceeds the limit, the last one takes what is left
-    const size_t xyz_bytes = (size_t)vt->el_words * 12, aff_bytes = (size_t)vt->el_words * 8, fr_bytes = (size_t)vt->fr_words * 4;
+    const size_t xyz_bytes = (size_t)vt->el_words * 12, aff_bytes = (size_t)vt->el_words * 8;
+    const size_t fr_bytes = ss ? ss->elem_bytes(vt) : (size_t)vt->fr_words * 4;   // one bit length for all ranges
     int rc = ensure_partials(ctx);
     if (rc) return rc;
     amdmsm_opts o = AMDMSM_OPTS_INIT;
@@ -966,7 +1008,7 @@ int msm_device_ranges(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d
         const size_t lo = k * one, cnt = (k == parts - 1) ? n - lo : one;
         rc = msm_device_impl(ctx, vt, (const uint32_t *)((const char *)d_bases + lo * aff_bytes),
                              (const uint32_t *)((const char *)d_scalars + lo * fr_bytes), cnt,
-                             (uint32_t *)((char *)ctx->chunk_partials + k * xyz_bytes), &o);
+                             (uint32_t *)((char *)ctx->chunk_partials + k * xyz_bytes), &o, 0, nullptr, nullptr, ss);
         if (rc) return rc;
     }
     vt->sum_points(st, (const uint32_t *)ctx->chunk_partials, (int)parts, form, d_out);
@@ -1161,7 +1203,7 @@ void amdmsm_ctx_destroy(amdmsm_ctx *ctx) {
             if (ctx->ss.h_stage[b]) (void)hipHostFree(ctx->ss.h_stage[b]);
             if (ctx->ss.streams[b]) (void)hipStreamDestroy(ctx->ss.streams[b]);
         }
-        for (grow_buf *b : {&ctx->hb_src, &ctx->hb_aff, &ctx->hb_sc, &ctx->hb_out, &ctx->hb_stats, &ctx->hb_idx, &ctx->sel_flag, &ctx->sel_gather, &ctx->fb.small, &ctx->fb.table,
+        for (grow_buf *b : {&ctx->hb_src, &ctx->hb_aff, &ctx->hb_sc, &ctx->hb_out, &ctx->hb_stats, &ctx->hb_idx, &ctx->sel_flag, &ctx->sel_gather, &ctx->short_word, &ctx->short_out, &ctx->fb.small, &ctx->fb.table,
                             &ctx->fb.table_aff, &ctx->fb.out, &ctx->ss.d_raw[0], &ctx->ss.d_raw[1], &ctx->ss.d_aff[0],
                             &ctx->ss.d_aff[1], &ctx->ss.d_sc[0], &ctx->ss.d_sc[1], &ctx->ss.partials, &ctx->ss.status}) {
             if (b->p) (void)hipFree(b->p);
@@ -1749,9 +1791,10 @@ int upload_bases_hook(void *arg, hipEvent_t *wait_for) {
 // ctx->hb_out (and the scalar statistics in ctx->hb_stats) -- the caller copies it back.
 // Device buffers are the context's grow-only staging buffers: no allocation in steady state.
 int host_msm_enqueue(amdmsm_ctx *ctx, const group_vtable *vt, const void *bases_xyz, size_t stride, int base_form,
-                     const void *scalars, size_t n, const amdmsm_opts *opts, bool want_stats, bool clear_stats = true) {
+                     const void *scalars, size_t n, const amdmsm_opts *opts, bool want_stats, bool clear_stats = true,
+                     const short_spec *ss = nullptr) {
     const size_t xyz_bytes = (size_t)vt->el_words * 12, aff_bytes = (size_t)vt->el_words * 8;
-    const size_t fr_bytes = (size_t)vt->fr_words * 4;
+    const size_t fr_bytes = ss ? ss->elem_bytes(vt) : (size_t)vt->fr_words * 4;   // packed integers: n * width bytes cross PCIe
     hipStream_t st = ctx->stream;
     int rc = ensure_buf(ctx, ctx->hb_out, xyz_bytes);
     if (rc) return rc;
@@ -1776,7 +1819,7 @@ int host_msm_enqueue(amdmsm_ctx *ctx, const group_vtable *vt, const void *bases_
         d_aff = find_resident_bases(ctx, vt, bases_xyz, stride, base_form, n, &be, &first);
         if (!d_aff && auto_cache_bases(ctx, vt, bases_xyz, stride, base_form, n))
             d_aff = find_resident_bases(ctx, vt, bases_xyz, stride, base_form, n, &be, &first);
-        if (d_aff && be && use_endomorphism(vt, n, &o, 0)) {
+        if (d_aff && be && !ss && use_endomorphism(vt, n, &o, 0)) {
             // resident bases keep their phi(P) records too: built once (whole vector), then every
             // split MSM over them skips k_endo_points
             if (!be->d_endo) {
@@ -1801,14 +1844,14 @@ int host_msm_enqueue(amdmsm_ctx *ctx, const group_vtable *vt, const void *bases_
             hook.fn = upload_bases_hook;
             hook.arg = &up;
         }
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_sc.p, scalars, n * fr_bytes, hipMemcpyHostToDevice, st));
+        if (!(ss && ss->uploaded)) HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_sc.p, scalars, n * fr_bytes, hipMemcpyHostToDevice, st));
         if (want_stats) {
             vt->scalar_stats(st, (const uint32_t *)ctx->hb_sc.p, n, o.scalars_plain ? 0 : 1, (uint32_t *)ctx->hb_stats.p);
             HIP_TRY(ctx, hipGetLastError());
         }
     }
     return msm_device_impl(ctx, vt, (const uint32_t *)d_aff, (const uint32_t *)ctx->hb_sc.p, n, (uint32_t *)ctx->hb_out.p, &o,
-                           0, &hook, d_endo);
+                           0, &hook, d_endo, ss);
 }
 
 // one partial point from the device that produced it to the combining device (xGMI peer copy)
@@ -1825,13 +1868,19 @@ hipError_t copy_partial(hipStream_t st, void *dst, int dst_dev, const void *src,
 // finished before the next one reuses them), the partial points summed at the end.  The result is
 // left in ctx->hb_out in the requested form, the 0 / 1 counters of all ranges in ctx->hb_stats.
 int host_msm_ranges(amdmsm_ctx *ctx, const group_vtable *vt, const void *bases_xyz, size_t stride, int base_form,
-                    const void *scalars, size_t n, const amdmsm_opts *opts, bool want_stats) {
+                    const void *scalars, size_t n, const amdmsm_opts *opts, bool want_stats, const short_spec *ss = nullptr) {
     const size_t maxr = max_range_points();
-    if (n <= maxr) return host_msm_enqueue(ctx, vt, bases_xyz, stride, base_form, scalars, n, opts, want_stats);
+    if (n <= maxr) return host_msm_enqueue(ctx, vt, bases_xyz, stride, base_form, scalars, n, opts, want_stats, true, ss);
     const size_t parts = (n + maxr - 1) / maxr;
     if (parts > MAX_RANGES) return fail(ctx, AMDMSM_ERR_TOO_LARGE, "input too large for one call");
     const size_t one = (n + parts - 1) / parts;   // <= maxr (see msm_device_ranges)
-    const size_t xyz_bytes = (size_t)vt->el_words * 12, fr_bytes = (size_t)vt->fr_words * 4;
+    const size_t xyz_bytes = (size_t)vt->el_words * 12, fr_bytes = ss ? ss->elem_bytes(vt) : (size_t)vt->fr_words * 4;
+    short_spec ss_range;   // a range brings its own scalars in
+    if (ss) {
+        ss_range = *ss;
+        ss_range.uploaded = false;
+        ss = &ss_range;
+    }
     int rc = ensure_partials(ctx);
     if (rc) return rc;
     amdmsm_opts o = AMDMSM_OPTS_INIT;
@@ -1843,7 +1892,7 @@ int host_msm_ranges(amdmsm_ctx *ctx, const group_vtable *vt, const void *bases_x
     for (size_t k = 0; k < parts; ++k) {
         const size_t lo = k * one, cnt = (k == parts - 1) ? n - lo : one;
         rc = host_msm_enqueue(ctx, vt, (const char *)bases_xyz + lo * stride, stride, base_form,
-                              (const char *)scalars + lo * fr_bytes, cnt, &o, want_stats, k == 0);
+                              (const char *)scalars + lo * fr_bytes, cnt, &o, want_stats, k == 0, ss);
         if (rc) return rc;
         HIP_TRY(ctx, hipMemcpyAsync((char *)ctx->chunk_partials + k * xyz_bytes, ctx->hb_out.p, xyz_bytes,
                                     hipMemcpyDeviceToDevice, st));
@@ -1865,16 +1914,25 @@ int check_host_args(amdmsm_ctx *ctx, const group_vtable *vt, const void *bases_x
 }
 
 int host_multi_exp(amdmsm_ctx *ctx, const group_vtable *vt, const void *bases_xyz, size_t stride, int base_form,
-                   const void *scalars, size_t n, void *out_xyz, const amdmsm_opts *opts, size_t stats[3]) {
+                   const void *scalars, size_t n, void *out_xyz, const amdmsm_opts *opts, size_t stats[3],
+                   const short_spec *ss = nullptr) {
     int rc = check_host_args(ctx, vt, bases_xyz, stride, scalars, n, out_xyz);
     if (rc) return rc;
-    rc = host_msm_ranges(ctx, vt, bases_xyz, stride, base_form, scalars, n, opts, stats != nullptr);
+    rc = host_msm_ranges(ctx, vt, bases_xyz, stride, base_form, scalars, n, opts, stats != nullptr, ss);
     if (rc) {
         (void)hipDeviceSynchronize();   // nothing of this call may still touch the staging buffers
         return rc;
     }
     hipStream_t st = ctx->stream;
     uint32_t hs[4] = {};
+    if (ss && ss->flag) {
+        // a promise was tested by the digit passes: the result reaches the caller's buffer only if it was kept
+        uint32_t raised = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&raised, ss->flag, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream));
+        if (raised) return fail(ctx, AMDMSM_ERR_BAD_ARG, "a scalar is not below 2^bits (amdmsm_scalar_desc.bits is a promise)");
+    }
     HIP_TRY(ctx, hipMemcpyAsync(out_xyz, ctx->hb_out.p, (size_t)vt->el_words * 12, hipMemcpyDeviceToHost, st));
     if (stats) HIP_TRY(ctx, hipMemcpyAsync(hs, ctx->hb_stats.p, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -1896,6 +1954,226 @@ int amdmsm_multi_exp(amdmsm_ctx *ctx, int curve, int group, const void *bases_xy
     GET_VT(ctx, curve, group);
     CHECK_OPTS(ctx, opts);
     return host_multi_exp(ctx, vt, bases_xyz, base_stride_bytes, base_form, scalars, n, out_xyz, opts, nullptr);
+}
+
+// ---- scalars known to be short -------------------------------------------------------------------------------------
+}   // extern "C"
+
+namespace {
+
+// How a call whose scalars are below 2^bits runs.  The endomorphism split is kept only where today's rule would use it
+// AND bits exceeds the split's own bound on |k1|, |k2| -- below that bound the split cannot shorten anything and the
+// plain path with windows for bits + 2 bits is taken.  bits at or above Fr::num_bits is the ordinary plan.
+enum short_route { ROUTE_ORDINARY = 0, ROUTE_SHORT = 1 };
+short_route route_short(const group_vtable *vt, size_t n, const amdmsm_opts *opts, int kind, int bits) {
+    if (kind != AMDMSM_SCALAR_FR) return ROUTE_SHORT;   // packed integers have no full-width digit pass; 64 bits are below every bound
+    if (bits >= vt->fr_bits) return ROUTE_ORDINARY;
+    if (bits * 1000 > vt->glv_bound_log2_x1000 && use_endomorphism(vt, n, opts, 0)) return ROUTE_ORDINARY;
+    return ROUTE_SHORT;
+}
+
+int kind_width_bits(const group_vtable *vt, int kind) { return kind == AMDMSM_SCALAR_FR ? vt->fr_bits : 8 * kind; }
+
+// argument rules of the short entries; *bits_full = the kind's full width
+int check_short_args(amdmsm_ctx *ctx, const group_vtable *vt, const amdmsm_scalar_desc *desc, const void *scalars, size_t n,
+                     const amdmsm_opts *opts) {
+    if (!desc) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null amdmsm_scalar_desc");
+    if (desc->struct_size != sizeof(amdmsm_scalar_desc))
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "amdmsm_scalar_desc.struct_size does not match this library: initialise with AMDMSM_SCALAR_DESC_INIT");
+    const int k = desc->kind;
+    if (k != AMDMSM_SCALAR_FR && k != AMDMSM_SCALAR_U8 && k != AMDMSM_SCALAR_U16 && k != AMDMSM_SCALAR_U32 && k != AMDMSM_SCALAR_U64)
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "amdmsm_scalar_desc.kind is not an AMDMSM_SCALAR_* value");
+    if (desc->bits < -1 || desc->bits > kind_width_bits(vt, k))
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "amdmsm_scalar_desc.bits must be -1, 0 or 1 .. the kind's width");
+    if (opts && opts->window_bits > 22) return fail(ctx, AMDMSM_ERR_BAD_ARG, "window_bits > 22 is not available for short scalars");
+    if (opts && (opts->window_bits < 0 || opts->window_bits == 1)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "bad window_bits");
+    if (k != AMDMSM_SCALAR_FR && n && ((uintptr_t)scalars % (uintptr_t)k))
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "scalars must be aligned to the element width");
+    return AMDMSM_OK;
+}
+
+// bit length of the longest of n device-resident scalars, added to what *acc (device word) already holds
+int measure_enqueue(amdmsm_ctx *ctx, const group_vtable *vt, const void *d_scalars, int kind, size_t n, int mont, uint32_t *acc,
+                    hipStream_t st) {
+    vt->scalar_bits(st, d_scalars, kind, n, mont, acc);
+    HIP_TRY(ctx, hipGetLastError());
+    return AMDMSM_OK;
+}
+
+int read_word(amdmsm_ctx *ctx, const uint32_t *d_word, hipStream_t st, uint32_t *out) {
+    HIP_TRY(ctx, hipMemcpyAsync(out, d_word, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return AMDMSM_OK;
+}
+
+int scalar_bits_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const void *d_scalars, int kind, size_t n, int mont,
+                            hipStream_t st, int *bits) {
+    int rc = ensure_buf(ctx, ctx->short_word, 8);
+    if (rc) return rc;
+    uint32_t *acc = (uint32_t *)ctx->short_word.p + 1;
+    HIP_TRY(ctx, hipMemsetAsync(acc, 0, 4, st));
+    rc = measure_enqueue(ctx, vt, d_scalars, kind, n, mont, acc, st);
+    if (rc) return rc;
+    uint32_t v = 0;
+    rc = read_word(ctx, acc, st, &v);
+    if (rc) return rc;
+    *bits = (int)v;
+    return AMDMSM_OK;
+}
+
+}   // namespace
+
+extern "C" {
+
+int amdmsm_plan_short(int curve, int group, size_t n, int window_bits, int endomorphism, int scalar_bits, int *c,
+                      int *num_windows, uint32_t *num_buckets, size_t *workspace_bytes, int *endomorphism_used) {
+    const group_vtable *vt = find_vt(curve, group);
+    if (!vt) return AMDMSM_ERR_UNSUPPORTED;
+    if (scalar_bits < 0 || window_bits > 22) return AMDMSM_ERR_BAD_ARG;
+    amdmsm_opts o = AMDMSM_OPTS_INIT;
+    o.window_bits = window_bits;
+    o.endomorphism = endomorphism;
+    if (scalar_bits == 0 || route_short(vt, n, &o, AMDMSM_SCALAR_FR, scalar_bits) == ROUTE_ORDINARY)
+        return amdmsm_plan_ex(curve, group, n, window_bits, endomorphism, c, num_windows, num_buckets, workspace_bytes,
+                              endomorphism_used);
+    plan_t p;
+    const int rc = make_plan(vt, n, window_bits, 0, p, 0, 0, 0, false, false, 1, 0, scalar_bits);
+    if (rc) return rc;
+    if (c) *c = p.c;
+    if (num_windows) *num_windows = p.W;
+    if (num_buckets) *num_buckets = p.B;
+    if (workspace_bytes) *workspace_bytes = p.total;
+    if (endomorphism_used) *endomorphism_used = 0;
+    return AMDMSM_OK;
+}
+
+int amdmsm_scalar_bits_device(amdmsm_ctx *ctx, int curve, int group, const void *d_scalars, size_t n,
+                              const amdmsm_scalar_desc *desc, int scalars_plain, int *bits) {
+    GET_VT(ctx, curve, group);
+    int rc = check_short_args(ctx, vt, desc, d_scalars, n, nullptr);
+    if (rc) return rc;
+    if (!bits || (n && !d_scalars)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null pointer");
+    return scalar_bits_device_impl(ctx, vt, d_scalars, desc->kind, n, scalars_plain ? 0 : 1, ctx->stream, bits);
+}
+
+int amdmsm_msm_device_short(amdmsm_ctx *ctx, int curve, int group, const void *d_bases_affine, const void *d_scalars,
+                            const amdmsm_scalar_desc *desc, size_t n, void *d_out_xyz, const amdmsm_opts *opts) {
+    GET_VT(ctx, curve, group);
+    CHECK_OPTS(ctx, opts);
+    int rc = check_short_args(ctx, vt, desc, d_scalars, n, opts);
+    if (rc) return rc;
+    if (!d_out_xyz || (n && (!d_bases_affine || !d_scalars))) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null pointer");
+    hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : ctx->stream;
+    const int kind = desc->kind, full = kind_width_bits(vt, kind);
+    const int mont = (opts && opts->scalars_plain) ? 0 : 1;
+    const uint32_t *bases = (const uint32_t *)d_bases_affine;
+    uint32_t *out = (uint32_t *)d_out_xyz;
+    if (n == 0 || (kind == AMDMSM_SCALAR_FR && (desc->bits == 0 || desc->bits >= full)))
+        return msm_device_ranges(ctx, vt, bases, (const uint32_t *)d_scalars, n, out, opts);
+    int bits = desc->bits ? desc->bits : full;
+    bool promise = desc->bits > 0 && desc->bits < full;
+    if (desc->bits == -1) {
+        rc = scalar_bits_device_impl(ctx, vt, d_scalars, kind, n, mont, st, &bits);
+        if (rc) return rc;
+        if (bits == 0) return msm_device_impl(ctx, vt, bases, nullptr, 0, out, opts);   // every scalar is zero: the group's zero, no plan
+    }
+    if (route_short(vt, n, opts, kind, bits) == ROUTE_ORDINARY) {
+        // the split (or the full-width plan) serves this length: the ordinary digit pass, which tests nothing -- a
+        // promise is checked by the measuring pass before anything else is launched
+        if (promise) {
+            int longest = 0;
+            rc = scalar_bits_device_impl(ctx, vt, d_scalars, kind, n, mont, st, &longest);
+            if (rc) return rc;
+            if (longest > bits) return fail(ctx, AMDMSM_ERR_BAD_ARG, "a scalar is not below 2^bits (amdmsm_scalar_desc.bits is a promise)");
+        }
+        return msm_device_ranges(ctx, vt, bases, (const uint32_t *)d_scalars, n, out, opts);
+    }
+    short_spec ss;
+    ss.kind = kind;
+    ss.bits = bits;
+    if (!promise) return msm_device_ranges(ctx, vt, bases, (const uint32_t *)d_scalars, n, out, opts, &ss);   // asynchronous
+    // a promise: the digit pass tests it, and the result is held back until the flag has been read
+    const size_t xyz_bytes = (size_t)vt->el_words * 12;
+    rc = ensure_buf(ctx, ctx->short_word, 8);
+    if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->short_out, xyz_bytes);
+    if (rc) return rc;
+    ss.flag = (uint32_t *)ctx->short_word.p;
+    HIP_TRY(ctx, hipMemsetAsync(ss.flag, 0, 4, st));
+    rc = msm_device_ranges(ctx, vt, bases, (const uint32_t *)d_scalars, n, (uint32_t *)ctx->short_out.p, opts, &ss);
+    if (rc) return rc;
+    uint32_t raised = 0;
+    rc = read_word(ctx, ss.flag, st, &raised);
+    if (rc) return rc;
+    if (raised) return fail(ctx, AMDMSM_ERR_BAD_ARG, "a scalar is not below 2^bits (amdmsm_scalar_desc.bits is a promise)");
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->short_out.p, xyz_bytes, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));   // the held-back result is the context's
+    return AMDMSM_OK;
+}
+
+int amdmsm_multi_exp_short(amdmsm_ctx *ctx, int curve, int group, const void *bases_xyz, size_t base_stride_bytes,
+                           int base_form, const void *scalars, const amdmsm_scalar_desc *desc, size_t n, void *out_xyz,
+                           const amdmsm_opts *opts) {
+    GET_VT(ctx, curve, group);
+    CHECK_OPTS(ctx, opts);
+    int rc = check_short_args(ctx, vt, desc, scalars, n, opts);
+    if (rc) return rc;
+    size_t stride = base_stride_bytes;
+    rc = check_host_args(ctx, vt, bases_xyz, stride, scalars, n, out_xyz);
+    if (rc) return rc;
+    const int kind = desc->kind, full = kind_width_bits(vt, kind);
+    if (n == 0 || (kind == AMDMSM_SCALAR_FR && (desc->bits == 0 || desc->bits >= full)))
+        return host_multi_exp(ctx, vt, bases_xyz, stride, base_form, scalars, n, out_xyz, opts, nullptr);
+    hipStream_t st = ctx->stream;
+    amdmsm_opts o = AMDMSM_OPTS_INIT;
+    if (opts) o = *opts;
+    else o.out_form = AMDMSM_OUT_LIBFF;
+    const int mont = o.scalars_plain ? 0 : 1;
+    short_spec ss;
+    ss.kind = kind;
+    const size_t eb = ss.elem_bytes(vt), maxr = max_range_points();
+    int bits = desc->bits ? desc->bits : full;
+    const bool promise = desc->bits > 0 && desc->bits < full;
+    rc = ensure_buf(ctx, ctx->short_word, 8);
+    if (rc) return rc;
+    // one bit length for the whole call: measured (bits = -1, or a promise the ordinary digit pass cannot test) over
+    // every range before anything is planned; a call of one range keeps the scalars it uploaded for that
+    auto measure = [&](int *longest) -> int {
+        uint32_t *acc = (uint32_t *)ctx->short_word.p + 1;
+        HIP_TRY(ctx, hipMemsetAsync(acc, 0, 4, st));
+        for (size_t lo = 0; lo < n; lo += maxr) {
+            const size_t cnt = std::min(maxr, n - lo);
+            int r = ensure_buf(ctx, ctx->hb_sc, cnt * eb);
+            if (r) return r;
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_sc.p, (const char *)scalars + lo * eb, cnt * eb, hipMemcpyHostToDevice, st));
+            r = measure_enqueue(ctx, vt, ctx->hb_sc.p, kind, cnt, mont, acc, st);
+            if (r) return r;
+        }
+        uint32_t v = 0;
+        const int r = read_word(ctx, acc, st, &v);
+        *longest = (int)v;
+        return r;
+    };
+    if (desc->bits == -1) {
+        rc = measure(&bits);
+        if (rc) return rc;
+        if (bits == 0) return host_multi_exp(ctx, vt, bases_xyz, stride, base_form, scalars, 0, out_xyz, opts, nullptr);   // the group's zero
+        ss.uploaded = n <= maxr;
+    }
+    if (route_short(vt, n, &o, kind, bits) == ROUTE_ORDINARY) {
+        if (promise) {
+            int longest = 0;
+            rc = measure(&longest);
+            if (rc) return rc;
+            if (longest > bits) return fail(ctx, AMDMSM_ERR_BAD_ARG, "a scalar is not below 2^bits (amdmsm_scalar_desc.bits is a promise)");
+        }
+        return host_multi_exp(ctx, vt, bases_xyz, stride, base_form, scalars, n, out_xyz, opts, nullptr);
+    }
+    ss.bits = bits;
+    if (promise) {
+        ss.flag = (uint32_t *)ctx->short_word.p;
+        HIP_TRY(ctx, hipMemsetAsync(ss.flag, 0, 4, st));
+    }
+    return host_multi_exp(ctx, vt, bases_xyz, stride, base_form, scalars, n, out_xyz, opts, nullptr, &ss);
 }
 
 int amdmsm_multi_exp_filter_one_zero(amdmsm_ctx *ctx, int curve, int group, const void *bases_xyz,

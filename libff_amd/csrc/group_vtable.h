@@ -212,6 +212,16 @@ struct group_vtable {
     // out[i] = the scalar base i selects, copied as it is stored (same selection and guard as sort_sel)
     void (*gather_scalars)(hipStream_t, const uint32_t* shared, size_t shared_n, const uint32_t* index, size_t offset,
                            uint32_t* flag, size_t n, uint32_t* out);
+
+    // Scalars known to be short (amdmsm_*_short).  kind = AMDMSM_SCALAR_*: 0 = Fr records (mont as for `sort`), else the
+    // bytes of one packed little-endian unsigned integer (1, 2, 4, 8; the pointer needs that alignment only).
+    // *out_bits = max(*out_bits, bit length of the longest scalar); one word, cleared by the caller
+    void (*scalar_bits)(hipStream_t, const void* scalars, int kind, size_t n, int mont, uint32_t* out_bits);
+    // `sort` (mode 0) with W sized for scalars below 2^limit_bits.  A scalar that is not counts as 0 and sets *flag (one
+    // word, cleared by the caller) to nonzero; limit_bits at the kind's full width tests nothing and flag may be null.
+    void (*sort_short)(hipStream_t, const void* scalars, int kind, int limit_bits, uint32_t* flag, size_t n, int mont, int c, int W,
+                       uint32_t* coarse, uint32_t* cursor, int32_t* digits, uint32_t* tmp_payload, uint32_t* tmp_key,
+                       uint32_t* ends, uint32_t* lists, size_t stride, uint32_t* big);
 };
 
 const group_vtable* vt_alt_bn128_g1() __attribute__((weak));

@@ -743,6 +743,184 @@ __global__ void __launch_bounds__(TPB) k_gather_scalars(const uint32_t* __restri
     fp_store(out + i * FRW, x);
 }
 
+// ------------------------------------------------- scalars known to be short (amdmsm_*_short)
+// KIND = AMDMSM_SCALAR_*: 0 = Fr records, otherwise the bytes of one packed little-endian unsigned integer (1, 2, 4, 8).
+// Packed integers are read 16 bytes per lane -- 16 / 8 / 4 / 2 consecutive elements -- wherever the vector is 16-byte
+// aligned; the pointer itself needs only the element's alignment, so up to 16 / WB - 1 elements in front of the first
+// boundary ("head") and as many behind the last whole vector ("tail") are read one by one.  Work items of a pass:
+// item t < nvec is the vector of elements head + t * EPL ..., item nvec + e is single element e of head and tail.
+template <int WB>
+struct packed_split {
+    static constexpr int EPL = 16 / WB;
+    size_t head, nvec, rest;   // rest = head + tail
+    AMDMSM_HD packed_split(const void* p, size_t n) {
+        const size_t mis = (size_t)(reinterpret_cast<uintptr_t>(p) & 15u);
+        head = mis ? (16 - mis) / WB : 0;
+        if (head > n) head = n;
+        nvec = (n - head) / EPL;
+        rest = n - nvec * EPL;
+    }
+    AMDMSM_HD size_t items() const { return nvec + rest; }
+    AMDMSM_HD size_t single_index(size_t t) const {
+        const size_t e = t - nvec;
+        return e < head ? e : nvec * EPL + e;
+    }
+};
+template <int WB>
+AMDMSM_DEV uint64_t packed_elem(const uint32_t (&v)[4], int j) {   // j is a constant after unrolling
+    if (WB == 8) return (uint64_t)v[(2 * j) & 3] | ((uint64_t)v[(2 * j + 1) & 3] << 32);
+    if (WB == 4) return v[j & 3];
+    if (WB == 2) return (v[(j >> 1) & 3] >> (16 * (j & 1))) & 0xffffu;
+    return (v[(j >> 2) & 3] >> (8 * (j & 3))) & 0xffu;
+}
+template <int WB>
+AMDMSM_DEV uint64_t packed_one(const void* p, size_t i) {
+    if (WB == 8) return reinterpret_cast<const uint64_t*>(p)[i];
+    if (WB == 4) return reinterpret_cast<const uint32_t*>(p)[i];
+    if (WB == 2) return reinterpret_cast<const unsigned short*>(p)[i];
+    return reinterpret_cast<const unsigned char*>(p)[i];
+}
+AMDMSM_DEV void packed_vec(uint32_t (&v)[4], const void* p, size_t byte_off) {
+    const uint4 q = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(p) + byte_off);
+    v[0] = q.x;
+    v[1] = q.y;
+    v[2] = q.z;
+    v[3] = q.w;
+}
+
+// Bit length of the longest scalar: *out = max(*out, max_i bits(scalar i)); *out is cleared by the caller.
+// Fr records are reduced first (load_scalar), packed integers are OR-ed together.  One atomic per wave.
+template <int KIND>
+__global__ void __launch_bounds__(TPB) k_scalar_bits(const void* __restrict__ scalars, size_t n, int mont,
+                                                     uint32_t* __restrict__ out) {
+    uint32_t top = 0;
+    const size_t step = (size_t)gridDim.x * TPB;
+    if constexpr (KIND == 0) {
+        for (size_t i = gtid(); i < n; i += step) {
+            uint32_t s[FRW];
+            load_scalar(s, reinterpret_cast<const uint32_t*>(scalars), i, mont);
+            uint32_t b = 0;
+#pragma unroll
+            for (int j = 0; j < FRW; ++j) {
+                if (s[j]) b = 32u * j + 32u - (uint32_t)__clz((int)s[j]);
+            }
+            top = b > top ? b : top;
+        }
+    } else {
+        const packed_split<KIND> sp(scalars, n);
+        uint64_t acc = 0;
+        for (size_t t = gtid(); t < sp.items(); t += step) {
+            if (t < sp.nvec) {
+                uint32_t v[4];
+                packed_vec(v, scalars, (sp.head * KIND) + t * 16);
+                acc |= (uint64_t)(v[0] | v[2]) | ((uint64_t)(v[1] | v[3]) << 32);
+            } else {
+                acc |= packed_one<KIND>(scalars, sp.single_index(t));
+            }
+        }
+        if (KIND < 8) acc = (acc | (acc >> 32)) & 0xffffffffull;   // elements narrower than a word: fold the halves
+        if (KIND == 2) acc = (acc | (acc >> 16)) & 0xffffull;
+        if (KIND == 1) {
+            acc |= acc >> 16;
+            acc = (acc | (acc >> 8)) & 0xffull;
+        }
+        top = acc ? 64u - (uint32_t)__clzll((long long)acc) : 0u;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)top, off, 64);
+        top = o > top ? o : top;
+    }
+    if ((threadIdx.x & 63u) == 0 && top) atomicMax(out, top);
+}
+
+// The digit pass of the two-level sort (k_sort_digits, mode 0) for scalars below 2^limit_bits: W covers limit_bits + 2
+// bits only.  A kernel of its own, body and all, for the reason given above k_sort_digits_sel.
+//   packed integers: the scalar is one or two words in registers; a lane recodes the 16 / 8 / 4 / 2 elements of its
+//     16-byte load one after the other, so the digit columns a wave writes are one contiguous run per window
+//   Fr records: reduced as usual; the words at and above limit_bits are known to be zero and W ends the recoding after
+//     the digits the low ceil(limit_bits / 32) words fill
+// A scalar with a bit at or above limit_bits (a broken promise) raises *flag and counts as 0; limit_bits at the
+// kind's full width tests nothing and flag is not touched.
+template <int KIND>
+__global__ void __launch_bounds__(SORT_TPB) k_sort_digits_short(const void* __restrict__ scalars, size_t n, int mont, int c,
+                                                                int W, int hb, uint32_t per_block, int32_t* __restrict__ digits,
+                                                                size_t stride, uint32_t* __restrict__ coarse_counts,
+                                                                int limit_bits, uint32_t* __restrict__ flag) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];   // [W][2^hb]
+    const uint32_t nbin = 1u << hb;
+    const int fb = c - 1 - hb;
+    const uint32_t nctr = (uint32_t)W * nbin;
+    for (uint32_t j = threadIdx.x; j < nctr; j += SORT_TPB) smem[j] = 0;
+    __syncthreads();
+    const size_t base = (size_t)blockIdx.x * per_block;
+    if constexpr (KIND == 0) {
+        for (uint32_t k = threadIdx.x; k < per_block; k += SORT_TPB) {
+            const size_t i = base + k;
+            if (i >= n) break;
+            uint32_t s[FRW];
+            load_scalar(s, reinterpret_cast<const uint32_t*>(scalars), i, mont);
+            uint32_t over = 0;
+#pragma unroll
+            for (int j = 0; j < FRW; ++j) {
+                const int lo = limit_bits - 32 * j;   // bits of word j below the limit
+                over |= lo <= 0 ? s[j] : (lo < 32 ? s[j] >> lo : 0u);
+            }
+            if (over) {
+                atomicOr(flag, 1u);
+#pragma unroll
+                for (int j = 0; j < FRW; ++j) s[j] = 0;
+            }
+            for_each_signed_digit(s, c, W, [&](int w, int32_t d) {
+                digits[(size_t)w * stride + i] = d;
+                if (d != 0) {
+                    const uint32_t idx = (uint32_t)(d < 0 ? -d : d) - 1u;
+                    atomicAdd(&smem[(uint32_t)w * nbin + (idx >> fb)], 1u);
+                }
+            });
+        }
+    } else {
+        constexpr int NW = KIND == 8 ? 2 : 1;
+        const packed_split<KIND> sp(scalars, n);
+        const size_t items = sp.items();
+        auto recode = [&](uint64_t v, size_t i) {
+            if (limit_bits < 8 * KIND && (v >> limit_bits) != 0) {
+                atomicOr(flag, 1u);
+                v = 0;
+            }
+            uint32_t s[NW];
+            s[0] = (uint32_t)v;
+            if (NW > 1) s[NW - 1] = (uint32_t)(v >> 32);
+            for_each_signed_digit(s, c, W, [&](int w, int32_t d) {
+                digits[(size_t)w * stride + i] = d;
+                if (d != 0) {
+                    const uint32_t idx = (uint32_t)(d < 0 ? -d : d) - 1u;
+                    atomicAdd(&smem[(uint32_t)w * nbin + (idx >> fb)], 1u);
+                }
+            });
+        };
+        for (uint32_t k = threadIdx.x; k < per_block; k += SORT_TPB) {
+            const size_t t = base + k;
+            if (t >= items) break;
+            if (t < sp.nvec) {
+                uint32_t v[4];
+                packed_vec(v, scalars, (sp.head * KIND) + t * 16);
+                const size_t i0 = sp.head + t * packed_split<KIND>::EPL;
+#pragma unroll
+                for (int j = 0; j < packed_split<KIND>::EPL; ++j) recode(packed_elem<KIND>(v, j), i0 + j);
+            } else {
+                const size_t i = sp.single_index(t);
+                recode(packed_one<KIND>(scalars, i), i);
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < nctr; j += SORT_TPB) {
+        const uint32_t v = smem[j];
+        if (v) atomicAdd(&coarse_counts[(j / nbin) * (nbin + 1) + (j % nbin)], v);
+    }
+}
+
 // Workgroup (tile, w) of the coarse pass.  Two of them share a CU (profiles/r05_sort_two_workgroups.txt: one workgroup
 // per CU spent three quarters of its wave-cycles waiting on the phase in front), so a tile costs 64 KiB of staging and
 // at most 64 registers per lane:
@@ -3099,11 +3277,19 @@ void l_scatter(hipStream_t st, const uint32_t* scalars, size_t n, int mont, int 
     if (!n) return;
     hipLaunchKernelGGL(k_scatter, dim3(blocks_for(n)), dim3(TPB), 0, st, scalars, n, mont, c, W, cursor, lists, list_stride);
 }
+// the short-scalar form of the digit pass (group_vtable::sort_short); scalars then points at elements of that kind
+struct short_src {
+    int kind, limit_bits;
+    uint32_t* flag;
+};
+template <int WB>
+size_t packed_items(const void* p, size_t n) { return packed_split<WB>(p, n).items(); }
 // digits / lists may alias (digits are dead once k_sort_coarse has run)
 // sel != null: the selecting form of the digit pass (group_vtable::sort_sel); everything behind it is the same
 void sort_launch(hipStream_t st, const uint32_t* scalars, size_t n, int mont, int c, int W, uint32_t* coarse,
                  uint32_t* cursor, int32_t* digits, uint32_t* tmp_payload, uint32_t* tmp_key, uint32_t* ends, uint32_t* lists,
-                 size_t stride, uint32_t* big, int mode, hipEvent_t after_coarse, const scalar_sel* sel) {
+                 size_t stride, uint32_t* big, int mode, hipEvent_t after_coarse, const scalar_sel* sel,
+                 const short_src* ss = nullptr) {
     if (!n) return;
     // mode 1 (flat): one list of n*W entries (entry i*W + j = digit j of scalar i), one bucket set
     // mode 2 (endomorphism split): 2n columns of W digits
@@ -3116,7 +3302,26 @@ void sort_launch(hipStream_t st, const uint32_t* scalars, size_t n, int mont, in
     // scalars per k_sort_digits workgroup: enough workgroups for every CU, few enough global atomics
     uint32_t per_block = 8192;
     while (per_block > SORT_TPB && (n + per_block - 1) / per_block < 1024) per_block >>= 1;
-    if (sel)
+    if (ss) {
+        // packed integers: a work item is one 16-byte vector of elements, so the workgroups are cut by items and may
+        // be smaller than SORT_TPB items (a million bytes are 65536 items)
+        const int k = ss->kind;
+        const size_t items = k == 1 ? packed_items<1>(scalars, n) : k == 2 ? packed_items<2>(scalars, n) : k == 4 ? packed_items<4>(scalars, n)
+                             : k == 8 ? packed_items<8>(scalars, n) : n;
+        uint32_t pb = 8192;
+        while (pb > (k ? 256u : (uint32_t)SORT_TPB) && (items + pb - 1) / pb < 1024) pb >>= 1;
+        const dim3 grid((unsigned)((items + pb - 1) / pb));
+        const size_t lds = (size_t)W * nbin * 4;
+#define AMDMSM_LAUNCH_SHORT(K)                                                                                              \
+    hipLaunchKernelGGL(k_sort_digits_short<K>, grid, dim3(SORT_TPB), lds, st, (const void*)scalars, n, mont, c, W, hb, pb, digits, \
+                       stride, coarse, ss->limit_bits, ss->flag)
+        if (k == 1) AMDMSM_LAUNCH_SHORT(1);
+        else if (k == 2) AMDMSM_LAUNCH_SHORT(2);
+        else if (k == 4) AMDMSM_LAUNCH_SHORT(4);
+        else if (k == 8) AMDMSM_LAUNCH_SHORT(8);
+        else AMDMSM_LAUNCH_SHORT(0);
+#undef AMDMSM_LAUNCH_SHORT
+    } else if (sel)
         hipLaunchKernelGGL(k_sort_digits_sel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(SORT_TPB),
                            (size_t)(flat ? 1 : W) * nbin * 4, st, scalars, n, mont, c, W, hb, per_block, digits, stride, coarse,
                            mode, sel->index, sel->offset, sel->shared_n, sel->flag);
@@ -3186,6 +3391,24 @@ void l_sort_sel(hipStream_t st, const uint32_t* shared, size_t shared_n, const u
     const scalar_sel sel{index, offset, shared_n, flag};
     sort_launch(st, shared, n, mont, c, W, coarse, cursor, digits, tmp_payload, tmp_key, ends, lists, stride, big, mode,
                 nullptr, &sel);
+}
+void l_sort_short(hipStream_t st, const void* scalars, int kind, int limit_bits, uint32_t* flag, size_t n, int mont, int c, int W,
+                  uint32_t* coarse, uint32_t* cursor, int32_t* digits, uint32_t* tmp_payload, uint32_t* tmp_key, uint32_t* ends,
+                  uint32_t* lists, size_t stride, uint32_t* big) {
+    const short_src ss{kind, limit_bits, flag};
+    sort_launch(st, (const uint32_t*)scalars, n, mont, c, W, coarse, cursor, digits, tmp_payload, tmp_key, ends, lists, stride, big, 0,
+                nullptr, nullptr, &ss);
+}
+void l_scalar_bits(hipStream_t st, const void* scalars, int kind, size_t n, int mont, uint32_t* out) {
+    if (!n) return;
+    const size_t items = kind == 1 ? packed_items<1>(scalars, n) : kind == 2 ? packed_items<2>(scalars, n)
+                         : kind == 4 ? packed_items<4>(scalars, n) : kind == 8 ? packed_items<8>(scalars, n) : n;
+    const dim3 grid((unsigned)std::min<size_t>((items + TPB - 1) / TPB, 4096));
+    if (kind == 1) hipLaunchKernelGGL(k_scalar_bits<1>, grid, dim3(TPB), 0, st, scalars, n, mont, out);
+    else if (kind == 2) hipLaunchKernelGGL(k_scalar_bits<2>, grid, dim3(TPB), 0, st, scalars, n, mont, out);
+    else if (kind == 4) hipLaunchKernelGGL(k_scalar_bits<4>, grid, dim3(TPB), 0, st, scalars, n, mont, out);
+    else if (kind == 8) hipLaunchKernelGGL(k_scalar_bits<8>, grid, dim3(TPB), 0, st, scalars, n, mont, out);
+    else hipLaunchKernelGGL(k_scalar_bits<0>, grid, dim3(TPB), 0, st, scalars, n, mont, out);
 }
 void l_gather_scalars(hipStream_t st, const uint32_t* shared, size_t shared_n, const uint32_t* index, size_t offset,
                       uint32_t* flag, size_t n, uint32_t* out) {
@@ -3434,7 +3657,7 @@ const group_vtable g_vt = {
     GLV::BOUND_LOG2_X1000, GP::SUBGROUP_CHECK == 0 ? 1 : 0, GLV::LAMBDA, l_endo_points, l_glv_digits,
     l_import_bases, l_precompute_table, l_count, l_scatter, l_scalar_stats, l_sort, l_accumulate, l_accumulate_resident_lanes, (AMDMSM_OVERLAP_OK && ACC_OVERLAP_LDS) ? 1 : 0, l_accumulate_fixup, l_reduce_segments, l_sum_butterfly, l_sum_block, l_reduce_rowcol, l_horner, l_horner_batch, l_sum_points,
     l_gen_bases_seq, l_export_affine, l_ffi_decode_points, l_ffi_decode_scalars, l_ffi_encode_point, l_disk_decode, l_disk_decode_compressed, l_fixed_base_exp, l_field_op, l_group_op, l_digits, l_mul_bench, l_madd_bench,
-    GP::HAS_ENDO ? 1 : 0, GP::COEFF_A != 0 ? 1 : 0, l_sort_sel, l_gather_scalars,
+    GP::HAS_ENDO ? 1 : 0, GP::COEFF_A != 0 ? 1 : 0, l_sort_sel, l_gather_scalars, l_scalar_bits, l_sort_short,
 };
 
 }  // namespace

@@ -60,7 +60,10 @@ EXPORTED_SYMBOLS = [
     "amdmsm_get_slot_timings", "amdmsm_field_op_device", "amdmsm_group_op_device",
     "amdmsm_digits_device", "amdmsm_mul_bench_device", "amdmsm_madd_bench_device", "amdmsm_malloc", "amdmsm_free",
     "amdmsm_memcpy_h2d", "amdmsm_memcpy_d2h", "amdmsm_synchronize",
+    "amdmsm_plan_short", "amdmsm_scalar_bits_device", "amdmsm_multi_exp_short", "amdmsm_msm_device_short",
 ]
+# amdmsm_scalar_desc.kind: Fr records, or the width in bytes of packed little-endian unsigned integers
+SCALAR_FR, SCALAR_U8, SCALAR_U16, SCALAR_U32, SCALAR_U64 = 0, 1, 2, 4, 8
 
 
 class AmdMsmError(RuntimeError):
@@ -79,6 +82,18 @@ class BatchItemStruct(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("bases", ctypes.c_void_p), ("n", ctypes.c_size_t),
                 ("scalars", ctypes.c_void_p), ("shared_offset", ctypes.c_size_t), ("index", ctypes.c_void_p),
                 ("out_xyz", ctypes.c_void_p)]
+
+
+class ScalarDesc(ctypes.Structure):
+    # include/amdmsm.h amdmsm_scalar_desc
+    _fields_ = [("struct_size", ctypes.c_uint32), ("kind", ctypes.c_int), ("bits", ctypes.c_int)]
+
+
+def scalar_desc(kind, bits=0):
+    return ScalarDesc(ctypes.sizeof(ScalarDesc), int(kind), int(bits))
+
+
+_INT_KINDS = {"uint8": SCALAR_U8, "uint16": SCALAR_U16, "uint32": SCALAR_U32, "uint64": SCALAR_U64}
 
 
 class BatchItem:
@@ -152,6 +167,21 @@ def plan(curve, group, n, window_bits=0, endomorphism=0):
                                        ctypes.byref(w), ctypes.byref(b), ctypes.byref(ws), ctypes.byref(used))
     if rc:
         raise AmdMsmError(f"amdmsm_plan_ex: {rc}")
+    return {"c": c.value, "num_windows": w.value, "num_buckets": b.value, "workspace_bytes": ws.value,
+            "endomorphism": bool(used.value)}
+
+
+def plan_short(curve, group, n, scalar_bits, window_bits=0, endomorphism=0):
+    """``plan`` for scalars below ``2**scalar_bits`` (``amdmsm_plan_short``; 0 = full width): the windows cover
+    ``scalar_bits + 2`` bits, and the endomorphism split is kept only above its own bound."""
+    c, w, used = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    b = ctypes.c_uint32(0)
+    ws = ctypes.c_size_t(0)
+    rc = load_library().amdmsm_plan_short(curve, group, ctypes.c_size_t(n), window_bits, endomorphism, int(scalar_bits),
+                                          ctypes.byref(c), ctypes.byref(w), ctypes.byref(b), ctypes.byref(ws),
+                                          ctypes.byref(used))
+    if rc:
+        raise AmdMsmError(f"amdmsm_plan_short: {rc}")
     return {"c": c.value, "num_windows": w.value, "num_buckets": b.value, "workspace_bytes": ws.value,
             "endomorphism": bool(used.value)}
 
@@ -325,6 +355,36 @@ class Engine:
                                            _np_ptr(partials[i]), ctypes.byref(o))
             self._check(rc, "amdmsm_multi_exp")
         return self.sum_points(curve, group, partials, out_form=out_form)
+
+    def multi_exp_short(self, curve, group, bases, scalars, bits=0, base_form=multi_exp_base_form_normal,
+                        out_form=OUT_AFFINE, window_bits=0, scalars_plain=False):
+        """``multi_exp`` for scalars known to be short (``amdmsm_multi_exp_short``).  A one-dimensional array of dtype
+        uint8 / uint16 / uint32 / uint64 is passed as packed integers (``n * width`` bytes are uploaded); an
+        ``(n, fr_limbs)`` uint64 array is passed as Fr records.  ``bits``: 0 = the kind's full width, N > 0 = the
+        promise that every scalar is below ``2**N`` (a broken promise raises, nothing is returned), -1 = measure on the
+        device first."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint64)
+        scalars = np.ascontiguousarray(scalars)
+        s = sizes(curve, group)
+        n = bases.shape[0] if bases.ndim == 2 else 0
+        if scalars.ndim == 1 and scalars.dtype.name in _INT_KINDS:
+            kind = _INT_KINDS[scalars.dtype.name]
+            assert scalars.shape[0] == n, "one scalar per base"
+        else:
+            kind = SCALAR_FR
+            scalars = np.ascontiguousarray(scalars, dtype=np.uint64)
+            if n:
+                assert scalars.shape == (n, s["fr_bytes"] // 8), "scalars must be (n, fr_limbs) uint64 or a packed integer vector"
+        if n:
+            assert bases.shape[1] * 8 == s["g_bytes"], "bases must be (n, 3*coord_limbs) uint64"
+        out = np.zeros(s["g_bytes"] // 8, dtype=np.uint64)
+        o = self._opts(window_bits=window_bits, out_form=out_form, scalars_plain=scalars_plain)
+        d = scalar_desc(kind, bits)
+        rc = self.lib.amdmsm_multi_exp_short(self.h, curve, group, _np_ptr(bases) if n else None,
+                                             ctypes.c_size_t(s["g_bytes"]), base_form, _np_ptr(scalars) if n else None,
+                                             ctypes.byref(d), ctypes.c_size_t(n), _np_ptr(out), ctypes.byref(o))
+        self._check(rc, "amdmsm_multi_exp_short")
+        return out
 
     def multi_exp_batch(self, curve, group, bases_list, scalars_list, base_form=multi_exp_base_form_normal,
                         out_form=OUT_AFFINE, window_bits=0, scalars_plain=False):
@@ -610,6 +670,24 @@ class Engine:
         self._check(self.lib.amdmsm_msm_device(self.h, curve, group, _vp(d_bases_affine),
                                                _vp(d_scalars), ctypes.c_size_t(n),
                                                _vp(d_out_xyz), ctypes.byref(o)), "amdmsm_msm_device")
+
+    def msm_device_short(self, curve, group, d_bases_affine, d_scalars, kind, n, d_out_xyz, bits=0, out_form=OUT_LIBFF,
+                         window_bits=0, segment_len=0, scalars_plain=False, stream=None):
+        """``msm_device`` on scalars of ``kind`` (``SCALAR_*``) known to be short; asynchronous only with ``bits=0``."""
+        o = self._opts(window_bits, segment_len, out_form, scalars_plain, stream)
+        d = scalar_desc(kind, bits)
+        self._check(self.lib.amdmsm_msm_device_short(self.h, curve, group, _vp(d_bases_affine), _vp(d_scalars),
+                                                     ctypes.byref(d), ctypes.c_size_t(n), _vp(d_out_xyz),
+                                                     ctypes.byref(o)), "amdmsm_msm_device_short")
+
+    def scalar_bits(self, curve, group, d_scalars, kind, n, scalars_plain=False):
+        """Bit length of the longest of ``n`` device-resident scalars of ``kind`` (0: all zero); synchronises."""
+        d = scalar_desc(kind, 0)
+        bits = ctypes.c_int(0)
+        self._check(self.lib.amdmsm_scalar_bits_device(self.h, curve, group, _vp(d_scalars), ctypes.c_size_t(n),
+                                                       ctypes.byref(d), int(scalars_plain), ctypes.byref(bits)),
+                    "amdmsm_scalar_bits_device")
+        return bits.value
 
     def msm_device_batch(self, curve, group, d_bases_affine, d_scalars, n, d_out_xyz, out_form=OUT_LIBFF,
                          window_bits=0, scalars_plain=False, stream=None):
