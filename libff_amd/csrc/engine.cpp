@@ -327,8 +327,21 @@ int choose_c(const group_vtable *vt, size_t n, bool glv = false, double *cost_ou
 // glv: n counts the 2 x points digit columns of the endomorphism split
 // batch > 1: workspace for `batch` MSMs side by side, each of at most n entries -- every per-window array holds batch * W windows, MSM j
 // owning windows [j * W, (j + 1) * W), so that the tail kernels run once over all of them (amdmsm_msm_device_batch)
-int make_plan(const group_vtable *vt, size_t n, int c_req, int L_req, plan_t &p, int S_req = 0, int table_digits = 0,
-              int G_req = 0, bool glv = false, bool overlap = false, int batch = 1, size_t big_words_min = 0, int sbits = 0) {
+// What a caller asks of make_plan; a field left at its default is chosen by make_plan (c, L, S) or not in use.
+struct plan_req {
+    size_t entries = 0;          // n above: entries of one sorted list
+    int c = 0, L = 0, S = 0;     // window bits, buckets per reduction lane, entries per accumulation lane
+    int table_digits = 0;
+    int groups = 0;              // window groups (see ws_slot)
+    bool glv = false, overlap = false;
+    int batch = 1;
+    size_t big_words_min = 0;    // a batch of MSMs of different lengths: the largest big-bin scratch any of its lengths needs
+    int sbits = 0;               // > 0: every scalar is below 2^sbits (see num_windows)
+};
+int make_plan(const group_vtable *vt, const plan_req &r, plan_t &p) {
+    const size_t n = r.entries, big_words_min = r.big_words_min;
+    const int c_req = r.c, L_req = r.L, S_req = r.S, table_digits = r.table_digits, G_req = r.groups, batch = r.batch, sbits = r.sbits;
+    const bool glv = r.glv, overlap = r.overlap;
     if (c_req < 0 || c_req > 24 || c_req == 1) return AMDMSM_ERR_BAD_ARG;
     if (table_digits && (c_req < 2 || c_req > 22)) return AMDMSM_ERR_BAD_ARG;
     if (glv && (table_digits || c_req > 22)) return AMDMSM_ERR_BAD_ARG;
@@ -482,8 +495,7 @@ int ensure_ws(amdmsm_ctx *ctx, ws_slot &sl, size_t bytes) {
 }
 
 constexpr uint64_t TIMING_RING = 64;
-void record(amdmsm_ctx *ctx, ws_slot &sl, int idx, hipStream_t st) {
-    (void)sl;
+void record(amdmsm_ctx *ctx, ws_slot &, int idx, hipStream_t st) {
     if (ctx->timing) (void)hipEventRecord(ctx->ring[ctx->ticket % TIMING_RING][idx], st);
 }
 
@@ -549,6 +561,18 @@ int check_opts(amdmsm_ctx *ctx, const amdmsm_opts *opts) {
         if (rc_opts_) return rc_opts_;              \
     } while (0)
 
+// the stream a device entry launches on
+hipStream_t stream_of(const amdmsm_ctx *ctx, const amdmsm_opts *opts) {
+    return (opts && opts->stream) ? (hipStream_t)opts->stream : ctx->stream;
+}
+// the caller's options, or the defaults of an entry called without any
+amdmsm_opts opts_or_default(const amdmsm_opts *opts) {
+    amdmsm_opts o = AMDMSM_OPTS_INIT;
+    if (opts) o = *opts;
+    else o.out_form = AMDMSM_OUT_LIBFF;
+    return o;
+}
+
 // One MSM handles at most this many points (its sorted lists index points with 31 bits, and the
 // workspace grows with n: 42 GiB at 2^28 alt_bn128 points); longer inputs are cut into contiguous
 // ranges whose partial results are summed, exactly the reference's chunk loop (multiexp.tcc:655-687).
@@ -580,10 +604,45 @@ struct short_spec {
 int short_limit_bits(const group_vtable *vt, const short_spec &ss) {
     return ss.flag ? ss.bits : (ss.kind ? 8 * ss.kind : 32 * vt->fr_words);
 }
+// The tail of an MSM in front of its Horner chain, for the nw windows [w0, w0 + nw) of the workspace ws, on stream ts:
+// the fix-up of the buckets that span accumulation lanes (fix-up queue `queue`), then the bucket reduction -- row / column
+// sums and bit planes, or segment sums and the levels that fold them.  Returns the nw window sums Horner reads.
+uint32_t *enqueue_tail(const group_vtable *vt, const plan_t &p, char *ws, int w0, int nw, hipStream_t ts, int queue) {
+    const size_t zzw = (size_t)vt->bucket_words, xyzw = (size_t)vt->el_words * 3;   // words per XYZZ / Jacobian point
+    const size_t w = (size_t)w0;
+    uint32_t *buckets = (uint32_t *)(ws + p.off_buckets) + w * p.B * zzw;
+    vt->accumulate_fixup(ts, (uint32_t *)(ws + p.off_counts) + w * p.B, buckets, (uint32_t *)(ws + p.off_pfirst) + w * p.T * zzw,
+                         (uint32_t *)(ws + p.off_plast) + w * p.T * zzw, (uint32_t *)(ws + p.off_cont) + w * p.T,
+                         (uint32_t *)(ws + p.off_queue + (size_t)queue * p.queue_stride), nw, p.B, p.S, p.T);
+    if (p.rowcol) {
+        uint32_t *winsum = (uint32_t *)(ws + p.off_winsum) + w * xyzw;
+        vt->reduce_rowcol(ts, buckets, nw, p.B, p.c, p.q_row, p.q_col, (uint32_t *)(ws + p.off_rc) + w * p.rc_points * xyzw,
+                          (uint32_t *)(ws + p.off_planes) + w * p.c * xyzw, winsum);
+        return winsum;
+    }
+    const size_t M0 = p.B / p.L, cap1 = M0 / 2 + 1;   // segments of a window, points a window keeps in lvl1
+    uint32_t *src = (uint32_t *)(ws + p.off_lvl0) + w * M0 * xyzw, *dst = (uint32_t *)(ws + p.off_lvl1) + w * cap1 * xyzw;
+    vt->reduce_segments(ts, buckets, nw, p.B, p.L, src);
+    const uint32_t fold = (uint32_t)vt->reduce_fold;
+    uint32_t M = (uint32_t)M0;
+    M /= std::min<uint32_t>(M, fold);   // folded per wave inside reduce_segments
+    while (M > 1) {
+        if ((size_t)M * (64 / fold) <= 256) {   // the remaining levels in one launch
+            vt->sum_block(ts, src, nw, M, dst);
+            M = 1;
+        } else {
+            vt->sum_butterfly(ts, src, nw, M, dst);
+            M /= std::min<uint32_t>(M, fold);
+        }
+        std::swap(src, dst);
+    }
+    return src;
+}
+
 int msm_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_bases, const uint32_t *d_scalars,
                     size_t n, uint32_t *d_out, const amdmsm_opts *opts, int table_digits = 0,
                     const msm_hook *hook = nullptr, const uint32_t *d_endo_resident = nullptr, const short_spec *ss = nullptr) {
-    hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : ctx->stream;
+    hipStream_t st = stream_of(ctx, opts);
     hipStream_t const user_st = st;
     const int form = opts ? opts->out_form : AMDMSM_OUT_LIBFF;
     const int mont = (opts && opts->scalars_plain) ? 0 : 1;
@@ -609,8 +668,17 @@ int msm_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_b
     // but every kernel behind a cross-queue event wait starts ~50 us late, which outweighs the 0.7 ms tail it hides.
     static const bool overlap_env = getenv("AMDMSM_OVERLAP") && atoi(getenv("AMDMSM_OVERLAP")) != 0;
     const bool overlap = overlap_env && ctx->depth > 1 && ctx->bulk_stream && vt->accumulate_overlap_ok && !groups_env;
-    int rc = make_plan(vt, entries, opts ? opts->window_bits : 0, opts ? opts->segment_len : 0, p, acc_s_env, table_digits,
-                       groups_env, glv, overlap, 1, 0, ss ? ss->bits : 0);
+    plan_req req;
+    req.entries = entries;
+    req.c = opts ? opts->window_bits : 0;
+    req.L = opts ? opts->segment_len : 0;
+    req.S = acc_s_env;
+    req.table_digits = table_digits;
+    req.groups = groups_env;
+    req.glv = glv;
+    req.overlap = overlap;
+    req.sbits = ss ? ss->bits : 0;
+    int rc = make_plan(vt, req, p);
     if (rc) return fail(ctx, rc, "bad window_bits / segment_len");
     if (ss && p.c > 22) return fail(ctx, AMDMSM_ERR_BAD_ARG, "window_bits > 22 is not available for short scalars");
     const int slot_idx = (int)(ctx->next++ % (unsigned)ctx->depth);
@@ -629,8 +697,6 @@ int msm_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_b
     uint32_t *counts = (uint32_t *)(ws + p.off_counts);
     uint32_t *lists = (uint32_t *)(ws + p.off_lists);
     uint32_t *buckets = (uint32_t *)(ws + p.off_buckets);
-    uint32_t *lvl0 = (uint32_t *)(ws + p.off_lvl0);
-    uint32_t *lvl1 = (uint32_t *)(ws + p.off_lvl1);
 
     record(ctx, sl, 0, st);
     // phi(P) of every base (endomorphism split): independent of the sort, so it runs beside it on
@@ -681,7 +747,6 @@ int msm_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_b
     if (!overlap) HIP_TRY(ctx, hipStreamWaitEvent(st, sl.acc_done[0], 0));
     if (glv && !d_endo_resident && !endo_beside) vt->endo_points(st, d_bases, n, (uint32_t *)(ws + p.off_endo));
     const size_t zzw = (size_t)vt->bucket_words, xyzw = (size_t)vt->el_words * 3;   // words per XYZZ / Jacobian point
-    const size_t M0 = p.B / p.L, cap1 = M0 / 2 + 1;
     uint32_t *pfirst = (uint32_t *)(ws + p.off_pfirst), *plast = (uint32_t *)(ws + p.off_plast);
     uint32_t *cont = (uint32_t *)(ws + p.off_cont), *partial = (uint32_t *)(ws + p.off_partial);
     // groups of windows, highest first: [w0, w0 + wg)
@@ -708,31 +773,7 @@ int msm_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_b
             HIP_TRY(ctx, hipEventRecord(sl.acc_done[g], st));
             HIP_TRY(ctx, hipStreamWaitEvent(ts, sl.acc_done[g], 0));
         }
-        vt->accumulate_fixup(ts, counts + (size_t)w0 * p.B, buckets + (size_t)w0 * p.B * zzw,
-                             pfirst + (size_t)w0 * p.T * zzw, plast + (size_t)w0 * p.T * zzw, cont + (size_t)w0 * p.T,
-                             (uint32_t *)(ws + p.off_queue + g * p.queue_stride), wg, p.B, p.S, p.T);
-        uint32_t *src = lvl0 + (size_t)w0 * M0 * xyzw, *dst = lvl1 + (size_t)w0 * cap1 * xyzw;
-        if (p.rowcol) {
-            src = (uint32_t *)(ws + p.off_winsum) + (size_t)w0 * xyzw;
-            vt->reduce_rowcol(ts, buckets + (size_t)w0 * p.B * zzw, wg, p.B, p.c, p.q_row, p.q_col,
-                              (uint32_t *)(ws + p.off_rc) + (size_t)w0 * p.rc_points * xyzw,
-                              (uint32_t *)(ws + p.off_planes) + (size_t)w0 * p.c * xyzw, src);
-        } else {
-            vt->reduce_segments(ts, buckets + (size_t)w0 * p.B * zzw, wg, p.B, p.L, src);
-            const uint32_t fold = (uint32_t)vt->reduce_fold;
-            uint32_t M = (uint32_t)M0;
-            M /= std::min<uint32_t>(M, fold);   // folded per wave inside reduce_segments
-            while (M > 1) {
-                if ((size_t)M * (64 / fold) <= 256) {   // the remaining levels in one launch
-                    vt->sum_block(ts, src, wg, M, dst);
-                    M = 1;
-                } else {
-                    vt->sum_butterfly(ts, src, wg, M, dst);
-                    M /= std::min<uint32_t>(M, fold);
-                }
-                std::swap(src, dst);
-            }
-        }
+        const uint32_t *src = enqueue_tail(vt, p, ws, w0, wg, ts, g);
         // Horner over this group's windows, continuing from the groups above
         if (g > 0) HIP_TRY(ctx, hipStreamWaitEvent(ts, sl.tail_done[g - 1], 0));
         if (last) record(ctx, sl, 4, ts);
@@ -757,92 +798,7 @@ int msm_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_b
     return AMDMSM_OK;
 }
 
-// k MSMs of the same group and length in one call (amdmsm_msm_device_batch).  Sort and accumulation fill the device
-// and run MSM after MSM; the tail -- fix-up, bucket reduction, final Horner: dependent chains of a few waves, a quarter
-// of a 2^20-point MSM -- runs ONCE over the k * W windows of all of them, so its latency is paid once per batch
-// instead of once per MSM (2^20 points, k = 3: see profiles/r03_experiments.txt).  This is the overlap a prover's
-// back-to-back MSMs can really have on this device: in one stream, by making the latency-bound kernels wider.
-constexpr int MAX_BATCH = 8;
-int msm_device_batch_impl(amdmsm_ctx *ctx, const group_vtable *vt, int k, const uint32_t *const *d_bases,
-                          const uint32_t *const *d_scalars, size_t n, uint32_t *const *d_outs, const amdmsm_opts *opts) {
-    hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : ctx->stream;
-    const int form = opts ? opts->out_form : AMDMSM_OUT_LIBFF;
-    const int mont = (opts && opts->scalars_plain) ? 0 : 1;
-    const bool glv = use_endomorphism(vt, n, opts, 0);
-    const size_t entries = glv ? 2 * n : n;
-    plan_t p;
-    int rc = make_plan(vt, entries, opts ? opts->window_bits : 0, opts ? opts->segment_len : 0, p, 0, 0, 0, glv, false, k);
-    if (rc) return fail(ctx, rc, "bad window_bits / segment_len");
-    if (p.c > 22) return fail(ctx, AMDMSM_ERR_BAD_ARG, "window_bits > 22 is not available for a batch");
-    const int slot_idx = (int)(ctx->next++ % (unsigned)ctx->depth);
-    ws_slot &sl = ctx->slots[slot_idx];
-    ctx->last_slot = slot_idx;
-    if (sl.used) HIP_TRY(ctx, hipStreamWaitEvent(st, sl.done, 0));
-    rc = ensure_ws(ctx, sl, p.total);
-    if (rc) return rc;
-    char *ws = (char *)sl.ws;
-    const size_t zzw = (size_t)vt->bucket_words, xyzw = (size_t)vt->el_words * 3;
-    const size_t Wt = (size_t)p.W * (size_t)k;
-    uint32_t *counts = (uint32_t *)(ws + p.off_counts), *lists = (uint32_t *)(ws + p.off_lists);
-    uint32_t *buckets = (uint32_t *)(ws + p.off_buckets);
-    uint32_t *pfirst = (uint32_t *)(ws + p.off_pfirst), *plast = (uint32_t *)(ws + p.off_plast), *cont = (uint32_t *)(ws + p.off_cont);
-    record(ctx, sl, 0, st);
-    HIP_TRY(ctx, hipMemsetAsync(ws + p.off_coarse, 0, p.off_big - p.off_coarse, st));   // counters + cursors
-    for (int j = 0; j < k; ++j) HIP_TRY(ctx, hipMemsetAsync(ws + p.off_big + (size_t)j * p.big_stride, 0, 16, st));
-    HIP_TRY(ctx, hipMemsetAsync(buckets, 0, Wt * p.B * vt->bucket_words * 4, st));
-    HIP_TRY(ctx, hipMemsetAsync(ws + p.off_queue, 0, 8, st));
-    record(ctx, sl, 1, st);
-    for (int j = 0; j < k; ++j) {
-        const size_t w0 = (size_t)j * p.W;
-        uint32_t *lists_j = lists + w0 * p.list_stride, *counts_j = counts + w0 * p.B;
-        vt->sort(st, d_scalars[j], n, mont, p.c, p.W, (uint32_t *)(ws + p.off_coarse) + w0 * 1025,
-                 (uint32_t *)(ws + p.off_cursor) + w0 * 1024, (int32_t *)lists_j,
-                 (uint32_t *)(ws + p.off_tmp_payload) + w0 * p.list_stride, (uint32_t *)(ws + p.off_tmp_key) + w0 * p.list_stride,
-                 counts_j, lists_j, p.list_stride, (uint32_t *)(ws + p.off_big + (size_t)j * p.big_stride), glv ? 2 : 0, nullptr);
-        uint32_t *endo_j = glv ? (uint32_t *)(ws + p.off_endo + (size_t)j * p.endo_stride) : nullptr;
-        if (glv) vt->endo_points(st, d_bases[j], n, endo_j);
-        if (j == 0) record(ctx, sl, 2, st);
-        vt->accumulate(st, counts_j, lists_j, p.list_stride, d_bases[j], buckets + w0 * p.B * zzw, pfirst + w0 * p.T * zzw,
-                       plast + w0 * p.T * zzw, cont + w0 * p.T, p.W, p.B, p.S, p.T, endo_j, n, 0);
-    }
-    record(ctx, sl, 3, st);
-    vt->accumulate_fixup(st, counts, buckets, pfirst, plast, cont, (uint32_t *)(ws + p.off_queue), (int)Wt, p.B, p.S, p.T);
-    uint32_t *src;
-    if (p.rowcol) {
-        src = (uint32_t *)(ws + p.off_winsum);
-        vt->reduce_rowcol(st, buckets, (int)Wt, p.B, p.c, p.q_row, p.q_col, (uint32_t *)(ws + p.off_rc),
-                          (uint32_t *)(ws + p.off_planes), src);
-    } else {
-        const size_t M0 = p.B / p.L, cap1 = M0 / 2 + 1;
-        (void)cap1;
-        src = (uint32_t *)(ws + p.off_lvl0);
-        uint32_t *dst = (uint32_t *)(ws + p.off_lvl1);
-        vt->reduce_segments(st, buckets, (int)Wt, p.B, p.L, src);
-        const uint32_t fold = (uint32_t)vt->reduce_fold;
-        uint32_t M = (uint32_t)M0;
-        M /= std::min<uint32_t>(M, fold);
-        while (M > 1) {
-            if ((size_t)M * (64 / fold) <= 256) {
-                vt->sum_block(st, src, (int)Wt, M, dst);
-                M = 1;
-            } else {
-                vt->sum_butterfly(st, src, (int)Wt, M, dst);
-                M /= std::min<uint32_t>(M, fold);
-            }
-            std::swap(src, dst);
-        }
-    }
-    record(ctx, sl, 4, st);
-    vt->horner_batch(st, src, k, p.W, p.c, form, d_outs);
-    record(ctx, sl, 5, st);
-    if (ctx->timing) sl.last_ticket = (long long)ctx->ticket++;
-    sl.ev_valid = ctx->timing;
-    HIP_TRY(ctx, hipEventRecord(sl.done, st));
-    sl.used = true;
-    HIP_TRY(ctx, hipGetLastError());
-    return AMDMSM_OK;
-}
-
+constexpr int MAX_BATCH = 8;   // MSMs of one batch call
 int ensure_buf(amdmsm_ctx *ctx, grow_buf &b, size_t bytes);
 
 // One MSM of a ragged batch, every pointer an HBM address (amdmsm_batch_item after upload / as the device entry got it).
@@ -855,7 +811,11 @@ struct item_dev {
     uint32_t *out = nullptr;
 };
 
-// k MSMs of one group and of different lengths in one pass: msm_device_batch_impl with per-MSM n_j.
+// k MSMs of one group, each of its own length n_j, in one pass (the batch entries, equal-length and ragged).  Sort and
+// accumulation fill the device and run MSM after MSM; the tail -- fix-up, bucket reduction, final Horner: dependent chains
+// of a few waves, a quarter of a 2^20-point MSM -- runs ONCE over the k * W windows of all of them, so its latency is paid
+// once per batch instead of once per MSM (2^20 points, k = 3: see profiles/r03_experiments.txt).  This is the overlap a
+// prover's back-to-back MSMs can really have on this device: in one stream, by making the latency-bound kernels wider.
 // ONE plan for the batch -- window size, window count, endomorphism decision and lane length are those of the longest
 // MSM: sort and accumulation are linear in the entries, so the longest MSM carries most of their cost and is served
 // best by its own optimum, while the shared tail depends on (k W, B, c) only.  (Minimising the summed plan_cost would
@@ -863,15 +823,16 @@ struct item_dev {
 // the prover's shape -- both rules pick the same c.)  Every per-MSM stride of the workspace is sized for that longest
 // MSM; a shorter one uses the front of its share, an empty one launches nothing and has its window ends and lane
 // markers cleared so that the shared tail finds empty windows.
-// flags: k words, zeroed here; word j becomes nonzero when MSM j named an element at or past shared_n.
+// flags: k words, zeroed here; word j becomes nonzero when MSM j named an element at or past shared_n.  Null where every
+// MSM brings its own scalars (the equal-length entries): nothing is cleared and no MSM may select from d_shared.
 int msm_device_batch_items_impl(amdmsm_ctx *ctx, const group_vtable *vt, int k, const item_dev *it, const uint32_t *d_shared,
                                 size_t shared_n, uint32_t *flags, const amdmsm_opts *opts) {
-    hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : ctx->stream;
+    hipStream_t st = stream_of(ctx, opts);
     const int form = opts ? opts->out_form : AMDMSM_OUT_LIBFF;
     const int mont = (opts && opts->scalars_plain) ? 0 : 1;
     size_t n_max = 0;
     for (int j = 0; j < k; ++j) n_max = std::max(n_max, it[j].n);
-    HIP_TRY(ctx, hipMemsetAsync(flags, 0, (size_t)k * 4, st));
+    if (flags) HIP_TRY(ctx, hipMemsetAsync(flags, 0, (size_t)k * 4, st));
     if (n_max == 0) {
         for (int j = 0; j < k; ++j) vt->sum_points(st, it[j].out, 0, form, it[j].out);
         HIP_TRY(ctx, hipGetLastError());
@@ -879,23 +840,24 @@ int msm_device_batch_items_impl(amdmsm_ctx *ctx, const group_vtable *vt, int k, 
     }
     const bool glv = use_endomorphism(vt, n_max, opts, 0);
     const size_t entries = glv ? 2 * n_max : n_max;
-    const int c_req = opts ? opts->window_bits : 0;
-    if (c_req > 22) return fail(ctx, AMDMSM_ERR_BAD_ARG, "window_bits > 22 is not available for a batch");
+    plan_req req;
+    req.entries = entries;
+    req.c = opts ? opts->window_bits : 0;
+    req.L = opts ? opts->segment_len : 0;
+    req.glv = glv;
+    req.batch = k;
     plan_t p;
-    int rc;
-    {
-        // the sort geometry (coarse bits, chunk size, big-bin scratch) follows each MSM's own length: the scratch
-        // of every MSM is sized for the largest need of any length in the batch
-        plan_t p0;
-        rc = make_plan(vt, entries, c_req, opts ? opts->segment_len : 0, p0, 0, 0, 0, glv, false, k);
-        if (rc) return fail(ctx, rc, "bad window_bits / segment_len");
-        size_t big_words = 0;
-        for (int j = 0; j < k; ++j) {
-            if (it[j].n) big_words = std::max(big_words, sort_geometry(glv ? 2 * it[j].n : it[j].n, p0.c, p0.W).big_words);
-        }
-        rc = make_plan(vt, entries, p0.c, opts ? opts->segment_len : 0, p, 0, 0, 0, glv, false, k, big_words);
-        if (rc) return fail(ctx, rc, "bad window_bits / segment_len");
+    int rc = make_plan(vt, req, p);
+    if (rc) return fail(ctx, rc, "bad window_bits / segment_len");
+    if (p.c > 22) return fail(ctx, AMDMSM_ERR_BAD_ARG, "window_bits > 22 is not available for a batch");
+    // the sort geometry (coarse bits, chunk size, big-bin scratch) follows each MSM's own length: the scratch
+    // of every MSM is sized for the largest need of any length in the batch, planned again with the c just chosen
+    req.c = p.c;
+    for (int j = 0; j < k; ++j) {
+        if (it[j].n) req.big_words_min = std::max(req.big_words_min, sort_geometry(glv ? 2 * it[j].n : it[j].n, p.c, p.W).big_words);
     }
+    rc = make_plan(vt, req, p);
+    if (rc) return fail(ctx, rc, "bad window_bits / segment_len");
     const int slot_idx = (int)(ctx->next++ % (unsigned)ctx->depth);
     ws_slot &sl = ctx->slots[slot_idx];
     ctx->last_slot = slot_idx;
@@ -942,30 +904,7 @@ int msm_device_batch_items_impl(amdmsm_ctx *ctx, const group_vtable *vt, int k, 
                        plast + w0 * p.T * zzw, cont + w0 * p.T, p.W, p.B, p.S, p.T, endo_j, n, 0);
     }
     record(ctx, sl, 3, st);
-    vt->accumulate_fixup(st, counts, buckets, pfirst, plast, cont, (uint32_t *)(ws + p.off_queue), (int)Wt, p.B, p.S, p.T);
-    uint32_t *src;
-    if (p.rowcol) {
-        src = (uint32_t *)(ws + p.off_winsum);
-        vt->reduce_rowcol(st, buckets, (int)Wt, p.B, p.c, p.q_row, p.q_col, (uint32_t *)(ws + p.off_rc),
-                          (uint32_t *)(ws + p.off_planes), src);
-    } else {
-        src = (uint32_t *)(ws + p.off_lvl0);
-        uint32_t *dst = (uint32_t *)(ws + p.off_lvl1);
-        vt->reduce_segments(st, buckets, (int)Wt, p.B, p.L, src);
-        const uint32_t fold = (uint32_t)vt->reduce_fold;
-        uint32_t M = p.B / p.L;
-        M /= std::min<uint32_t>(M, fold);
-        while (M > 1) {
-            if ((size_t)M * (64 / fold) <= 256) {
-                vt->sum_block(st, src, (int)Wt, M, dst);
-                M = 1;
-            } else {
-                vt->sum_butterfly(st, src, (int)Wt, M, dst);
-                M /= std::min<uint32_t>(M, fold);
-            }
-            std::swap(src, dst);
-        }
-    }
+    const uint32_t *src = enqueue_tail(vt, p, ws, 0, (int)Wt, st, 0);
     record(ctx, sl, 4, st);
     uint32_t *outs[MAX_BATCH];
     for (int j = 0; j < k; ++j) outs[j] = it[j].out;
@@ -998,12 +937,10 @@ int msm_device_ranges(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d
     const size_t fr_bytes = ss ? ss->elem_bytes(vt) : (size_t)vt->fr_words * 4;   // one bit length for all ranges
     int rc = ensure_partials(ctx);
     if (rc) return rc;
-    amdmsm_opts o = AMDMSM_OPTS_INIT;
-    if (opts) o = *opts;
-    else o.out_form = AMDMSM_OUT_LIBFF;
+    amdmsm_opts o = opts_or_default(opts);
     const int form = o.out_form;
     o.out_form = AMDMSM_OUT_JACOBIAN;
-    hipStream_t st = o.stream ? (hipStream_t)o.stream : ctx->stream;
+    hipStream_t st = stream_of(ctx, &o);
     for (size_t k = 0; k < parts; ++k) {
         const size_t lo = k * one, cnt = (k == parts - 1) ? n - lo : one;
         rc = msm_device_impl(ctx, vt, (const uint32_t *)((const char *)d_bases + lo * aff_bytes),
@@ -1019,7 +956,7 @@ int msm_device_ranges(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d
 
 // A ragged batch on device-resident inputs: one pass where its limits hold (k <= 8, sum n_j < 2^30, every n_j within one
 // range), otherwise the MSMs one after the other through the single-MSM path, the scalars of an MSM that selects from
-// the shared vector gathered on the device first (same selection, same guard).  flags: see msm_device_batch_items_impl.
+// the shared vector gathered on the device first (same selection, same guard).  flags (nullable): see msm_device_batch_items_impl.
 int run_batch_items(amdmsm_ctx *ctx, const group_vtable *vt, int k, const item_dev *it, const uint32_t *d_shared, size_t shared_n,
                     uint32_t *flags, const amdmsm_opts *opts) {
     size_t sum = 0, n_max = 0;
@@ -1030,9 +967,9 @@ int run_batch_items(amdmsm_ctx *ctx, const group_vtable *vt, int k, const item_d
     if (n_max <= max_range_points() && sum < ((size_t)1 << 30))
         return msm_device_batch_items_impl(ctx, vt, k, it, d_shared, shared_n, flags, opts);
     if (opts && opts->window_bits > 22) return fail(ctx, AMDMSM_ERR_BAD_ARG, "window_bits > 22 is not available for a batch");
-    hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : ctx->stream;
+    hipStream_t st = stream_of(ctx, opts);
     const size_t fr_bytes = (size_t)vt->fr_words * 4;
-    HIP_TRY(ctx, hipMemsetAsync(flags, 0, (size_t)k * 4, st));
+    if (flags) HIP_TRY(ctx, hipMemsetAsync(flags, 0, (size_t)k * 4, st));
     for (int j = 0; j < k; ++j) {
         const uint32_t *sc = it[j].scalars;
         if (!sc && it[j].n) {
@@ -1240,8 +1177,12 @@ int amdmsm_plan_ex(int curve, int group, size_t n, int window_bits, int endomorp
     o.window_bits = window_bits;
     o.endomorphism = endomorphism;
     const bool glv = use_endomorphism(vt, n, &o, 0);
+    plan_req req;
+    req.entries = glv ? 2 * n : n;
+    req.c = window_bits;
+    req.glv = glv;
     plan_t p;
-    const int rc = make_plan(vt, glv ? 2 * n : n, window_bits, 0, p, 0, 0, 0, glv);
+    const int rc = make_plan(vt, req, p);
     if (rc) return rc;
     if (c) *c = p.c;
     if (num_windows) *num_windows = p.W;
@@ -1258,8 +1199,12 @@ int amdmsm_plan_sort(int curve, int group, size_t n, int window_bits, int endomo
     o.window_bits = window_bits;
     o.endomorphism = endomorphism;
     const bool glv = use_endomorphism(vt, n, &o, 0);
+    plan_req req;
+    req.entries = glv ? 2 * n : n;
+    req.c = window_bits;
+    req.glv = glv;
     plan_t p;
-    const int rc = make_plan(vt, glv ? 2 * n : n, window_bits, 0, p, 0, 0, 0, glv);
+    const int rc = make_plan(vt, req, p);
     if (rc) return rc;
     if (p.c > 22) return AMDMSM_ERR_UNSUPPORTED;
     const sort_geom g = sort_geometry(glv ? 2 * n : n, p.c, p.W);
@@ -1401,8 +1346,14 @@ int amdmsm_msm_device_batch(amdmsm_ctx *ctx, int curve, int group, int k, const 
         }
         return AMDMSM_OK;
     }
-    return msm_device_batch_impl(ctx, vt, k, (const uint32_t *const *)d_bases_affine, (const uint32_t *const *)d_scalars, n,
-                                 (uint32_t *const *)d_out_xyz, opts);
+    item_dev it[MAX_BATCH];
+    for (int j = 0; j < k; ++j) {
+        it[j].bases = (const uint32_t *)d_bases_affine[j];
+        it[j].n = n;
+        it[j].scalars = (const uint32_t *)d_scalars[j];
+        it[j].out = (uint32_t *)d_out_xyz[j];
+    }
+    return msm_device_batch_items_impl(ctx, vt, k, it, nullptr, 0, nullptr, opts);
 }
 
 int amdmsm_msm_device_batch_items(amdmsm_ctx *ctx, int curve, int group, int k, const amdmsm_batch_item *items,
@@ -1427,7 +1378,7 @@ int amdmsm_msm_device_batch_items(amdmsm_ctx *ctx, int curve, int group, int k, 
     rc = run_batch_items(ctx, vt, k, it, (const uint32_t *)d_shared_scalars, shared_n, (uint32_t *)ctx->sel_flag.p, opts);
     if (rc || !indexed) return rc;
     // index lists live in HBM: whether one of them named a missing element is known once the digit passes have run
-    hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : ctx->stream;
+    hipStream_t st = stream_of(ctx, opts);
     uint32_t h_flags[MAX_BATCH] = {};
     HIP_TRY(ctx, hipMemcpyAsync(h_flags, ctx->sel_flag.p, (size_t)k * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -1473,9 +1424,7 @@ int amdmsm_msm_precomputed_device(amdmsm_ctx *ctx, int curve, int group, const v
     // more digits than the scalar has windows (+1 for the final carry) would only index multiples
     // that are never selected; such a table layout is a caller error
     if (num_digits > ((size_t)vt->fr_bits + c - 1) / c + 1) return fail(ctx, AMDMSM_ERR_BAD_ARG, "num_digits exceeds ceil(bits/c) + 1");
-    amdmsm_opts o = AMDMSM_OPTS_INIT;
-    if (opts) o = *opts;
-    else o.out_form = AMDMSM_OUT_LIBFF;
+    amdmsm_opts o = opts_or_default(opts);
     o.window_bits = (int)c;
     // one sorted list holds n * num_digits entries and is indexed with 31 bits: larger inputs are
     // split into ranges of points whose partial results are summed (multiexp.tcc:663-687 shape)
@@ -1496,7 +1445,7 @@ int amdmsm_msm_precomputed_device(amdmsm_ctx *ctx, int curve, int group, const v
     }
     const int form = o.out_form;
     o.out_form = AMDMSM_OUT_JACOBIAN;
-    hipStream_t st = o.stream ? (hipStream_t)o.stream : ctx->stream;
+    hipStream_t st = stream_of(ctx, &o);
     for (size_t k = 0; k < parts; ++k) {
         const size_t lo = k * max_pts, cnt = std::min(max_pts, n - lo);
         const int rc = msm_device_impl(ctx, vt, (const uint32_t *)((const char *)d_table + lo * num_digits * aff_bytes),
@@ -1803,9 +1752,7 @@ int host_msm_enqueue(amdmsm_ctx *ctx, const group_vtable *vt, const void *bases_
         if (rc) return rc;
         if (clear_stats) HIP_TRY(ctx, hipMemsetAsync(ctx->hb_stats.p, 0, 16, st));
     }
-    amdmsm_opts o = AMDMSM_OPTS_INIT;
-    if (opts) o = *opts;
-    else o.out_form = AMDMSM_OUT_LIBFF;
+    amdmsm_opts o = opts_or_default(opts);
     o.stream = st;
     void *d_aff = nullptr;
     const uint32_t *d_endo = nullptr;
@@ -1883,9 +1830,7 @@ int host_msm_ranges(amdmsm_ctx *ctx, const group_vtable *vt, const void *bases_x
     }
     int rc = ensure_partials(ctx);
     if (rc) return rc;
-    amdmsm_opts o = AMDMSM_OPTS_INIT;
-    if (opts) o = *opts;
-    else o.out_form = AMDMSM_OUT_LIBFF;
+    amdmsm_opts o = opts_or_default(opts);
     const int form = o.out_form;
     o.out_form = AMDMSM_OUT_JACOBIAN;
     hipStream_t st = ctx->stream;
@@ -2036,8 +1981,12 @@ int amdmsm_plan_short(int curve, int group, size_t n, int window_bits, int endom
     if (scalar_bits == 0 || route_short(vt, n, &o, AMDMSM_SCALAR_FR, scalar_bits) == ROUTE_ORDINARY)
         return amdmsm_plan_ex(curve, group, n, window_bits, endomorphism, c, num_windows, num_buckets, workspace_bytes,
                               endomorphism_used);
+    plan_req req;
+    req.entries = n;
+    req.c = window_bits;
+    req.sbits = scalar_bits;
     plan_t p;
-    const int rc = make_plan(vt, n, window_bits, 0, p, 0, 0, 0, false, false, 1, 0, scalar_bits);
+    const int rc = make_plan(vt, req, p);
     if (rc) return rc;
     if (c) *c = p.c;
     if (num_windows) *num_windows = p.W;
@@ -2063,7 +2012,7 @@ int amdmsm_msm_device_short(amdmsm_ctx *ctx, int curve, int group, const void *d
     int rc = check_short_args(ctx, vt, desc, d_scalars, n, opts);
     if (rc) return rc;
     if (!d_out_xyz || (n && (!d_bases_affine || !d_scalars))) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null pointer");
-    hipStream_t st = (opts && opts->stream) ? (hipStream_t)opts->stream : ctx->stream;
+    hipStream_t st = stream_of(ctx, opts);
     const int kind = desc->kind, full = kind_width_bits(vt, kind);
     const int mont = (opts && opts->scalars_plain) ? 0 : 1;
     const uint32_t *bases = (const uint32_t *)d_bases_affine;
@@ -2124,9 +2073,7 @@ int amdmsm_multi_exp_short(amdmsm_ctx *ctx, int curve, int group, const void *ba
     if (n == 0 || (kind == AMDMSM_SCALAR_FR && (desc->bits == 0 || desc->bits >= full)))
         return host_multi_exp(ctx, vt, bases_xyz, stride, base_form, scalars, n, out_xyz, opts, nullptr);
     hipStream_t st = ctx->stream;
-    amdmsm_opts o = AMDMSM_OPTS_INIT;
-    if (opts) o = *opts;
-    else o.out_form = AMDMSM_OUT_LIBFF;
+    amdmsm_opts o = opts_or_default(opts);
     const int mont = o.scalars_plain ? 0 : 1;
     short_spec ss;
     ss.kind = kind;
@@ -2189,96 +2136,27 @@ int amdmsm_multi_exp_filter_one_zero(amdmsm_ctx *ctx, int curve, int group, cons
     return host_multi_exp(ctx, vt, bases_xyz, base_stride_bytes, base_form, scalars, n, out_xyz, opts, stats);
 }
 
-// k multi_exp calls of one group and length as ONE batch (amdmsm_msm_device_batch over host vectors): scalars over PCIe
-// per MSM, bases from the resident copies where registered (amdmsm_register_bases) and uploaded + imported otherwise.
-int amdmsm_multi_exp_batch(amdmsm_ctx *ctx, int curve, int group, int k, const void *const *bases_xyz,
-                           size_t base_stride_bytes, int base_form, const void *const *scalars, size_t n,
-                           void *const *out_xyz, const amdmsm_opts *opts) {
-    GET_VT(ctx, curve, group);
-    CHECK_OPTS(ctx, opts);
-    if (k < 1 || k > MAX_BATCH || !bases_xyz || !scalars || !out_xyz) return fail(ctx, AMDMSM_ERR_BAD_ARG, "batch of 1 .. 8 MSMs");
-    size_t stride = base_stride_bytes;
-    for (int j = 0; j < k; ++j) {
-        const int rcj = check_host_args(ctx, vt, bases_xyz[j], stride, scalars[j], n, out_xyz[j]);
-        if (rcj) return rcj;
-    }
-    if (k == 1 || n == 0 || n > max_range_points() || (size_t)k * n >= ((size_t)1 << 30)) {
-        for (int j = 0; j < k; ++j) {
-            const int rcj = host_multi_exp(ctx, vt, bases_xyz[j], stride, base_form, scalars[j], n, out_xyz[j], opts, nullptr);
-            if (rcj) return rcj;
-        }
-        return AMDMSM_OK;
-    }
-    const size_t xyz_bytes = (size_t)vt->el_words * 12, aff_bytes = (size_t)vt->el_words * 8, fr_bytes = (size_t)vt->fr_words * 4;
-    hipStream_t st = ctx->stream;
-    int rc = ensure_buf(ctx, ctx->hb_out, (size_t)k * xyz_bytes);
-    if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->hb_sc, (size_t)k * n * fr_bytes);
-    if (rc) return rc;
-    const uint32_t *d_b[MAX_BATCH], *d_s[MAX_BATCH];
-    uint32_t *d_o[MAX_BATCH];
-    int missing = 0;
-    // Every resident vector this batch resolves is pinned until the call returns: registering vector j under
-    // AMDMSM_BASE_CACHE_MB evicts least-recently-used automatic entries (hipFree), which must never be the copy behind
-    // d_b[j'] of an earlier j'.  A vector that does not fit beside the pinned ones is uploaded like an unregistered one.
-    struct unpin_all {
-        amdmsm_ctx *c;
-        ~unpin_all() {
-            for (auto &e : c->bases) e.pinned = false;
-        }
-    } unpin{ctx};
-    for (int j = 0; j < k; ++j) {
-        base_entry *be = nullptr;
-        d_b[j] = (const uint32_t *)find_resident_bases(ctx, vt, bases_xyz[j], stride, base_form, n, &be);
-        if (!d_b[j] && auto_cache_bases(ctx, vt, bases_xyz[j], stride, base_form, n))
-            d_b[j] = (const uint32_t *)find_resident_bases(ctx, vt, bases_xyz[j], stride, base_form, n, &be);
-        if (d_b[j] && be) be->pinned = true;
-        if (!d_b[j]) ++missing;
-    }
-    if (missing) {
-        rc = ensure_buf(ctx, ctx->hb_src, n * stride);
-        if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->hb_aff, (size_t)missing * n * aff_bytes);
-        if (rc) return rc;
-    }
-    int slot = 0;
-    for (int j = 0; j < k; ++j) {
-        d_s[j] = (const uint32_t *)((char *)ctx->hb_sc.p + (size_t)j * n * fr_bytes);
-        d_o[j] = (uint32_t *)((char *)ctx->hb_out.p + (size_t)j * xyz_bytes);
-        HIP_TRY(ctx, hipMemcpyAsync((void *)d_s[j], scalars[j], n * fr_bytes, hipMemcpyHostToDevice, st));
-        if (!d_b[j]) {
-            uint32_t *aff = (uint32_t *)((char *)ctx->hb_aff.p + (size_t)slot++ * n * aff_bytes);
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_src.p, bases_xyz[j], n * stride, hipMemcpyHostToDevice, st));
-            vt->import_bases(st, (const uint32_t *)ctx->hb_src.p, stride / 4, base_form == AMDMSM_FORM_SPECIAL, n, aff);
-            HIP_TRY(ctx, hipGetLastError());
-            d_b[j] = aff;
-        }
-    }
-    amdmsm_opts o = AMDMSM_OPTS_INIT;
-    if (opts) o = *opts;
-    else o.out_form = AMDMSM_OUT_LIBFF;
-    o.stream = st;
-    rc = msm_device_batch_impl(ctx, vt, k, d_b, d_s, n, d_o, &o);
-    if (rc) {
-        (void)hipDeviceSynchronize();
-        return rc;
-    }
-    for (int j = 0; j < k; ++j) HIP_TRY(ctx, hipMemcpyAsync(out_xyz[j], d_o[j], xyz_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return AMDMSM_OK;
-}
+}   // extern "C"
 
-// k multi_exp calls of one group, each of its own length, as one batch (amdmsm_msm_device_batch_items over host vectors).
-// The shared scalar vector crosses PCIe once, own vectors and index lists per item; bases as in amdmsm_multi_exp_batch.
-int amdmsm_multi_exp_batch_items(amdmsm_ctx *ctx, int curve, int group, int k, const amdmsm_batch_item *items,
-                                 size_t base_stride_bytes, int base_form, const void *shared_scalars, size_t shared_n,
-                                 const amdmsm_opts *opts) {
-    GET_VT(ctx, curve, group);
-    CHECK_OPTS(ctx, opts);
-    int rc = check_batch_items(ctx, k, items, shared_scalars, shared_n, true);
-    if (rc) return rc;
+namespace {
+
+// Every resident base vector a batch resolves is pinned until the call returns: registering vector j under
+// AMDMSM_BASE_CACHE_MB evicts least-recently-used automatic entries (hipFree), which must never be the copy an earlier
+// MSM of the same batch is about to read.  A vector that does not fit beside the pinned ones is uploaded like an
+// unregistered one.
+struct unpin_all {
+    amdmsm_ctx *c;
+    ~unpin_all() {
+        for (auto &e : c->bases) e.pinned = false;
+    }
+};
+
+// A batch over host vectors, its arguments checked (stride: bytes between base records): scalars over PCIe -- the shared
+// vector once, own vectors and index lists per item --, bases from the resident copies where registered
+// (amdmsm_register_bases) and uploaded + imported otherwise.
+int host_batch_items(amdmsm_ctx *ctx, const group_vtable *vt, int k, const amdmsm_batch_item *items, size_t stride, int base_form,
+                     const void *shared_scalars, size_t shared_n, const amdmsm_opts *opts) {
     const size_t xyz_bytes = (size_t)vt->el_words * 12, aff_bytes = (size_t)vt->el_words * 8, fr_bytes = (size_t)vt->fr_words * 4;
-    size_t stride = base_stride_bytes ? base_stride_bytes : xyz_bytes;
-    if (stride % rec_align(vt) || stride < xyz_bytes) return fail(ctx, AMDMSM_ERR_BAD_ARG, "base stride");
-    if (opts && opts->window_bits > 22) return fail(ctx, AMDMSM_ERR_BAD_ARG, "window_bits > 22 is not available for a batch");
     // staging: [shared | own vectors] in hb_sc, the index lists in hb_idx, imported bases of unregistered vectors in hb_aff
     bool any_shared = false;
     size_t sc_bytes = 0, idx_bytes = 0, max_src = 0;
@@ -2290,20 +2168,16 @@ int amdmsm_multi_exp_batch_items(amdmsm_ctx *ctx, int curve, int group, int k, c
     }
     const size_t shared_bytes = any_shared ? align_up(shared_n * fr_bytes, 256) : 0;
     hipStream_t st = ctx->stream;
-    rc = ensure_buf(ctx, ctx->hb_out, (size_t)MAX_BATCH * xyz_bytes);
+    int rc = ensure_buf(ctx, ctx->hb_out, (size_t)MAX_BATCH * xyz_bytes);
     if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->hb_sc, shared_bytes + sc_bytes);
     if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->hb_idx, idx_bytes);
     if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->sel_flag, MAX_BATCH * 4);
     if (rc) return rc;
+    // out-of-range flags exist only for a batch that selects from the shared vector
+    uint32_t *flags = any_shared ? (uint32_t *)ctx->sel_flag.p : nullptr;
     item_dev it[MAX_BATCH];
     size_t aff_need = 0;
-    // resident vectors are pinned until the call returns (see amdmsm_multi_exp_batch)
-    struct unpin_all {
-        amdmsm_ctx *c;
-        ~unpin_all() {
-            for (auto &e : c->bases) e.pinned = false;
-        }
-    } unpin{ctx};
+    unpin_all unpin{ctx};
     for (int j = 0; j < k; ++j) {
         const amdmsm_batch_item &m = items[j];
         it[j].n = m.n;
@@ -2349,11 +2223,9 @@ int amdmsm_multi_exp_batch_items(amdmsm_ctx *ctx, int curve, int group, int k, c
             it[j].bases = aff;
         }
     }
-    amdmsm_opts o = AMDMSM_OPTS_INIT;
-    if (opts) o = *opts;
-    else o.out_form = AMDMSM_OUT_LIBFF;
+    amdmsm_opts o = opts_or_default(opts);
     o.stream = st;
-    rc = run_batch_items(ctx, vt, k, it, (const uint32_t *)ctx->hb_sc.p, shared_n, (uint32_t *)ctx->sel_flag.p, &o);
+    rc = run_batch_items(ctx, vt, k, it, (const uint32_t *)ctx->hb_sc.p, shared_n, flags, &o);
     if (rc) {
         (void)hipDeviceSynchronize();
         return rc;
@@ -2362,12 +2234,62 @@ int amdmsm_multi_exp_batch_items(amdmsm_ctx *ctx, int curve, int group, int k, c
     std::vector<char> h_out((size_t)k * xyz_bytes);
     uint32_t h_flags[MAX_BATCH] = {};
     HIP_TRY(ctx, hipMemcpyAsync(h_out.data(), ctx->hb_out.p, (size_t)k * xyz_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(h_flags, ctx->sel_flag.p, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+    if (flags) HIP_TRY(ctx, hipMemcpyAsync(h_flags, flags, (size_t)k * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     rc = check_batch_flags(ctx, k, h_flags);
     if (rc) return rc;
     for (int j = 0; j < k; ++j) memcpy(items[j].out_xyz, h_out.data() + (size_t)j * xyz_bytes, xyz_bytes);
     return AMDMSM_OK;
+}
+
+}   // namespace
+
+extern "C" {
+
+// k multi_exp calls of one group and length as ONE batch (amdmsm_msm_device_batch over host vectors): a batch of items
+// that all bring their own n scalars.
+int amdmsm_multi_exp_batch(amdmsm_ctx *ctx, int curve, int group, int k, const void *const *bases_xyz,
+                           size_t base_stride_bytes, int base_form, const void *const *scalars, size_t n,
+                           void *const *out_xyz, const amdmsm_opts *opts) {
+    GET_VT(ctx, curve, group);
+    CHECK_OPTS(ctx, opts);
+    if (k < 1 || k > MAX_BATCH || !bases_xyz || !scalars || !out_xyz) return fail(ctx, AMDMSM_ERR_BAD_ARG, "batch of 1 .. 8 MSMs");
+    size_t stride = base_stride_bytes;
+    for (int j = 0; j < k; ++j) {
+        const int rcj = check_host_args(ctx, vt, bases_xyz[j], stride, scalars[j], n, out_xyz[j]);
+        if (rcj) return rcj;
+    }
+    if (k == 1 || n == 0 || n > max_range_points() || (size_t)k * n >= ((size_t)1 << 30)) {
+        for (int j = 0; j < k; ++j) {
+            const int rcj = host_multi_exp(ctx, vt, bases_xyz[j], stride, base_form, scalars[j], n, out_xyz[j], opts, nullptr);
+            if (rcj) return rcj;
+        }
+        return AMDMSM_OK;
+    }
+    amdmsm_batch_item items[MAX_BATCH];
+    for (int j = 0; j < k; ++j) {
+        items[j] = AMDMSM_BATCH_ITEM_INIT;
+        items[j].bases = bases_xyz[j];
+        items[j].n = n;
+        items[j].scalars = scalars[j];
+        items[j].out_xyz = out_xyz[j];
+    }
+    return host_batch_items(ctx, vt, k, items, stride, base_form, nullptr, 0, opts);
+}
+
+// k multi_exp calls of one group, each of its own length, as one batch (amdmsm_msm_device_batch_items over host vectors).
+int amdmsm_multi_exp_batch_items(amdmsm_ctx *ctx, int curve, int group, int k, const amdmsm_batch_item *items,
+                                 size_t base_stride_bytes, int base_form, const void *shared_scalars, size_t shared_n,
+                                 const amdmsm_opts *opts) {
+    GET_VT(ctx, curve, group);
+    CHECK_OPTS(ctx, opts);
+    const int rc = check_batch_items(ctx, k, items, shared_scalars, shared_n, true);
+    if (rc) return rc;
+    const size_t xyz_bytes = (size_t)vt->el_words * 12;
+    const size_t stride = base_stride_bytes ? base_stride_bytes : xyz_bytes;
+    if (stride % rec_align(vt) || stride < xyz_bytes) return fail(ctx, AMDMSM_ERR_BAD_ARG, "base stride");
+    if (opts && opts->window_bits > 22) return fail(ctx, AMDMSM_ERR_BAD_ARG, "window_bits > 22 is not available for a batch");
+    return host_batch_items(ctx, vt, k, items, stride, base_form, shared_scalars, shared_n, opts);
 }
 
 int amdmsm_register_bases(amdmsm_ctx *ctx, int curve, int group, const void *bases_xyz, size_t base_stride_bytes,
@@ -2443,9 +2365,7 @@ int amdmsm_multi_exp_filter_one_zero_multi(amdmsm_ctx *const *ctxs, int ndev, in
     if (rc) return rc;
     const size_t xyz_bytes = (size_t)vt->el_words * 12, fr_bytes = (size_t)vt->fr_words * 4;
     const size_t one = n / (size_t)ndev;
-    amdmsm_opts o = AMDMSM_OPTS_INIT;
-    if (opts) o = *opts;
-    else o.out_form = AMDMSM_OUT_LIBFF;
+    amdmsm_opts o = opts_or_default(opts);
     const int final_form = o.out_form;
     o.out_form = AMDMSM_OUT_JACOBIAN;
     std::vector<int> rcs((size_t)ndev, AMDMSM_OK);
@@ -2535,9 +2455,7 @@ int amdmsm_msm_device_multi(amdmsm_ctx *const *ctxs, int ndev, int curve, int gr
     std::vector<std::unique_lock<std::recursive_mutex>> locks;
     for (int k = 0; k < ndev; ++k) locks.emplace_back(ctxs[k]->mu);
     const size_t xyz_bytes = (size_t)vt->el_words * 12;
-    amdmsm_opts o = AMDMSM_OPTS_INIT;
-    if (opts) o = *opts;
-    else o.out_form = AMDMSM_OUT_LIBFF;
+    amdmsm_opts o = opts_or_default(opts);
     const int final_form = o.out_form;
     hipStream_t user_stream = (hipStream_t)o.stream;
     o.out_form = AMDMSM_OUT_JACOBIAN;

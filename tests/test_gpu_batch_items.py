@@ -398,6 +398,93 @@ def test_registered_bases_and_equal_length_batch_around_a_ragged_call(engine, po
         assert (before[j] == after[j]).all() and tuple(after[j]) == be.msm(eq_b[j], eq_s[j])
 
 
+@pytest.mark.parametrize("window_bits", [7, 12], ids=["segment-kernels", "row-column-sums"])
+@pytest.mark.parametrize("name,curve,group", [GROUPS[0], GROUPS[3], MNT_GROUPS[0]])
+def test_equal_length_and_ragged_entries_agree(engine, port, name, curve, group, window_bits):
+    """k = 3 MSMs of 300 points through amdmsm_msm_device_batch and, every item with its own scalars, through
+    amdmsm_msm_device_batch_items: the same records from both, equal to the oracle's; then the ragged call with one item
+    of length 0 and one of length 1.  window_bits 7 takes the segment kernels, 12 the row / column sums."""
+    be = backend(port, name, curve, group)
+    s = libff_amd.sizes(curve, group)
+    aw, gw = s["affine_bytes"] // 8, s["g_bytes"] // 8
+    k, n = 3, 300
+    bases = [be.bases(n, 10 * j + 1) for j in range(k)]
+    scs = [be.scalars(n, 30 + j) for j in range(k)]
+    exact = isinstance(be, PortBackend)   # the C restatement gives the record itself, the integer model the point
+
+    def same(out, want):
+        return tuple(out) == want if exact else be.canon(out) == want
+
+    dev = _Dev(engine)
+    try:
+        d_b = [dev.put(b[:, :aw]) for b in bases]
+        d_s = [dev.put(x) for x in scs]
+        d_o = [dev.put(np.zeros(gw, dtype=np.uint64)) for _ in range(k)]
+
+        def fetch():
+            engine.synchronize()
+            outs = np.zeros((k, gw), dtype=np.uint64)
+            for j in range(k):
+                engine.d2h(outs[j], ctypes.c_void_p(d_o[j]))
+                engine.h2d(ctypes.c_void_p(d_o[j]), np.zeros(gw, dtype=np.uint64))
+            return outs
+
+        engine.msm_device_batch(curve, group, d_b, d_s, n, d_o, out_form=OUT_AFFINE, window_bits=window_bits)
+        equal = fetch()
+        lens = [n] * k
+        items = lambda: [dict(bases=d_b[j], n=lens[j], scalars=d_s[j], out=d_o[j]) for j in range(k)]
+        engine.msm_device_batch_items(curve, group, items(), out_form=OUT_AFFINE, window_bits=window_bits)
+        ragged = fetch()
+        assert (equal == ragged).all()
+        for j in range(k):
+            assert same(equal[j], be.msm(bases[j], scs[j])), j
+        lens = [n, 0, 1]
+        engine.msm_device_batch_items(curve, group, items(), out_form=OUT_AFFINE, window_bits=window_bits)
+        ragged = fetch()
+        assert (ragged[0] == equal[0]).all()
+        assert same(ragged[1], be.zero) and same(ragged[2], be.msm(bases[2][:1], scs[2][:1]))
+    finally:
+        dev.free()
+
+
+FOLD_CHILD = r'''
+import ctypes, sys
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+import numpy as np
+import libff_amd
+from oracle import port
+port.build()
+e = libff_amd.Engine(0)
+curve, group, n = 1, 2, 300
+vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+ptrs = lambda arrs: (ctypes.c_void_p * len(arrs))(*[vp(a) for a in arrs])
+bases = [port.bases_seq(curve, group, n, first=500 * j) for j in range(2)]
+scs = [port.scalars_sha512(curve, 3 + j, n) for j in range(2)]
+wants = [port.multi_exp(curve, group, b, x, port.BDLO12_SIGNED, port.FORM_SPECIAL, chunks=8, omp=True) for b, x in zip(bases, scs)]
+assert libff_amd.plan(curve, group, n, window_bits=15)["num_buckets"] == 1 << 14
+o = e._opts(window_bits=15, segment_len=2, out_form=libff_amd.OUT_AFFINE)
+outs = np.zeros((3, libff_amd.sizes(curve, group)["g_bytes"] // 8), dtype=np.uint64)
+rc = e.lib.amdmsm_multi_exp(e.h, curve, group, vp(bases[0]), ctypes.c_size_t(0), libff_amd.multi_exp_base_form_special,
+                            vp(scs[0]), ctypes.c_size_t(n), vp(outs[0]), ctypes.byref(o))
+assert rc == 0 and (outs[0] == wants[0]).all(), rc
+rc = e.lib.amdmsm_multi_exp_batch(e.h, curve, group, 2, ptrs(bases), ctypes.c_size_t(0), libff_amd.multi_exp_base_form_special,
+                                  ptrs(scs), ctypes.c_size_t(n), ptrs([outs[1], outs[2]]), ctypes.byref(o))
+assert rc == 0 and (outs[1] == wants[0]).all() and (outs[2] == wants[1]).all(), rc
+print("fold-child-ok")
+'''
+
+
+def test_fold_levels_of_the_segment_sums():
+    """The segment kernels with more segments than one launch folds: AMDMSM_ROWCOL=0, bls12_377 G2, window_bits = 15 and
+    segment_len = 2 give 2^14 / 2 = 8192 segments per window; k_reduce_segments folds 32 of them per wave, which leaves 256
+    two-lane rows -- more than the 256 lanes of k_sum_block -- so one k_sum_butterfly level runs in front of it.  One
+    MSM and a batch of two, each against the oracle."""
+    code = FOLD_CHILD % (REPO, os.path.join(REPO, "tests"))
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900,
+                       env=dict(os.environ, AMDMSM_ROWCOL="0"))
+    assert r.returncode == 0 and "fold-child-ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
+
+
 CHILD = r'''
 import os, sys
 sys.path.insert(0, %r); sys.path.insert(0, %r)
