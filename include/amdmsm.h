@@ -159,6 +159,26 @@ int amdmsm_multi_exp_filter_one_zero(amdmsm_ctx *ctx, int curve, int group,
 int amdmsm_batch_to_special(amdmsm_ctx *ctx, int curve, int group, void *elems_xyz,
                             size_t stride_bytes, size_t n);
 
+/* Element-wise scalar multiplication of a point vector: out[i] = scalars[i] * points[i], n results -- what a host does
+ * with libff's operator* in a loop (an SRS or proving key re-randomised, a powers-of-tau contribution).  One lane per
+ * element: a table of the element's multiples 1 P .. 8 P, then a signed 4-bit fixed-window ladder.  points_xyz, stride
+ * and base_form as for amdmsm_multi_exp; scalars are Montgomery residues, or with opts->scalars_plain any integers of
+ * fr_bytes (values >= r included: the result is the integer multiple); out_xyz receives n packed records in
+ * opts->out_form (AMDMSM_OUT_LIBFF by default; AMDMSM_OUT_AFFINE: special form, normalised as amdmsm_batch_to_special
+ * does).  The table takes 16 compact affine records of workspace per element, so the vector is worked through
+ * chunk_points elements at a time; 0 = as many as fit a workspace of 1 GiB.  n = 0 succeeds and writes nothing.
+ * opts->window_bits and opts->endomorphism are accepted and ignored.  With timing enabled, amdmsm_get_timings reports
+ * [0] import, [1] table, [2] ladder, [3] normalisation / export -- of the first chunk -- [4] the chunks after it,
+ * [AMDMSM_PH_TOTAL] the call. */
+int amdmsm_scalar_mul_vec(amdmsm_ctx *ctx, int curve, int group, const void *points_xyz, size_t stride_bytes,
+                          int base_form, const void *scalars, size_t n, void *out_xyz,
+                          size_t chunk_points, const amdmsm_opts *opts);
+/* the same on device-resident inputs: compact affine points (amdmsm_import_bases_device), n records written to
+ * d_out_xyz; enqueued on opts->stream (or the context's), not synchronised */
+int amdmsm_scalar_mul_vec_device(amdmsm_ctx *ctx, int curve, int group, const void *d_points_affine,
+                                 const void *d_scalars, size_t n, void *d_out_xyz,
+                                 size_t chunk_points, const amdmsm_opts *opts);
+
 /* k (<= 8) multi_exp calls of the same group, length and base form as ONE batch: for a caller that has k base vectors
  * of ONE length with a scalar vector each, instead of k calls of multiexp.tcc:643-688.  (The four G1 MSMs of libsnark's
  * r1cs_gg_ppzksnark_prover -- A, B, L, H -- have different lengths and share the assignment as their scalar vector:

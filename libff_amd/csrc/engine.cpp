@@ -2863,3 +2863,139 @@ int amdmsm_batch_to_special(amdmsm_ctx *ctx, int curve, int group, void *elems_x
 }
 
 }  // extern "C"
+
+// ---- element-wise scalar multiplication: out[i] = k_i * P_i ---------------------------------------------------------
+namespace {
+
+// The per-element table (group_vtable::smv_table) and its scratch are 2 * smv_entries compact affine records per element,
+// so a vector is worked through in chunks.  chunk_points = 0 picks the chunk from a workspace budget of 1 GiB: the
+// largest multiple of 256 elements whose table and scratch fit (at least 256).
+constexpr size_t SMV_WS_BUDGET = (size_t)1 << 30;
+size_t smv_ws_bytes(const group_vtable *vt, size_t cn) { return 2 * (size_t)vt->smv_entries * cn * (size_t)vt->el_words * 8; }
+size_t smv_chunk_points(const group_vtable *vt, size_t n, size_t chunk_points) {
+    size_t cn = chunk_points;
+    if (!cn) {
+        cn = SMV_WS_BUDGET / smv_ws_bytes(vt, 1) / 256 * 256;
+        if (cn < 256) cn = 256;
+    }
+    return cn < n ? cn : n;
+}
+
+// one chunk on device-resident inputs: table, ladder and -- for OUT_AFFINE -- the batch normalisation of
+// amdmsm_batch_to_special (import_bases of the ladder's libff records, one inversion per IMPORT_K of them, then
+// export_affine), its affine records in the table scratch, which the ladder no longer needs
+int smv_chunk(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, const uint32_t *d_aff, const uint32_t *d_sc, size_t cn,
+              uint32_t *d_out, int form, int mont, char *ws, ws_slot &sl, bool timed) {
+    uint32_t *table = (uint32_t *)ws, *tmp = (uint32_t *)(ws + smv_ws_bytes(vt, cn) / 2);
+    if (timed) record(ctx, sl, 1, st);
+    vt->smv_table(st, d_aff, cn, tmp, table);
+    if (timed) record(ctx, sl, 2, st);
+    vt->smv_ladder(st, table, cn, d_sc, mont, form == AMDMSM_OUT_AFFINE ? (int)AMDMSM_OUT_LIBFF : form, d_out);
+    if (timed) record(ctx, sl, 3, st);
+    if (form == AMDMSM_OUT_AFFINE) {
+        vt->import_bases(st, d_out, (size_t)vt->el_words * 3, 0, cn, tmp);
+        vt->export_affine(st, tmp, cn, d_out);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return AMDMSM_OK;
+}
+
+// the workspace slot of a call, sized for chunks of cn elements
+int smv_begin(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, size_t cn, ws_slot *&slp) {
+    const int slot_idx = (int)(ctx->next++ % (unsigned)ctx->depth);
+    ws_slot &sl = ctx->slots[slot_idx];
+    ctx->last_slot = slot_idx;
+    if (sl.used) HIP_TRY(ctx, hipStreamWaitEvent(st, sl.done, 0));   // previous user of this slot
+    slp = &sl;
+    return ensure_ws(ctx, sl, smv_ws_bytes(vt, cn));
+}
+// Phase times of a timed call, through the MSM's timing calls: [0] import (host entry: with the upload), [1] table,
+// [2] ladder, [3] normalisation / export (host entry: with the download) -- those four of the first chunk -- [4] the
+// chunks after the first, [AMDMSM_PH_TOTAL] the call.
+int smv_end(amdmsm_ctx *ctx, hipStream_t st, ws_slot &sl) {
+    record(ctx, sl, 5, st);
+    if (ctx->timing) sl.last_ticket = (long long)ctx->ticket++;
+    sl.ev_valid = ctx->timing;
+    HIP_TRY(ctx, hipEventRecord(sl.done, st));
+    sl.used = true;
+    return AMDMSM_OK;
+}
+
+}   // namespace
+
+extern "C" {
+
+// a group the library does not carry -- (MNT6, G2) -- is refused before anything else is looked at, the context included
+#define SMV_REFUSE_UNKNOWN(ctx, curve, group) \
+    if (!find_vt(curve, group)) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve/group")
+
+int amdmsm_scalar_mul_vec_device(amdmsm_ctx *ctx, int curve, int group, const void *d_points_affine, const void *d_scalars,
+                                 size_t n, void *d_out_xyz, size_t chunk_points, const amdmsm_opts *opts) {
+    SMV_REFUSE_UNKNOWN(ctx, curve, group);
+    GET_VT(ctx, curve, group);
+    CHECK_OPTS(ctx, opts);
+    if (n && (!d_points_affine || !d_scalars || !d_out_xyz)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null pointer");
+    if (!n) return AMDMSM_OK;
+    hipStream_t st = stream_of(ctx, opts);
+    const int form = opts ? opts->out_form : AMDMSM_OUT_LIBFF;
+    const int mont = (opts && opts->scalars_plain) ? 0 : 1;
+    const size_t ew = (size_t)vt->el_words, cn = smv_chunk_points(vt, n, chunk_points);
+    ws_slot *sl = nullptr;
+    int rc = smv_begin(ctx, vt, st, cn, sl);
+    if (rc) return rc;
+    record(ctx, *sl, 0, st);
+    for (size_t o = 0; o < n; o += cn) {
+        const size_t m = n - o < cn ? n - o : cn;
+        rc = smv_chunk(ctx, vt, st, (const uint32_t *)d_points_affine + o * 2 * ew, (const uint32_t *)d_scalars + o * vt->fr_words, m,
+                       (uint32_t *)d_out_xyz + o * 3 * ew, form, mont, (char *)sl->ws, *sl, o == 0);
+        if (rc) return rc;
+        if (o == 0) record(ctx, *sl, 4, st);
+    }
+    return smv_end(ctx, st, *sl);
+}
+
+int amdmsm_scalar_mul_vec(amdmsm_ctx *ctx, int curve, int group, const void *points_xyz, size_t stride_bytes, int base_form,
+                          const void *scalars, size_t n, void *out_xyz, size_t chunk_points, const amdmsm_opts *opts) {
+    SMV_REFUSE_UNKNOWN(ctx, curve, group);
+    GET_VT(ctx, curve, group);
+    CHECK_OPTS(ctx, opts);
+    if (n && (!points_xyz || !scalars || !out_xyz)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null pointer");
+    const size_t xyz_bytes = (size_t)vt->el_words * 12, aff_bytes = (size_t)vt->el_words * 8, fr_bytes = (size_t)vt->fr_words * 4;
+    if (stride_bytes == 0) stride_bytes = xyz_bytes;
+    if (stride_bytes % rec_align(vt) || stride_bytes < xyz_bytes) return fail(ctx, AMDMSM_ERR_BAD_ARG, "point stride");
+    if (!n) return AMDMSM_OK;
+    hipStream_t st = ctx->stream;
+    const amdmsm_opts o = opts_or_default(opts);
+    const int mont = o.scalars_plain ? 0 : 1;
+    const size_t cn = smv_chunk_points(vt, n, chunk_points);
+    int rc = ensure_buf(ctx, ctx->hb_src, cn * stride_bytes);
+    if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->hb_aff, cn * aff_bytes);
+    if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->hb_sc, cn * fr_bytes);
+    if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->fb.out, cn * xyz_bytes);
+    ws_slot *sl = nullptr;
+    if (rc == AMDMSM_OK) rc = smv_begin(ctx, vt, st, cn, sl);
+    if (rc) return rc;
+    record(ctx, *sl, 0, st);
+    for (size_t off = 0; off < n; off += cn) {
+        const size_t m = n - off < cn ? n - off : cn;
+        // the last record of a strided vector ends with its coordinates: nothing past them is read
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_src.p, (const char *)points_xyz + off * stride_bytes, (m - 1) * stride_bytes + xyz_bytes,
+                                    hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_sc.p, (const char *)scalars + off * fr_bytes, m * fr_bytes, hipMemcpyHostToDevice, st));
+        vt->import_bases(st, (const uint32_t *)ctx->hb_src.p, stride_bytes / 4, base_form == AMDMSM_FORM_SPECIAL, m,
+                         (uint32_t *)ctx->hb_aff.p);
+        rc = smv_chunk(ctx, vt, st, (const uint32_t *)ctx->hb_aff.p, (const uint32_t *)ctx->hb_sc.p, m, (uint32_t *)ctx->fb.out.p,
+                       o.out_form, mont, (char *)sl->ws, *sl, off == 0);
+        if (rc) {
+            (void)hipDeviceSynchronize();   // nothing of this call may still touch the staging buffers
+            return rc;
+        }
+        HIP_TRY(ctx, hipMemcpyAsync((char *)out_xyz + off * xyz_bytes, ctx->fb.out.p, m * xyz_bytes, hipMemcpyDeviceToHost, st));
+        if (off == 0) record(ctx, *sl, 4, st);
+        // the next chunk reuses the staging buffers
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+    }
+    return smv_end(ctx, st, *sl);
+}
+
+}  // extern "C"

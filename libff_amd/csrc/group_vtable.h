@@ -222,6 +222,15 @@ struct group_vtable {
     void (*sort_short)(hipStream_t, const void* scalars, int kind, int limit_bits, uint32_t* flag, size_t n, int mont, int c, int W,
                        uint32_t* coarse, uint32_t* cursor, int32_t* digits, uint32_t* tmp_payload, uint32_t* tmp_key,
                        uint32_t* ends, uint32_t* lists, size_t stride, uint32_t* big);
+
+    // Element-wise scalar multiplication out[i] = k_i * P_i (amdmsm_scalar_mul_vec), one lane per element.
+    // smv_table: table[j * n + i] = (j + 1) * P_i as compact affine records, j < smv_entries ((0, 0) = infinity); tmp: as
+    // many records of scratch.  smv_ladder: signed fixed-window ladder over that table; scalars as for `sort` (a plain
+    // scalar may be any integer of fr_words words), out: n records in `form` (OUT_AFFINE inverts once per lane: the engine
+    // asks for OUT_LIBFF and normalises the batch).
+    int smv_entries;
+    void (*smv_table)(hipStream_t, const uint32_t* bases_affine, size_t n, uint32_t* tmp, uint32_t* table);
+    void (*smv_ladder)(hipStream_t, const uint32_t* table, size_t n, const uint32_t* scalars, int mont, int form, uint32_t* out);
 };
 
 const group_vtable* vt_alt_bn128_g1() __attribute__((weak));

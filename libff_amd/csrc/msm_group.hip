@@ -3250,6 +3250,119 @@ __global__ void __launch_bounds__(TPB, 2) k_fb_exp_rr(const uint32_t* __restrict
 }
 #endif
 
+// ---------------------------------------------------------------- element-wise scalar multiplication
+// out[i] = k_i * P_i, one lane per element (amdmsm_scalar_mul_vec): a signed fixed-window ladder over a table of the
+// lane's own small multiples.  Entry j of element i, the affine point (j + 1) P_i, is record j * n + i of the table, so
+// that the lanes of a wave, which read one entry index each at the same step of the ladder, read neighbouring records
+// whenever their digits agree in magnitude.
+constexpr int SMV_W = 4;                      // window width
+constexpr int SMV_T = 1 << (SMV_W - 1);       // table entries per element: 1 P .. 2^(w-1) P
+constexpr int SMV_DIGITS = (32 * FRW + SMV_W - 1) / SMV_W + 1;   // the last digit is the carry out of the top window
+static_assert(32 % SMV_W == 0, "the digits are packed whole into 32-bit words");
+
+// table[j * n + i] = (j + 1) P_i, affine.  The multiples are built in Jacobian coordinates by repeated mixed addition of
+// P_i (the first addition copies P_i, the second meets the equal point and doubles) and made affine with one inversion per
+// lane, Montgomery's trick over the lane's own entries as in k_fb_table_affine: tmp[j * n + i] holds Z_j and the product
+// of the Z's before it between the two passes.  An infinite multiple (P_i infinite, or of order <= 2^(w-1)) becomes (0, 0).
+__global__ void __launch_bounds__(TPB) k_smv_table(const uint32_t* __restrict__ bases, size_t n, uint32_t* __restrict__ tmp,
+                                                   uint32_t* __restrict__ table) {
+    const size_t i = gtid();
+    if (i >= n) return;
+    Aff<E> p;
+    load_aff(p, bases + i * AFFW);
+    Jac<E> q;
+    jac_set_inf(q);
+    E acc;
+    el_one(acc);
+#pragma unroll 1
+    for (int j = 0; j < SMV_T; ++j) {
+        jac_madd(q, p);
+        const size_t rec = ((size_t)j * n + i) * AFFW;
+        el_store(table + rec, q.x);
+        el_store(table + rec + EW, q.y);
+        el_store(tmp + rec, q.z);
+        el_store(tmp + rec + EW, acc);   // prefix product of the Z's before this entry
+        if (!jac_is_inf(q)) el_mul(acc, acc, q.z);
+    }
+    E inv;
+    el_inv(inv, acc);
+#pragma unroll 1
+    for (int j = SMV_T; j-- > 0;) {
+        const size_t rec = ((size_t)j * n + i) * AFFW;
+        E z;
+        el_load(z, tmp + rec);
+        Aff<E> a;
+        if (el_is_zero(z)) {
+            el_zero(a.x);
+            el_zero(a.y);
+        } else {
+            E pre, zi, z2;
+            el_load(pre, tmp + rec + EW);
+            load_aff(a, table + rec);
+            el_mul(zi, inv, pre);      // Z_j^-1
+            el_mul(inv, inv, z);
+            el_sqr(z2, zi);
+            el_mul(a.x, a.x, z2);
+            el_mul(z2, z2, zi);
+            el_mul(a.y, a.y, z2);
+        }
+        store_aff(table + rec, a);
+    }
+}
+
+// The ladder: the scalar recoded to signed radix-2^w digits (for_each_signed_digit, one digit more than the scalar's
+// words hold for the carry out of the top window, so a plain scalar may be any integer of 32 FRW bits), taken from the
+// top: w doublings of the XYZZ accumulator, then the mixed addition of +-table[|d| - 1] -- xyzz_madd, whose equal-point
+// branch doubles with the a != 0 term and whose opposite-point branch gives infinity.  A digit lies in [-2^(w-1),
+// 2^(w-1)), so it is kept as a w-bit two's-complement field; the packed digits are shifted up window by window and no
+// private array is indexed at run time.
+__global__ void __launch_bounds__(TPB) k_smv_ladder(const uint32_t* __restrict__ table, size_t n,
+                                                    const uint32_t* __restrict__ scalars, int mont, int form,
+                                                    uint32_t* __restrict__ out) {
+    const size_t i = gtid();
+    if (i >= n) return;
+    uint32_t s[FRW];
+    load_scalar(s, scalars, i, mont);
+    constexpr int PER = 32 / SMV_W;
+    constexpr uint32_t DMASK = (1u << SMV_W) - 1u;
+    uint32_t rec[FRW];
+    uint32_t top = 0;
+#pragma unroll
+    for (int j = 0; j < FRW; ++j) rec[j] = 0;
+    for_each_signed_digit(s, SMV_W, SMV_DIGITS, [&](int w, int32_t d) {
+        const uint32_t f = ((uint32_t)d & DMASK) << ((w % PER) * SMV_W);
+#pragma unroll
+        for (int j = 0; j < FRW; ++j) rec[j] |= (w / PER == j) ? f : 0u;
+        top |= (w / PER == FRW) ? f : 0u;
+    });
+    Xyzz<E> acc;
+    xyzz_set_inf(acc);
+    Aff<E> e;
+    // the carry digit is 0 or 1
+    if (top) {
+        load_aff(e, table + i * AFFW);
+        xyzz_madd(acc, e);
+    }
+#pragma unroll 1
+    for (int w = SMV_DIGITS - 2; w >= 0; --w) {
+#pragma unroll 1
+        for (int k = 0; k < SMV_W; ++k) xyzz_dbl(acc, acc);
+        const uint32_t f = rec[FRW - 1] >> (32 - SMV_W);
+#pragma unroll
+        for (int j = FRW - 1; j >= 0; --j) rec[j] = (rec[j] << SMV_W) | (j ? rec[j - 1] >> (32 - SMV_W) : 0u);
+        const bool neg = (f >> (SMV_W - 1)) != 0;
+        const uint32_t mag = neg ? (1u << SMV_W) - f : f;
+        if (mag) {
+            load_aff(e, table + ((size_t)(mag - 1) * n + i) * AFFW);
+            el_cneg(e.y, e.y, neg);
+            xyzz_madd(acc, e);
+        }
+    }
+    Jac<E> res;
+    xyzz_to_jac(res, acc);
+    store_out(out + i * XYZW, res, form);
+}
+
 // ---------------------------------------------------------------- launchers
 inline unsigned blocks_for(size_t n, int tpb = TPB) { return (unsigned)((n + tpb - 1) / tpb); }
 
@@ -3651,6 +3764,14 @@ void l_madd_bench(hipStream_t st, const uint32_t* pts, uint32_t* out, size_t nth
 #endif
     hipLaunchKernelGGL(k_madd_bench<E>, dim3(blocks_for(nthreads)), dim3(TPB), 0, st, pts, out, nthreads, iters);
 }
+void l_smv_table(hipStream_t st, const uint32_t* bases, size_t n, uint32_t* tmp, uint32_t* table) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_smv_table, dim3(blocks_for(n)), dim3(TPB), 0, st, bases, n, tmp, table);
+}
+void l_smv_ladder(hipStream_t st, const uint32_t* table, size_t n, const uint32_t* scalars, int mont, int form, uint32_t* out) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_smv_ladder, dim3(blocks_for(n)), dim3(TPB), 0, st, table, n, scalars, mont, form, out);
+}
 
 const group_vtable g_vt = {
     GP::CURVE, GP::GROUP, FRW, EW, FQ::N, FR::BITS, GP::LIBFF_PROJECTIVE ? 1 : 0, (int)RED_FOLD, ZZS, FR::R,
@@ -3658,6 +3779,7 @@ const group_vtable g_vt = {
     l_import_bases, l_precompute_table, l_count, l_scatter, l_scalar_stats, l_sort, l_accumulate, l_accumulate_resident_lanes, (AMDMSM_OVERLAP_OK && ACC_OVERLAP_LDS) ? 1 : 0, l_accumulate_fixup, l_reduce_segments, l_sum_butterfly, l_sum_block, l_reduce_rowcol, l_horner, l_horner_batch, l_sum_points,
     l_gen_bases_seq, l_export_affine, l_ffi_decode_points, l_ffi_decode_scalars, l_ffi_encode_point, l_disk_decode, l_disk_decode_compressed, l_fixed_base_exp, l_field_op, l_group_op, l_digits, l_mul_bench, l_madd_bench,
     GP::HAS_ENDO ? 1 : 0, GP::COEFF_A != 0 ? 1 : 0, l_sort_sel, l_gather_scalars, l_scalar_bits, l_sort_short,
+    SMV_T, l_smv_table, l_smv_ladder,
 };
 
 }  // namespace

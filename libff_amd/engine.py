@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = [
     "amdmsm_digits_device", "amdmsm_mul_bench_device", "amdmsm_madd_bench_device", "amdmsm_malloc", "amdmsm_free",
     "amdmsm_memcpy_h2d", "amdmsm_memcpy_d2h", "amdmsm_synchronize",
     "amdmsm_plan_short", "amdmsm_scalar_bits_device", "amdmsm_multi_exp_short", "amdmsm_msm_device_short",
+    "amdmsm_scalar_mul_vec", "amdmsm_scalar_mul_vec_device",
 ]
 # amdmsm_scalar_desc.kind: Fr records, or the width in bytes of packed little-endian unsigned integers
 SCALAR_FR, SCALAR_U8, SCALAR_U16, SCALAR_U32, SCALAR_U64 = 0, 1, 2, 4, 8
@@ -609,6 +610,32 @@ class Engine:
         self._check(rc, "amdmsm_batch_exp")
         return out
 
+    def scalar_mul_vec(self, curve, group, points, scalars, base_form=multi_exp_base_form_normal, out_form=OUT_LIBFF,
+                       scalars_plain=False, chunk_points=0, stride_bytes=None, out=None):
+        """Element-wise scalar multiplication (``amdmsm_scalar_mul_vec``): ``out[i] = scalars[i] * points[i]``, what a
+        host does with libff's ``operator*`` in a loop.  ``points``: (n, 3 * coordinate limbs) libff records in
+        ``base_form``; ``scalars``: (n, fr_limbs) Montgomery residues, or with ``scalars_plain`` any integers of that
+        width (values >= r included).  ``chunk_points``: elements worked through at a time, 0 = automatic.
+        ``stride_bytes``: bytes between two records of ``points`` (default: packed).  ``out``: result array to fill."""
+        s = sizes(curve, group)
+        points = np.ascontiguousarray(points, dtype=np.uint64)
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64)
+        n = scalars.shape[0]
+        if out is None:
+            out = np.zeros((n, s["g_bytes"] // 8), dtype=np.uint64)
+        assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape == (n, s["g_bytes"] // 8)
+        if n:
+            assert scalars.shape == (n, s["fr_bytes"] // 8), "scalars must be (n, fr_limbs) uint64"
+            if stride_bytes is None:
+                assert points.shape == (n, s["g_bytes"] // 8), "points must be (n, 3*coord_limbs) uint64"
+        o = self._opts(out_form=out_form, scalars_plain=scalars_plain)
+        rc = self.lib.amdmsm_scalar_mul_vec(self.h, curve, group, _np_ptr(points) if n else None,
+                                            ctypes.c_size_t(s["g_bytes"] if stride_bytes is None else stride_bytes), base_form,
+                                            _np_ptr(scalars) if n else None, ctypes.c_size_t(n), _np_ptr(out) if n else None,
+                                            ctypes.c_size_t(chunk_points), ctypes.byref(o))
+        self._check(rc, "amdmsm_scalar_mul_vec")
+        return out
+
     def batch_exp_timings(self):
         """device times (ms) of the last batch_exp: inputs H2D, window table (0 = reused), exponentiations, results D2H"""
         ms = (ctypes.c_float * 4)()
@@ -717,6 +744,14 @@ class Engine:
                                                            _vp(d_shared_scalars) if d_shared_scalars else None,
                                                            ctypes.c_size_t(shared_n), ctypes.byref(o)),
                     "amdmsm_msm_device_batch_items")
+
+    def scalar_mul_vec_device(self, curve, group, d_points_affine, d_scalars, n, d_out_xyz, out_form=OUT_LIBFF,
+                              scalars_plain=False, chunk_points=0, stream=None):
+        """``scalar_mul_vec`` on device-resident compact affine points; enqueued on ``stream``, not synchronised."""
+        o = self._opts(out_form=out_form, scalars_plain=scalars_plain, stream=stream)
+        self._check(self.lib.amdmsm_scalar_mul_vec_device(self.h, curve, group, _vp(d_points_affine), _vp(d_scalars),
+                                                          ctypes.c_size_t(n), _vp(d_out_xyz), ctypes.c_size_t(chunk_points),
+                                                          ctypes.byref(o)), "amdmsm_scalar_mul_vec_device")
 
     def precompute_bases_device(self, curve, group, d_bases_affine, n, c, num_digits, d_table, stream=None):
         self._check(self.lib.amdmsm_precompute_bases_device(

@@ -3,8 +3,8 @@
     hipcc --offload-device-only -S ... -o <dir>/<group>.s      (once per build and group, flags of libff_amd/build.py)
     python tools/asm_identity.py <dir_before> <dir_after>
 
-Comments and assembler directives are dropped, the ordinal of the function inside local labels (.LBB<fn>_<block>) is
-removed, and a function's body is what stands between its label and the next function's label.  Reports, per group, the
+Comments and assembler directives are dropped, the ordinals that count functions or long branches of the whole file inside
+local labels (.LBB<fn>_<block>, .Lpost_getpc<k>) are removed, and a function's body is what stands between its label and the next function's label.  Reports, per group, the
 functions whose text differs and the ones only one side has; exit code 1 when a function of the first build differs or
 is gone.  (DESIGN sections 9 and 10 quote its outcome.)
 """
@@ -30,7 +30,8 @@ def functions(path):
             continue   # directive
         if cur is not None:
             # local labels carry the function's ordinal in the file (.LBB<fn>_<block>), which moves when a kernel is added
-            cur.append(re.sub(r"\.L(BB|JTI|CPI)\d+_", r".L\1_", line.strip()))
+            # (so does the file-wide ordinal of a long branch's .Lpost_getpc<k> label)
+            cur.append(re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc", re.sub(r"\.L(BB|JTI|CPI)\d+_", r".L\1_", line.strip())))
     return out
 
 
