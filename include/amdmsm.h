@@ -179,6 +179,41 @@ int amdmsm_scalar_mul_vec_device(amdmsm_ctx *ctx, int curve, int group, const vo
                                  const void *d_scalars, size_t n, void *d_out_xyz,
                                  size_t chunk_points, const amdmsm_opts *opts);
 
+/* Segmented MSM: m sums in one call, out[j] = sum of scalars[i] * base(i) over offsets[j] <= i < offsets[j + 1] -- the
+ * shape of k proofs verified as a batch (sum of input_i * IC_i per proof), of row or column commitments, of the cross
+ * terms of an inner-product argument.  A single MSM per segment would pay the fixed cost of its launch chain m times;
+ * here a lane owns one (segment, 4-bit window) pair, adds the segment's terms from the table of amdmsm_scalar_mul_vec
+ * without ever doubling, and the doublings are paid once per segment in a Horner chain.
+ *   bases     as for amdmsm_multi_exp (records, stride, form).  Without flags n_bases == n_terms and term i uses base
+ *             i; with AMDMSM_SEG_SHARED_BASES term i of segment j uses base i - offsets[j] (one query shared by all
+ *             segments, its table built once), and n_bases is at least the longest segment
+ *   scalars   n_terms Montgomery residues, or with opts->scalars_plain any integers of fr_bytes (k >= r means k mod r)
+ *   offsets   m + 1 values in HOST memory (in the device entry too), non-decreasing, offsets[m] <= n_terms;
+ *             offsets[0] may be above 0; terms outside every segment are ignored, an empty segment gives zero
+ *   long_from segments of at least this many terms are run one after the other through the single-MSM route of
+ *             amdmsm_msm_device instead; 0 = the library's default, SIZE_MAX = never
+ *   out       m packed records in opts->out_form (AMDMSM_OUT_LIBFF by default; AMDMSM_OUT_AFFINE normalises the batch
+ *             as amdmsm_batch_to_special does), written only when the call succeeds
+ * AMDMSM_ERR_BAD_ARG, with amdmsm_last_error naming the segment, before anything is launched or written: a null
+ * pointer with work to do, a bad stride, a decreasing offset, offsets[m] > n_terms, an unknown flag, n_bases != n_terms
+ * without the flag, a segment longer than n_bases with it.  m = 0 succeeds and writes nothing.  The workspace follows
+ * the 1 GiB rule of amdmsm_scalar_mul_vec, chunked by whole segments.  With timing enabled: [0] table, [1] digits,
+ * [2] accumulation, [3] Horner -- of the first chunk -- [4] its normalisation and the chunks after it,
+ * [AMDMSM_PH_TOTAL] the segment pass; a segment on the single-MSM route is a timed MSM of its own. */
+#define AMDMSM_SEG_SHARED_BASES 1u
+int amdmsm_multi_exp_segments(amdmsm_ctx *ctx, int curve, int group, const void *bases_xyz, size_t base_stride_bytes,
+                              int base_form, size_t n_bases, const void *scalars, size_t n_terms,
+                              const uint64_t *offsets, size_t m, unsigned flags, size_t long_from, void *out,
+                              const amdmsm_opts *opts);
+/* the same on device-resident inputs: compact affine bases, m records written to d_out; enqueued on opts->stream (or the
+ * context's), not synchronised */
+int amdmsm_msm_device_segments(amdmsm_ctx *ctx, int curve, int group, const void *d_bases_affine, size_t n_bases,
+                               const void *d_scalars, size_t n_terms, const uint64_t *offsets, size_t m,
+                               unsigned flags, size_t long_from, void *d_out, const amdmsm_opts *opts);
+/* terms a segmented MSM of this context works through at a time (whole segments; a longer segment is a chunk of its own),
+ * 0 = as many as fit the workspace rule (the default) */
+int amdmsm_set_segments_chunk_terms(amdmsm_ctx *ctx, size_t chunk_terms);
+
 /* k (<= 8) multi_exp calls of the same group, length and base form as ONE batch: for a caller that has k base vectors
  * of ONE length with a scalar vector each, instead of k calls of multiexp.tcc:643-688.  (The four G1 MSMs of libsnark's
  * r1cs_gg_ppzksnark_prover -- A, B, L, H -- have different lengths and share the assignment as their scalar vector:

@@ -108,6 +108,10 @@ struct amdmsm_ctx {
     grow_buf hb_src, hb_aff, hb_sc, hb_out, hb_stats;
     grow_buf short_word, short_out;          // short scalars: [0] promise flag, [1] measured bit length; result held back until the flag is read
     grow_buf hb_idx, sel_flag, sel_gather;   // batch items: index lists, out-of-range flags, scalars gathered for one MSM
+    size_t seg_chunk_terms = 0;              // amdmsm_set_segments_chunk_terms: terms a segmented MSM works through at a time, 0 = automatic
+    void *seg_host = nullptr;                // segmented MSM: pinned staging of the slice descriptors (grow-only) and the
+    size_t seg_host_bytes = 0;               // event behind their last upload, which the next call waits for before it
+    hipEvent_t seg_copied = nullptr;         // overwrites them
     hipStream_t copy_stream = nullptr;
     hipEvent_t bases_ready = nullptr, host_done = nullptr;
     // Several MSMs in flight (pipeline depth > 1), overlap by construction: the bulk of every MSM -- bucket sort
@@ -1133,6 +1137,8 @@ void amdmsm_ctx_destroy(amdmsm_ctx *ctx) {
             }
         }
         if (ctx->chunk_partials) (void)hipFree(ctx->chunk_partials);
+        if (ctx->seg_host) (void)hipHostFree(ctx->seg_host);
+        if (ctx->seg_copied) (void)hipEventDestroy(ctx->seg_copied);
         for (auto &e : ctx->aux_ev) {
             if (e) (void)hipEventDestroy(e);
         }
@@ -2901,13 +2907,16 @@ int smv_chunk(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, const uin
 }
 
 // the workspace slot of a call, sized for chunks of cn elements
-int smv_begin(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, size_t cn, ws_slot *&slp) {
+int slot_begin(amdmsm_ctx *ctx, hipStream_t st, size_t bytes, ws_slot *&slp) {
     const int slot_idx = (int)(ctx->next++ % (unsigned)ctx->depth);
     ws_slot &sl = ctx->slots[slot_idx];
     ctx->last_slot = slot_idx;
     if (sl.used) HIP_TRY(ctx, hipStreamWaitEvent(st, sl.done, 0));   // previous user of this slot
     slp = &sl;
-    return ensure_ws(ctx, sl, smv_ws_bytes(vt, cn));
+    return ensure_ws(ctx, sl, bytes);
+}
+int smv_begin(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, size_t cn, ws_slot *&slp) {
+    return slot_begin(ctx, st, smv_ws_bytes(vt, cn), slp);
 }
 // Phase times of a timed call, through the MSM's timing calls: [0] import (host entry: with the upload), [1] table,
 // [2] ladder, [3] normalisation / export (host entry: with the download) -- those four of the first chunk -- [4] the
@@ -2996,6 +3005,272 @@ int amdmsm_scalar_mul_vec(amdmsm_ctx *ctx, int curve, int group, const void *poi
         HIP_TRY(ctx, hipStreamSynchronize(st));
     }
     return smv_end(ctx, st, *sl);
+}
+
+}  // extern "C"
+
+// ---- segmented MSM: out[j] = sum of s_i * P_i over segment j ------------------------------------------------------------
+namespace {
+
+// Terms one accumulation lane adds in a row: a longer segment is cut into slices of this many terms, whose window sums
+// are added before the Horner chain, so that one long segment among short ones does not hold its 65 .. 97 lanes for the
+// whole pass.
+constexpr size_t SEG_CHAIN_CAP = 512;
+// Segments of at least this many terms take the single-MSM route when the caller passes long_from = 0.  Measured
+// (profiles/segmented_msm.txt): a lone segment of 2^8 .. 2^14 terms is faster on the single-MSM route
+// at every size -- one segment cannot fill the device -- so that sweep gives no default; the rule is the length at which
+// a segment costs the segment pass of a full device (2^10 segments of 256 terms: 19 / 158 / 32 ns per term for
+// alt_bn128 G1 / bls12_377 G2 / mnt4 G1) what a single MSM of that length costs (0.49 / 2.1 / 1.35 ms): 2^14.6 / 2^13.7 /
+// 2^15.3 terms, rounded down, keyed by the words per coordinate (8 / 24 / 10 measured, the others by width).
+size_t seg_long_from_default(const group_vtable *vt) { return vt->el_words > 12 ? (size_t)1 << 13 : (size_t)1 << 14; }
+
+// a run of consecutive short segments worked through in one pass: segments [j0, j1), terms [t0, t0 + ct), ns slices;
+// desc: word offset of its descriptors (ns slices of 4 words, then j1 - j0 + 1 words of seg_first)
+struct seg_chunk {
+    size_t j0, j1, t0, ct, ns, desc;
+};
+struct seg_layout {
+    size_t table, digits, sums, winsum, norm, total;   // byte offsets inside a chunk's area
+};
+seg_layout seg_chunk_layout(const group_vtable *vt, bool shared, size_t ct, size_t ns, size_t mc) {
+    const size_t aff_bytes = (size_t)vt->el_words * 8, D = (size_t)vt->seg_windows;
+    seg_layout l;
+    size_t off = 0;
+    l.table = off;
+    if (!shared) off = align_up(off + smv_ws_bytes(vt, ct), 256);   // table and its scratch
+    l.digits = off;
+    off = align_up(off + ct * (size_t)vt->seg_digit_stride, 256);
+    l.sums = off;
+    off = align_up(off + ns * D * (size_t)vt->el_words * 16, 256);
+    l.winsum = off;
+    off = align_up(off + mc * D * (size_t)vt->el_words * 12, 256);
+    l.norm = off;
+    off = align_up(off + mc * aff_bytes, 256);
+    l.total = off;
+    return l;
+}
+
+// the argument rules of both entries; nothing is launched or written before they hold
+int seg_check(amdmsm_ctx *ctx, const void *bases, size_t n_bases, const void *scalars, size_t n_terms, const uint64_t *offsets,
+              size_t m, unsigned flags, const void *out) {
+    if (flags & ~(unsigned)AMDMSM_SEG_SHARED_BASES) return fail(ctx, AMDMSM_ERR_BAD_ARG, "unknown flag");
+    if (!m) return AMDMSM_OK;
+    if (!offsets || !out) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null pointer");
+    const bool shared = (flags & AMDMSM_SEG_SHARED_BASES) != 0;
+    if (!shared && n_bases != n_terms) return fail(ctx, AMDMSM_ERR_BAD_ARG, "n_bases must equal n_terms without AMDMSM_SEG_SHARED_BASES");
+    for (size_t j = 0; j < m; ++j) {
+        if (offsets[j + 1] < offsets[j]) return fail(ctx, AMDMSM_ERR_BAD_ARG, "segment " + std::to_string(j) + ": offsets decrease");
+        if (shared && offsets[j + 1] - offsets[j] > n_bases)
+            return fail(ctx, AMDMSM_ERR_BAD_ARG, "segment " + std::to_string(j) + ": longer than the shared base vector");
+    }
+    if (offsets[m] > n_terms) return fail(ctx, AMDMSM_ERR_BAD_ARG, "segment " + std::to_string(m - 1) + ": offsets[m] > n_terms");
+    if (offsets[m] > offsets[0] && (!bases || !scalars)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null pointer");
+    return AMDMSM_OK;
+}
+
+// Device-resident inputs, arguments checked.  The short segments run chunk by chunk -- whole segments, as many as keep
+// table, table scratch, digits and window sums inside SMV_WS_BUDGET (a segment too long for that alone is a chunk of its
+// own) -- in the call's workspace slot; a segment of long_from terms or more ends the chunk in front of it and is run
+// afterwards through msm_device_ranges, straight into its own out[j].  Phase times of a timed call: [0] table (the
+// shared one, or the first chunk's), [1] digits, [2] accumulation and slice sums, [3] Horner -- of the first chunk --
+// [4] its normalisation and the chunks after it, [AMDMSM_PH_TOTAL] the short pass; every long segment is a timed MSM of
+// its own.
+int seg_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_bases, size_t n_bases, const uint32_t *d_scalars,
+                    const uint64_t *offsets, size_t m, unsigned flags, size_t long_from, uint32_t *d_out, const amdmsm_opts *opts) {
+    hipStream_t st = stream_of(ctx, opts);
+    const int form = opts ? opts->out_form : AMDMSM_OUT_LIBFF;
+    const int mont = (opts && opts->scalars_plain) ? 0 : 1;
+    const bool shared = (flags & AMDMSM_SEG_SHARED_BASES) != 0;
+    if (!long_from) long_from = seg_long_from_default(vt);
+    const size_t ew = (size_t)vt->el_words, xyzw = 3 * ew, affw = 2 * ew, frw = (size_t)vt->fr_words;
+    const size_t cap_terms = ctx->seg_chunk_terms;
+
+    std::vector<seg_chunk> chunks;
+    std::vector<size_t> longs;
+    std::vector<uint32_t> desc;
+    size_t chunk_area = 0;
+    auto close = [&](seg_chunk &c, size_t j1) {
+        c.j1 = j1;
+        if (c.j1 == c.j0) return;
+        // descriptors: the slices, then seg_first (padded to whole 16-byte records)
+        c.desc = desc.size();
+        size_t ns = 0;
+        for (size_t j = c.j0; j < c.j1; ++j) {
+            const size_t len = (size_t)(offsets[j + 1] - offsets[j]);
+            for (size_t k = 0; k < len; k += SEG_CHAIN_CAP) {
+                const size_t a = (size_t)offsets[j] - c.t0 + k, e = std::min(a + SEG_CHAIN_CAP, (size_t)offsets[j + 1] - c.t0);
+                desc.insert(desc.end(), {(uint32_t)a, (uint32_t)e, (uint32_t)(shared ? k : a), 0u});
+                ++ns;
+            }
+        }
+        size_t first = 0;
+        for (size_t j = c.j0; j < c.j1; ++j) {
+            desc.push_back((uint32_t)first);
+            first += ((size_t)(offsets[j + 1] - offsets[j]) + SEG_CHAIN_CAP - 1) / SEG_CHAIN_CAP;
+        }
+        desc.push_back((uint32_t)first);
+        while (desc.size() % 4) desc.push_back(0u);
+        c.ns = ns;
+        chunk_area = std::max(chunk_area, seg_chunk_layout(vt, shared, c.ct, c.ns, c.j1 - c.j0).total);
+        chunks.push_back(c);
+    };
+    seg_chunk cur{0, 0, m ? (size_t)offsets[0] : 0, 0, 0, 0};
+    for (size_t j = 0; j < m; ++j) {
+        const size_t len = (size_t)(offsets[j + 1] - offsets[j]);
+        if (len >= long_from) {
+            close(cur, j);
+            longs.push_back(j);
+            cur = seg_chunk{j + 1, j + 1, (size_t)offsets[j + 1], 0, 0, 0};
+            continue;
+        }
+        if (len >= ((size_t)1 << 31)) return fail(ctx, AMDMSM_ERR_TOO_LARGE, "segment " + std::to_string(j) + ": too long for the segment pass");
+        const size_t sl = (len + SEG_CHAIN_CAP - 1) / SEG_CHAIN_CAP;
+        if (cur.j1 > cur.j0 && ((cap_terms && cur.ct + len > cap_terms) || cur.ct + len >= ((size_t)1 << 31) ||
+                                seg_chunk_layout(vt, shared, cur.ct + len, cur.ns + sl, j + 1 - cur.j0).total > SMV_WS_BUDGET)) {
+            close(cur, j);
+            cur = seg_chunk{j, j, (size_t)offsets[j], 0, 0, 0};
+        }
+        cur.ct += len;
+        cur.ns += sl;
+        cur.j1 = j + 1;
+    }
+    close(cur, cur.j1);
+
+    if (!chunks.empty()) {
+        // workspace: descriptors of every chunk | shared table | one chunk's area (the shared table's scratch lies there too)
+        const size_t desc_bytes = align_up(desc.size() * 4, 256);
+        const size_t shared_bytes = shared ? align_up(smv_ws_bytes(vt, n_bases) / 2, 256) : 0;
+        if (shared) chunk_area = std::max(chunk_area, smv_ws_bytes(vt, n_bases) / 2);
+        ws_slot *sl = nullptr;
+        int rc = slot_begin(ctx, st, desc_bytes + shared_bytes + chunk_area, sl);
+        if (rc) return rc;
+        char *ws = (char *)sl->ws, *area = ws + desc_bytes + shared_bytes;
+        const uint32_t *d_desc = (const uint32_t *)ws;
+        uint32_t *shared_table = (uint32_t *)(ws + desc_bytes);
+        // the descriptors go up through pinned memory, so that the call stays asynchronous
+        if (ctx->seg_copied) HIP_TRY(ctx, hipEventSynchronize(ctx->seg_copied));
+        else HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->seg_copied, hipEventDisableTiming));
+        if (ctx->seg_host_bytes < desc.size() * 4) {
+            if (ctx->seg_host) HIP_TRY(ctx, hipHostFree(ctx->seg_host));
+            ctx->seg_host = nullptr;
+            ctx->seg_host_bytes = 0;
+            HIP_TRY(ctx, hipHostMalloc(&ctx->seg_host, desc.size() * 4 * 2, hipHostMallocDefault));
+            ctx->seg_host_bytes = desc.size() * 4 * 2;
+        }
+        memcpy(ctx->seg_host, desc.data(), desc.size() * 4);
+        HIP_TRY(ctx, hipMemcpyAsync(ws, ctx->seg_host, desc.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipEventRecord(ctx->seg_copied, st));
+        record(ctx, *sl, 0, st);
+        if (shared) vt->smv_table(st, d_bases, n_bases, (uint32_t *)area, shared_table);
+        bool first = true;
+        for (const seg_chunk &c : chunks) {
+            const size_t mc = c.j1 - c.j0;
+            const seg_layout l = seg_chunk_layout(vt, shared, c.ct, c.ns, mc);
+            uint32_t *table = shared ? shared_table : (uint32_t *)(area + l.table);
+            uint32_t *digits = (uint32_t *)(area + l.digits), *sums = (uint32_t *)(area + l.sums);
+            uint32_t *winsum = (uint32_t *)(area + l.winsum), *norm = (uint32_t *)(area + l.norm);
+            uint32_t *out = d_out + c.j0 * xyzw;
+            if (!shared) vt->smv_table(st, d_bases + c.t0 * affw, c.ct, (uint32_t *)(area + l.table + smv_ws_bytes(vt, c.ct) / 2), table);
+            if (first) record(ctx, *sl, 1, st);
+            vt->seg_digits(st, d_scalars + c.t0 * frw, c.ct, mont, digits);
+            if (first) record(ctx, *sl, 2, st);
+            vt->seg_accumulate(st, table, shared ? n_bases : c.ct, digits, d_desc + c.desc, c.ns, sums);
+            vt->seg_fold(st, sums, d_desc + c.desc + 4 * c.ns, mc, winsum);
+            if (first) record(ctx, *sl, 3, st);
+            vt->seg_horner(st, winsum, mc, form == AMDMSM_OUT_AFFINE ? (int)AMDMSM_OUT_LIBFF : form, out);
+            if (first) record(ctx, *sl, 4, st);
+            if (form == AMDMSM_OUT_AFFINE) {   // the batch normalisation of amdmsm_batch_to_special, as smv_chunk does it
+                vt->import_bases(st, out, xyzw, 0, mc, norm);
+                vt->export_affine(st, norm, mc, out);
+            }
+            HIP_TRY(ctx, hipGetLastError());
+            first = false;
+        }
+        rc = smv_end(ctx, st, *sl);
+        if (rc) return rc;
+    }
+    for (size_t j : longs) {
+        const size_t len = (size_t)(offsets[j + 1] - offsets[j]);
+        const int rc = msm_device_ranges(ctx, vt, shared ? d_bases : d_bases + (size_t)offsets[j] * affw,
+                                         d_scalars + (size_t)offsets[j] * frw, len, d_out + j * xyzw, opts);
+        if (rc) return rc;
+    }
+    return AMDMSM_OK;
+}
+
+}   // namespace
+
+extern "C" {
+
+int amdmsm_set_segments_chunk_terms(amdmsm_ctx *ctx, size_t chunk_terms) {
+    if (!ctx) return AMDMSM_ERR_BAD_ARG;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    ctx->seg_chunk_terms = chunk_terms;
+    return AMDMSM_OK;
+}
+
+int amdmsm_msm_device_segments(amdmsm_ctx *ctx, int curve, int group, const void *d_bases_affine, size_t n_bases,
+                               const void *d_scalars, size_t n_terms, const uint64_t *offsets, size_t m, unsigned flags,
+                               size_t long_from, void *d_out, const amdmsm_opts *opts) {
+    SMV_REFUSE_UNKNOWN(ctx, curve, group);
+    GET_VT(ctx, curve, group);
+    CHECK_OPTS(ctx, opts);
+    const int rc = seg_check(ctx, d_bases_affine, n_bases, d_scalars, n_terms, offsets, m, flags, d_out);
+    if (rc || !m) return rc;
+    return seg_device_impl(ctx, vt, (const uint32_t *)d_bases_affine, n_bases, (const uint32_t *)d_scalars, offsets, m, flags,
+                           long_from, (uint32_t *)d_out, opts);
+}
+
+int amdmsm_multi_exp_segments(amdmsm_ctx *ctx, int curve, int group, const void *bases_xyz, size_t base_stride_bytes,
+                              int base_form, size_t n_bases, const void *scalars, size_t n_terms, const uint64_t *offsets,
+                              size_t m, unsigned flags, size_t long_from, void *out, const amdmsm_opts *opts) {
+    SMV_REFUSE_UNKNOWN(ctx, curve, group);
+    GET_VT(ctx, curve, group);
+    CHECK_OPTS(ctx, opts);
+    const size_t xyz_bytes = (size_t)vt->el_words * 12, aff_bytes = (size_t)vt->el_words * 8, fr_bytes = (size_t)vt->fr_words * 4;
+    if (base_stride_bytes == 0) base_stride_bytes = xyz_bytes;
+    if (base_stride_bytes % rec_align(vt) || base_stride_bytes < xyz_bytes) return fail(ctx, AMDMSM_ERR_BAD_ARG, "base stride");
+    int rc = seg_check(ctx, bases_xyz, n_bases, scalars, n_terms, offsets, m, flags, out);
+    if (rc || !m) return rc;
+    // only the terms some segment names are staged: offsets are rebased to the first of them
+    const bool shared = (flags & AMDMSM_SEG_SHARED_BASES) != 0;
+    const size_t t0 = (size_t)offsets[0], nt = (size_t)offsets[m] - t0;
+    std::vector<uint64_t> offs(m + 1);
+    size_t longest = 0;
+    for (size_t j = 0; j <= m; ++j) {
+        offs[j] = offsets[j] - t0;
+        if (j) longest = std::max(longest, (size_t)(offs[j] - offs[j - 1]));
+    }
+    const size_t b0 = shared ? 0 : t0, nb = shared ? longest : nt;   // the bases in use
+    hipStream_t st = ctx->stream;
+    amdmsm_opts o = opts_or_default(opts);
+    o.stream = nullptr;
+    rc = ensure_buf(ctx, ctx->hb_src, nb ? nb * base_stride_bytes : 16);
+    if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->hb_aff, nb ? nb * aff_bytes : 16);
+    if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->hb_sc, nt ? nt * fr_bytes : 16);
+    if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->fb.out, m * xyz_bytes);
+    if (rc) return rc;
+    if (nb) {
+        // the last record of a strided vector ends with its coordinates: nothing past them is read
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_src.p, (const char *)bases_xyz + b0 * base_stride_bytes,
+                                    (nb - 1) * base_stride_bytes + xyz_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_sc.p, (const char *)scalars + t0 * fr_bytes, nt * fr_bytes, hipMemcpyHostToDevice, st));
+        vt->import_bases(st, (const uint32_t *)ctx->hb_src.p, base_stride_bytes / 4, base_form == AMDMSM_FORM_SPECIAL, nb,
+                         (uint32_t *)ctx->hb_aff.p);
+    }
+    rc = seg_device_impl(ctx, vt, (const uint32_t *)ctx->hb_aff.p, nb, (const uint32_t *)ctx->hb_sc.p, offs.data(), m, flags,
+                         long_from, (uint32_t *)ctx->fb.out.p, &o);
+    // the results reach the caller's array only when the whole call has succeeded
+    std::vector<char> h_out(m * xyz_bytes);
+    hipError_t e = hipSuccess;
+    if (rc == AMDMSM_OK) e = hipMemcpyAsync(h_out.data(), ctx->fb.out.p, m * xyz_bytes, hipMemcpyDeviceToHost, st);
+    if (rc == AMDMSM_OK && e == hipSuccess) e = hipStreamSynchronize(st);
+    if (rc || e != hipSuccess) {
+        (void)hipDeviceSynchronize();   // nothing of this call may still touch the staging buffers
+        return rc ? rc : fail(ctx, AMDMSM_ERR_HIP, hipGetErrorString(e));
+    }
+    memcpy(out, h_out.data(), m * xyz_bytes);
+    return AMDMSM_OK;
 }
 
 }  // extern "C"

@@ -231,6 +231,22 @@ struct group_vtable {
     int smv_entries;
     void (*smv_table)(hipStream_t, const uint32_t* bases_affine, size_t n, uint32_t* tmp, uint32_t* table);
     void (*smv_ladder)(hipStream_t, const uint32_t* table, size_t n, const uint32_t* scalars, int mont, int form, uint32_t* out);
+
+    // Segmented MSM out[j] = sum of k_t * P_t over segment j (amdmsm_multi_exp_segments), over smv_table's records and
+    // the ladder's signed 4-bit digits, seg_windows of them per scalar.
+    // seg_digits: digits[t * seg_digit_stride + w] = digit w of scalar t, one signed byte each (n * seg_digit_stride bytes).
+    // seg_accumulate: one lane per (slice, window).  slices[4 s ..] = (first term, end term, table column of the first
+    // term, unused): terms index `digits`, columns the table's rows of nt records; sums: n_slices * seg_windows
+    // (X, Y, ZZ, ZZZ) records of 4 * el_words words.
+    // seg_fold: winsum[seg * seg_windows + w] = sum over the slices [seg_first[seg], seg_first[seg + 1]) of their window
+    // sum w, engine Jacobian (seg_first: m + 1 words).  seg_horner: out[seg] = Horner over the segment's window sums in
+    // `form`, one wave per segment (m < 2^31).
+    int seg_windows, seg_digit_stride;
+    void (*seg_digits)(hipStream_t, const uint32_t* scalars, size_t n, int mont, uint32_t* digits);
+    void (*seg_accumulate)(hipStream_t, const uint32_t* table, size_t nt, const uint32_t* digits, const uint32_t* slices,
+                           size_t n_slices, uint32_t* sums);
+    void (*seg_fold)(hipStream_t, const uint32_t* sums, const uint32_t* seg_first, size_t m, uint32_t* winsum);
+    void (*seg_horner)(hipStream_t, const uint32_t* winsum, size_t m, int form, uint32_t* out);
 };
 
 const group_vtable* vt_alt_bn128_g1() __attribute__((weak));

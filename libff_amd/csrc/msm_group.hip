@@ -3363,6 +3363,93 @@ __global__ void __launch_bounds__(TPB) k_smv_ladder(const uint32_t* __restrict__
     store_out(out + i * XYZW, res, form);
 }
 
+// ---------------------------------------------------------------- segmented MSM
+// out[j] = sum of k_t * P_t over the terms of segment j, many short segments in one pass (amdmsm_multi_exp_segments).
+// The terms share the ladder's table (k_smv_table) and its signed 4-bit digits, but a lane owns one (slice, window)
+// pair instead of one term: it adds +-table[|d| - 1] of every term of its slice -- a slice is a segment, or a piece of
+// a long one -- and no lane doubles anything.  The doublings are paid once per segment, in the Horner chain over its
+// SMV_DIGITS window sums.
+constexpr int SEG_DS = (SMV_DIGITS + 3) / 4 * 4;   // bytes between the digit rows of two terms
+
+// digits[t * SEG_DS + w] = digit w of scalar t as a signed byte: the lanes of one segment, which step through its terms
+// together and differ only in w, read one term's digits from neighbouring bytes.  One pass of its own: recoding inside
+// the accumulation lane would repeat the scalar's Montgomery reduction SMV_DIGITS times per term.
+__global__ void __launch_bounds__(TPB) k_seg_digits(const uint32_t* __restrict__ scalars, size_t n, int mont,
+                                                    uint32_t* __restrict__ digits) {
+    const size_t i = gtid();
+    if (i >= n) return;
+    uint32_t s[FRW];
+    load_scalar(s, scalars, i, mont);
+    uint32_t* row = digits + i * (SEG_DS / 4);
+    uint32_t word = 0;
+    for_each_signed_digit(s, SMV_W, SMV_DIGITS, [&](int w, int32_t d) {
+        word |= ((uint32_t)d & 0xffu) << ((w & 3) * 8);
+        if ((w & 3) == 3 || w == SMV_DIGITS - 1) {
+            row[w >> 2] = word;
+            word = 0;
+        }
+    });
+}
+
+// Lane L = slice * SMV_DIGITS + w.  slices[s] = (first term, end term, table column of the first term, -): terms count
+// from the start of `digits`, columns index the table's rows of nt records (the term itself, or with shared bases its
+// place in the segment).  A wave lies inside one slice except where two meet (SMV_DIGITS is 65, 81 or 97), so its lanes
+// run the same number of steps wherever neighbouring slices are equally long.  The addition is the complete xyzz_madd;
+// a zero digit is skipped.  sums[L] = the lane's window sum, (X, Y, ZZ, ZZZ).
+__global__ void __launch_bounds__(TPB) k_seg_accumulate(const uint32_t* __restrict__ table, size_t nt,
+                                                        const signed char* __restrict__ digits,
+                                                        const uint4* __restrict__ slices, size_t lanes,
+                                                        uint32_t* __restrict__ sums) {
+    const size_t lane = gtid();
+    if (lane >= lanes) return;
+    const size_t sl = lane / SMV_DIGITS;
+    const uint32_t w = (uint32_t)(lane - sl * SMV_DIGITS);
+    const uint4 s = slices[sl];
+    Xyzz<E> acc;
+    xyzz_set_inf(acc);
+    Aff<E> e;
+    const signed char* dp = digits + (size_t)s.x * SEG_DS + w;
+    size_t col = s.z;
+#pragma unroll 1
+    for (uint32_t t = s.x; t < s.y; ++t, ++col, dp += SEG_DS) {
+        const int d = *dp;
+        if (d) {
+            const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
+            load_aff(e, table + ((size_t)(mag - 1) * nt + col) * AFFW);
+            el_cneg(e.y, e.y, d < 0);
+            xyzz_madd(acc, e);
+        }
+    }
+    store_xyzz(sums + lane * ZZW, acc);
+}
+
+// winsum[seg * SMV_DIGITS + w] = sum over the segment's slices [seg_first[seg], seg_first[seg + 1]) of their window
+// sum w, as an engine-Jacobian record for the Horner chain; a segment without slices (an empty one) gives infinity
+__global__ void __launch_bounds__(TPB) k_seg_fold(const uint32_t* __restrict__ sums, const uint32_t* __restrict__ seg_first,
+                                                  size_t lanes, uint32_t* __restrict__ winsum) {
+    const size_t lane = gtid();
+    if (lane >= lanes) return;
+    const size_t seg = lane / SMV_DIGITS;
+    const uint32_t w = (uint32_t)(lane - seg * SMV_DIGITS);
+    Xyzz<E> acc, x;
+    xyzz_set_inf(acc);
+#pragma unroll 1
+    for (uint32_t sl = seg_first[seg]; sl < seg_first[seg + 1]; ++sl) {
+        load_xyzz(x, sums + ((size_t)sl * SMV_DIGITS + w) * ZZW);
+        xyzz_add(acc, acc, x);
+    }
+    Jac<E> r;
+    xyzz_to_jac(r, acc);
+    store_jac(winsum + lane * XYZW, r);
+}
+
+// one wave per segment: the Horner chain of k_horner over the segment's window sums, SMV_W doublings between them
+__global__ void __launch_bounds__(64) k_seg_horner(const uint32_t* __restrict__ winsum, int form, uint32_t* __restrict__ out) {
+    Jac<E> res;
+    horner_chain(res, winsum + (size_t)blockIdx.x * SMV_DIGITS * XYZW, SMV_DIGITS, SMV_W, nullptr);
+    if (threadIdx.x == 0) store_out(out + (size_t)blockIdx.x * XYZW, res, form);
+}
+
 // ---------------------------------------------------------------- launchers
 inline unsigned blocks_for(size_t n, int tpb = TPB) { return (unsigned)((n + tpb - 1) / tpb); }
 
@@ -3772,6 +3859,26 @@ void l_smv_ladder(hipStream_t st, const uint32_t* table, size_t n, const uint32_
     if (!n) return;
     hipLaunchKernelGGL(k_smv_ladder, dim3(blocks_for(n)), dim3(TPB), 0, st, table, n, scalars, mont, form, out);
 }
+void l_seg_digits(hipStream_t st, const uint32_t* scalars, size_t n, int mont, uint32_t* digits) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_seg_digits, dim3(blocks_for(n)), dim3(TPB), 0, st, scalars, n, mont, digits);
+}
+void l_seg_accumulate(hipStream_t st, const uint32_t* table, size_t nt, const uint32_t* digits, const uint32_t* slices,
+                      size_t n_slices, uint32_t* sums) {
+    if (!n_slices) return;
+    const size_t lanes = n_slices * SMV_DIGITS;
+    hipLaunchKernelGGL(k_seg_accumulate, dim3(blocks_for(lanes)), dim3(TPB), 0, st, table, nt, (const signed char*)digits,
+                       (const uint4*)slices, lanes, sums);
+}
+void l_seg_fold(hipStream_t st, const uint32_t* sums, const uint32_t* seg_first, size_t m, uint32_t* winsum) {
+    if (!m) return;
+    const size_t lanes = m * SMV_DIGITS;
+    hipLaunchKernelGGL(k_seg_fold, dim3(blocks_for(lanes)), dim3(TPB), 0, st, sums, seg_first, lanes, winsum);
+}
+void l_seg_horner(hipStream_t st, const uint32_t* winsum, size_t m, int form, uint32_t* out) {
+    if (!m) return;
+    hipLaunchKernelGGL(k_seg_horner, dim3((unsigned)m), dim3(64), 0, st, winsum, form, out);
+}
 
 const group_vtable g_vt = {
     GP::CURVE, GP::GROUP, FRW, EW, FQ::N, FR::BITS, GP::LIBFF_PROJECTIVE ? 1 : 0, (int)RED_FOLD, ZZS, FR::R,
@@ -3780,6 +3887,7 @@ const group_vtable g_vt = {
     l_gen_bases_seq, l_export_affine, l_ffi_decode_points, l_ffi_decode_scalars, l_ffi_encode_point, l_disk_decode, l_disk_decode_compressed, l_fixed_base_exp, l_field_op, l_group_op, l_digits, l_mul_bench, l_madd_bench,
     GP::HAS_ENDO ? 1 : 0, GP::COEFF_A != 0 ? 1 : 0, l_sort_sel, l_gather_scalars, l_scalar_bits, l_sort_short,
     SMV_T, l_smv_table, l_smv_ladder,
+    SMV_DIGITS, SEG_DS, l_seg_digits, l_seg_accumulate, l_seg_fold, l_seg_horner,
 };
 
 }  // namespace

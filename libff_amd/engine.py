@@ -62,7 +62,10 @@ EXPORTED_SYMBOLS = [
     "amdmsm_memcpy_h2d", "amdmsm_memcpy_d2h", "amdmsm_synchronize",
     "amdmsm_plan_short", "amdmsm_scalar_bits_device", "amdmsm_multi_exp_short", "amdmsm_msm_device_short",
     "amdmsm_scalar_mul_vec", "amdmsm_scalar_mul_vec_device",
+    "amdmsm_multi_exp_segments", "amdmsm_msm_device_segments", "amdmsm_set_segments_chunk_terms",
 ]
+SEG_SHARED_BASES = 1            # include/amdmsm.h AMDMSM_SEG_SHARED_BASES
+SEG_LONG_NEVER = 2 ** 64 - 1    # long_from = SIZE_MAX: no segment takes the single-MSM route
 # amdmsm_scalar_desc.kind: Fr records, or the width in bytes of packed little-endian unsigned integers
 SCALAR_FR, SCALAR_U8, SCALAR_U16, SCALAR_U32, SCALAR_U64 = 0, 1, 2, 4, 8
 
@@ -636,6 +639,48 @@ class Engine:
         self._check(rc, "amdmsm_scalar_mul_vec")
         return out
 
+    def multi_exp_segments(self, curve, group, bases, scalars, offsets, *, shared_bases=False, long_from=0,
+                           base_form=multi_exp_base_form_normal, out_form=OUT_LIBFF, scalars_plain=False, chunk_terms=0,
+                           stride_bytes=None, out=None):
+        """Segmented MSM (``amdmsm_multi_exp_segments``): ``out[j] = sum(scalars[i] * bases[i])`` over
+        ``offsets[j] <= i < offsets[j + 1]``, ``len(offsets) - 1`` results from one call.  ``bases``: (n, 3 * coordinate
+        limbs) libff records in ``base_form``; ``scalars``: (n_terms, fr_limbs) Montgomery residues, or with
+        ``scalars_plain`` any integers of that width; ``offsets``: non-decreasing, ``offsets[-1] <= n_terms``.
+        ``shared_bases``: term i of segment j uses ``bases[i - offsets[j]]`` (one query for every segment).  ``long_from``:
+        segments of at least this many terms take the single-MSM route (0 = the library's default, ``SEG_LONG_NEVER``).
+        ``chunk_terms``: terms worked through at a time, 0 = automatic.  ``stride_bytes``: bytes between two records of
+        ``bases`` (default: packed).  ``out``: result array to fill."""
+        s = sizes(curve, group)
+        bases = np.ascontiguousarray(bases, dtype=np.uint64)
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64)
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        m = max(int(offs.shape[0]) - 1, 0)
+        n_terms = int(scalars.shape[0])
+        gl = s["g_bytes"] // 8
+        if stride_bytes is None:
+            n_bases = int(bases.shape[0]) if bases.ndim == 2 else 0
+        else:
+            n_bases = (bases.nbytes - s["g_bytes"]) // stride_bytes + 1 if bases.nbytes >= s["g_bytes"] else 0
+        if out is None:
+            out = np.zeros((m, gl), dtype=np.uint64)
+        assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape == (m, gl)
+        if n_terms:
+            assert scalars.shape == (n_terms, s["fr_bytes"] // 8), "scalars must be (n_terms, fr_limbs) uint64"
+        o = self._opts(out_form=out_form, scalars_plain=scalars_plain)
+        self._check(self.lib.amdmsm_set_segments_chunk_terms(self.h, ctypes.c_size_t(chunk_terms)),
+                    "amdmsm_set_segments_chunk_terms")
+        try:
+            rc = self.lib.amdmsm_multi_exp_segments(
+                self.h, curve, group, _np_ptr(bases) if n_bases else None,
+                ctypes.c_size_t(s["g_bytes"] if stride_bytes is None else stride_bytes), base_form, ctypes.c_size_t(n_bases),
+                _np_ptr(scalars) if n_terms else None, ctypes.c_size_t(n_terms), _np_ptr(offs) if offs.shape[0] else None,
+                ctypes.c_size_t(m), ctypes.c_uint(SEG_SHARED_BASES if shared_bases else 0), ctypes.c_size_t(long_from),
+                _np_ptr(out) if m else None, ctypes.byref(o))
+        finally:
+            self.lib.amdmsm_set_segments_chunk_terms(self.h, ctypes.c_size_t(0))
+        self._check(rc, "amdmsm_multi_exp_segments")
+        return out
+
     def batch_exp_timings(self):
         """device times (ms) of the last batch_exp: inputs H2D, window table (0 = reused), exponentiations, results D2H"""
         ms = (ctypes.c_float * 4)()
@@ -752,6 +797,26 @@ class Engine:
         self._check(self.lib.amdmsm_scalar_mul_vec_device(self.h, curve, group, _vp(d_points_affine), _vp(d_scalars),
                                                           ctypes.c_size_t(n), _vp(d_out_xyz), ctypes.c_size_t(chunk_points),
                                                           ctypes.byref(o)), "amdmsm_scalar_mul_vec_device")
+
+    def msm_device_segments(self, curve, group, d_bases_affine, n_bases, d_scalars, n_terms, offsets, d_out, *,
+                            shared_bases=False, long_from=0, out_form=OUT_LIBFF, scalars_plain=False, chunk_terms=0,
+                            stream=None):
+        """``multi_exp_segments`` on device-resident compact affine bases and scalars (``offsets`` stays a host array);
+        ``len(offsets) - 1`` records are written to ``d_out``; enqueued on ``stream``, not synchronised."""
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        m = max(int(offs.shape[0]) - 1, 0)
+        o = self._opts(out_form=out_form, scalars_plain=scalars_plain, stream=stream)
+        self._check(self.lib.amdmsm_set_segments_chunk_terms(self.h, ctypes.c_size_t(chunk_terms)),
+                    "amdmsm_set_segments_chunk_terms")
+        try:
+            rc = self.lib.amdmsm_msm_device_segments(
+                self.h, curve, group, _vp(d_bases_affine), ctypes.c_size_t(n_bases), _vp(d_scalars), ctypes.c_size_t(n_terms),
+                _np_ptr(offs) if offs.shape[0] else None, ctypes.c_size_t(m),
+                ctypes.c_uint(SEG_SHARED_BASES if shared_bases else 0), ctypes.c_size_t(long_from), _vp(d_out),
+                ctypes.byref(o))
+        finally:
+            self.lib.amdmsm_set_segments_chunk_terms(self.h, ctypes.c_size_t(0))
+        self._check(rc, "amdmsm_msm_device_segments")
 
     def precompute_bases_device(self, curve, group, d_bases_affine, n, c, num_digits, d_table, stream=None):
         self._check(self.lib.amdmsm_precompute_bases_device(
