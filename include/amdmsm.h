@@ -478,6 +478,24 @@ int amdmsm_field_op_device(amdmsm_ctx *ctx, int curve, int group, int op, const 
                            const void *d_b, void *d_out, size_t n);
 int amdmsm_group_op_device(amdmsm_ctx *ctx, int curve, int group, int op, const void *d_a,
                            const void *d_b, void *d_out, size_t n, int out_form);
+/* One coordinate-field function per element, on the element type of the cold kernels (impl 0) or the
+ * fully inlined one (impl 1).  Operands and result are arrays of n elements of el_words 32-bit words,
+ * taken and stored as they are; d_b, d_c, d_d are null where the op takes fewer operands.  d_flag (may be
+ * null): one word per element, the boolean the op returns, else 0.
+ * Canonical ops, operands in [0, p) per component: 0 mul, 1 sqr, 2 add, 3 sub, 4 neg, 5 inverse, 6 double,
+ * 7 conditional negate (where the low bit of b's first word is set), 8 half, 9 to Montgomery form,
+ * 10 from Montgomery form, 11 square root (flag: a is a square; either root).
+ * Almost-reduced ops, operands in [0, 2p) per component, results below 2p: 16 mul, 17 sqr, 18 sub,
+ * 19 add, 20 neg, 21 a b - c d, 22 is zero (flag), 23 canonical representative. */
+int amdmsm_field_probe_device(amdmsm_ctx *ctx, int curve, int group, int impl, int op, const void *d_a,
+                              const void *d_b, const void *d_c, const void *d_d, void *d_out,
+                              uint32_t *d_flag, size_t n);
+/* One extended-Jacobian (X, Y, ZZ, ZZZ) function per lane, impl as above: 0 mixed addition on
+ * almost-reduced coordinates, 1 mixed addition, 2 addition, 3 doubling, 4 doubling of an affine point,
+ * 5 conversion to Jacobian (X, Y, Z, then zeros).  d_acc and d_out: n records of 4 * el_words words;
+ * d_pt: n compact affine records (ops 0, 1, 4) or n more (X, Y, ZZ, ZZZ) records (op 2), else null. */
+int amdmsm_xyzz_probe_device(amdmsm_ctx *ctx, int curve, int group, int impl, int op, const void *d_acc,
+                             const void *d_pt, void *d_out, size_t n);
 int amdmsm_digits_device(amdmsm_ctx *ctx, int curve, int group, const void *d_scalars, size_t n,
                          int scalars_plain, int c, int num_windows, int32_t *d_out);
 /* throughput probes (2*iters dependent Fq products / iters mixed additions per lane);

@@ -1513,6 +1513,36 @@ int amdmsm_field_op_device(amdmsm_ctx *ctx, int curve, int group, int op, const 
     return AMDMSM_OK;
 }
 
+int amdmsm_field_probe_device(amdmsm_ctx *ctx, int curve, int group, int impl, int op, const void *d_a, const void *d_b,
+                              const void *d_c, const void *d_d, void *d_out, uint32_t *d_flag, size_t n) {
+    GET_VT(ctx, curve, group);
+    if ((impl != 0 && impl != 1) || !d_a || !d_out) return fail(ctx, AMDMSM_ERR_BAD_ARG, "impl / operands");
+    const bool known = (op >= FPROBE_MUL && op <= FPROBE_SQRT) || (op >= FPROBE_MUL_LZ && op <= FPROBE_CANON);
+    if (!known) return fail(ctx, AMDMSM_ERR_BAD_ARG, "op");
+    const int arity = op == FPROBE_MUL_SUB_MUL_LZ ? 4
+                      : (op == FPROBE_MUL || op == FPROBE_ADD || op == FPROBE_SUB || op == FPROBE_CNEG || op == FPROBE_MUL_LZ ||
+                         op == FPROBE_SUB_LZ || op == FPROBE_ADD_LZ) ? 2 : 1;
+    if ((arity >= 2 && !d_b) || (arity == 4 && (!d_c || !d_d))) return fail(ctx, AMDMSM_ERR_BAD_ARG, "missing operand");
+    vt->field_probe(ctx->stream, impl, op, (const uint32_t *)d_a, (const uint32_t *)d_b, (const uint32_t *)d_c,
+                    (const uint32_t *)d_d, (uint32_t *)d_out, d_flag, n);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return AMDMSM_OK;
+}
+
+int amdmsm_xyzz_probe_device(amdmsm_ctx *ctx, int curve, int group, int impl, int op, const void *d_acc, const void *d_pt,
+                             void *d_out, size_t n) {
+    GET_VT(ctx, curve, group);
+    if ((impl != 0 && impl != 1) || !d_acc || !d_out || op < XPROBE_MADD_LZ || op > XPROBE_TO_JAC)
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "impl / op / operands");
+    const bool needs_pt = op == XPROBE_MADD_LZ || op == XPROBE_MADD || op == XPROBE_ADD || op == XPROBE_DBL_AFFINE;
+    if (needs_pt && !d_pt) return fail(ctx, AMDMSM_ERR_BAD_ARG, "missing operand");
+    vt->xyzz_probe(ctx->stream, impl, op, (const uint32_t *)d_acc, (const uint32_t *)d_pt, (uint32_t *)d_out, n);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return AMDMSM_OK;
+}
+
 int amdmsm_group_op_device(amdmsm_ctx *ctx, int curve, int group, int op, const void *d_a, const void *d_b,
                            void *d_out, size_t n, int out_form) {
     GET_VT(ctx, curve, group);

@@ -247,7 +247,31 @@ struct group_vtable {
                            size_t n_slices, uint32_t* sums);
     void (*seg_fold)(hipStream_t, const uint32_t* sums, const uint32_t* seg_first, size_t m, uint32_t* winsum);
     void (*seg_horner)(hipStream_t, const uint32_t* winsum, size_t m, int form, uint32_t* out);
+
+    // ---- probes of the field and point layers (tests/test_gpu_field_probe.py) ----------
+    // One library function (FPROBE_*) per element on the cold element type (impl 0) or the fully inlined one (impl 1):
+    // operands a, b, c, d (null where the op takes fewer) and out are n elements of el_words words, taken and stored as
+    // they are; flag (may be null): one word per element, the boolean the op returns (else 0).
+    void (*field_probe)(hipStream_t, int impl, int op, const uint32_t* a, const uint32_t* b, const uint32_t* c,
+                        const uint32_t* d, uint32_t* out, uint32_t* flag, size_t n);
+    // One extended-Jacobian function (XPROBE_*) per lane: acc and out are n (X, Y, ZZ, ZZZ) records of 4 * el_words
+    // words; pt: n compact affine records, or n more (X, Y, ZZ, ZZZ) records for XPROBE_ADD (null where unused)
+    void (*xyzz_probe)(hipStream_t, int impl, int op, const uint32_t* acc, const uint32_t* pt, uint32_t* out, size_t n);
 };
+
+// op codes of field_probe: canonical operands in [0, p) per component ...
+enum {
+    FPROBE_MUL = 0, FPROBE_SQR = 1, FPROBE_ADD = 2, FPROBE_SUB = 3, FPROBE_NEG = 4, FPROBE_INV = 5, FPROBE_DBL = 6,
+    FPROBE_CNEG = 7,       // negates where the low bit of b's first word is set
+    FPROBE_HALF = 8, FPROBE_TO_MONT = 9, FPROBE_FROM_MONT = 10,
+    FPROBE_SQRT = 11,      // flag: a is a square (out: either root)
+    // ... and the almost-reduced set: operands in [0, 2p) per component, results below 2p
+    FPROBE_MUL_LZ = 16, FPROBE_SQR_LZ = 17, FPROBE_SUB_LZ = 18, FPROBE_ADD_LZ = 19, FPROBE_NEG_LZ = 20,
+    FPROBE_MUL_SUB_MUL_LZ = 21,   // a b - c d
+    FPROBE_IS_ZERO_LZ = 22,       // flag
+    FPROBE_CANON = 23,
+};
+enum { XPROBE_MADD_LZ = 0, XPROBE_MADD = 1, XPROBE_ADD = 2, XPROBE_DBL = 3, XPROBE_DBL_AFFINE = 4, XPROBE_TO_JAC = 5 };
 
 const group_vtable* vt_alt_bn128_g1() __attribute__((weak));
 const group_vtable* vt_alt_bn128_g2() __attribute__((weak));

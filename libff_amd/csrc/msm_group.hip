@@ -3137,6 +3137,118 @@ __global__ void __launch_bounds__(TPB) k_group_op(int op, const uint32_t* __rest
     store_out(out + i * XYZW, r, form);
 }
 
+// Field-layer probe (group_vtable::field_probe): one lane per element, one library function per op code, on the
+// element type T = E or EI.  The operands are taken as they are stored -- the almost-reduced ops get words in [0, 2p)
+// per component -- and the result is stored as the function left it (no canonicalisation), so a test sees which
+// representative came back.  Functions that exist per Fq component only run on each component of an Fq2 element.
+template <class P, bool I, class F> AMDMSM_DEV void probe_comp1(Fp<P, I>& r, const Fp<P, I>& a, F f) { f(r, a); }
+template <class P, int NR, bool I, class F> AMDMSM_DEV void probe_comp1(Fp2<P, NR, I>& r, const Fp2<P, NR, I>& a, F f) {
+    f(r.c0, a.c0);
+    f(r.c1, a.c1);
+}
+template <class P, bool I, class F> AMDMSM_DEV void probe_comp2(Fp<P, I>& r, const Fp<P, I>& a, const Fp<P, I>& b, F f) { f(r, a, b); }
+template <class P, int NR, bool I, class F>
+AMDMSM_DEV void probe_comp2(Fp2<P, NR, I>& r, const Fp2<P, NR, I>& a, const Fp2<P, NR, I>& b, F f) {
+    f(r.c0, a.c0, b.c0);
+    f(r.c1, a.c1, b.c1);
+}
+template <class T>
+__global__ void __launch_bounds__(TPB) k_field_probe(int op, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                     const uint32_t* __restrict__ c, const uint32_t* __restrict__ d,
+                                                     uint32_t* __restrict__ out, uint32_t* __restrict__ flag, size_t n) {
+    using FC = Fp<FQ, std::is_same<T, EI>::value>;   // component type of T
+    const size_t i = gtid();
+    if (i >= n) return;
+    T x, y, z, w, r;
+    el_load(x, a + i * EW);
+    if (b) el_load(y, b + i * EW); else el_zero(y);
+    if (c) el_load(z, c + i * EW); else el_zero(z);
+    if (d) el_load(w, d + i * EW); else el_zero(w);
+    uint32_t f = 0;
+    switch (op) {
+    case FPROBE_MUL: el_mul(r, x, y); break;
+    case FPROBE_SQR: el_sqr(r, x); break;
+    case FPROBE_ADD: el_add(r, x, y); break;
+    case FPROBE_SUB: el_sub(r, x, y); break;
+    case FPROBE_NEG: el_neg(r, x); break;
+    case FPROBE_INV: el_inv(r, x); break;
+    case FPROBE_DBL: el_dbl(r, x); break;
+    case FPROBE_CNEG: el_cneg(r, x, b && (b[i * EW] & 1u)); break;   // sense: low bit of b's first word
+    case FPROBE_HALF: probe_comp1(r, x, [](FC& o, const FC& v) { fp_half(o, v); }); break;
+    case FPROBE_TO_MONT: el_to_mont(r, x); break;
+    case FPROBE_FROM_MONT: el_from_mont(r, x); break;
+    case FPROBE_SQRT:
+        el_zero(r);
+        f = el_sqrt(r, x) ? 1u : 0u;
+        break;
+    case FPROBE_MUL_LZ: el_mul_lz(r, x, y); break;
+    case FPROBE_SQR_LZ: el_sqr_lz(r, x); break;
+    case FPROBE_SUB_LZ: el_sub_lz(r, x, y); break;
+    case FPROBE_ADD_LZ: probe_comp2(r, x, y, [](FC& o, const FC& u, const FC& v) { fp_add_lz(o, u, v); }); break;
+    case FPROBE_NEG_LZ: probe_comp1(r, x, [](FC& o, const FC& v) { fp_neg_lz(o, v); }); break;
+    case FPROBE_MUL_SUB_MUL_LZ: el_mul_sub_mul_lz(r, x, y, z, w); break;
+    case FPROBE_IS_ZERO_LZ:
+        r = x;
+        f = el_is_zero_lz(x) ? 1u : 0u;
+        break;
+    case FPROBE_CANON:
+        r = x;
+        el_canon(r);
+        break;
+    default: el_zero(r); break;
+    }
+    el_store(out + i * EW, r);
+    if (flag) flag[i] = f;
+}
+
+// Point-level probe (group_vtable::xyzz_probe) of the extended-Jacobian functions of ec.cuh on T = E or EI.  acc: n
+// (X, Y, ZZ, ZZZ) records of ZZW words taken as stored (xyzz_madd_lz: any representative in [0, 2p) per component); pt: n
+// compact affine records (the mixed additions and xyzz_dbl_affine) or n more (X, Y, ZZ, ZZZ) records (xyzz_add); out: n
+// records of ZZW words, stored as the function left them (xyzz_to_jac: X, Y, Z and ZZW - XYZW words of zero).
+template <class T>
+__global__ void __launch_bounds__(TPB) k_xyzz_probe(int op, const uint32_t* __restrict__ acc, const uint32_t* __restrict__ pt,
+                                                    uint32_t* __restrict__ out, size_t n) {
+    const size_t i = gtid();
+    if (i >= n) return;
+    Xyzz<T> a, r;
+    Aff<T> p;
+    load_xyzz(a, acc + i * ZZW);
+    switch (op) {
+    case XPROBE_MADD_LZ:
+        load_aff(p, pt + i * AFFW);
+        xyzz_madd_lz(a, p);
+        r = a;
+        break;
+    case XPROBE_MADD:
+        load_aff(p, pt + i * AFFW);
+        xyzz_madd(a, p);
+        r = a;
+        break;
+    case XPROBE_ADD: {
+        Xyzz<T> q;
+        load_xyzz(q, pt + i * ZZW);
+        xyzz_add(r, a, q);
+        break;
+    }
+    case XPROBE_DBL: xyzz_dbl(r, a); break;
+    case XPROBE_DBL_AFFINE:
+        load_aff(p, pt + i * AFFW);
+        xyzz_dbl_affine(r, p);
+        break;
+    case XPROBE_TO_JAC: {
+        Jac<T> j;
+        xyzz_to_jac(j, a);
+        r.x = j.x;
+        r.y = j.y;
+        r.zz = j.z;
+        el_zero(r.zzz);
+        break;
+    }
+    default: xyzz_set_inf(r); break;
+    }
+    store_xyzz(out + i * ZZW, r);
+}
+
 // Throughput probes: a dependent chain of Montgomery products / mixed additions per lane,
 // operands in registers, no memory traffic inside the loop.
 template <bool I>
@@ -3819,6 +3931,17 @@ void l_field_op(hipStream_t st, int op, const uint32_t* a, const uint32_t* b, ui
     if (!n) return;
     hipLaunchKernelGGL(k_field_op, dim3(blocks_for(n)), dim3(TPB), 0, st, op, a, b, out, n);
 }
+void l_field_probe(hipStream_t st, int impl, int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d,
+                   uint32_t* out, uint32_t* flag, size_t n) {
+    if (!n) return;
+    if (impl) hipLaunchKernelGGL(k_field_probe<EI>, dim3(blocks_for(n)), dim3(TPB), 0, st, op, a, b, c, d, out, flag, n);
+    else hipLaunchKernelGGL(k_field_probe<E>, dim3(blocks_for(n)), dim3(TPB), 0, st, op, a, b, c, d, out, flag, n);
+}
+void l_xyzz_probe(hipStream_t st, int impl, int op, const uint32_t* acc, const uint32_t* pt, uint32_t* out, size_t n) {
+    if (!n) return;
+    if (impl) hipLaunchKernelGGL(k_xyzz_probe<EI>, dim3(blocks_for(n)), dim3(TPB), 0, st, op, acc, pt, out, n);
+    else hipLaunchKernelGGL(k_xyzz_probe<E>, dim3(blocks_for(n)), dim3(TPB), 0, st, op, acc, pt, out, n);
+}
 void l_group_op(hipStream_t st, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n, int form) {
     if (!n) return;
     hipLaunchKernelGGL(k_group_op, dim3(blocks_for(n)), dim3(TPB), 0, st, op, a, b, out, n, form);
@@ -3888,6 +4011,7 @@ const group_vtable g_vt = {
     GP::HAS_ENDO ? 1 : 0, GP::COEFF_A != 0 ? 1 : 0, l_sort_sel, l_gather_scalars, l_scalar_bits, l_sort_short,
     SMV_T, l_smv_table, l_smv_ladder,
     SMV_DIGITS, SEG_DS, l_seg_digits, l_seg_accumulate, l_seg_fold, l_seg_horner,
+    l_field_probe, l_xyzz_probe,
 };
 
 }  // namespace

@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = [
     "amdmsm_set_timing", "amdmsm_get_timings", "amdmsm_last_timing_ticket", "amdmsm_get_timings_by_ticket",
     "amdmsm_set_pipeline_depth", "amdmsm_last_slot",
     "amdmsm_get_slot_timings", "amdmsm_field_op_device", "amdmsm_group_op_device",
+    "amdmsm_field_probe_device", "amdmsm_xyzz_probe_device",
     "amdmsm_digits_device", "amdmsm_mul_bench_device", "amdmsm_madd_bench_device", "amdmsm_malloc", "amdmsm_free",
     "amdmsm_memcpy_h2d", "amdmsm_memcpy_d2h", "amdmsm_synchronize",
     "amdmsm_plan_short", "amdmsm_scalar_bits_device", "amdmsm_multi_exp_short", "amdmsm_msm_device_short",
@@ -892,6 +893,46 @@ class Engine:
             self.d2h(out, po)
         finally:
             for p in (pa, pb, po):
+                if p is not None:
+                    self.free(p)
+        return out
+
+    def field_probe(self, curve, group, impl, op, a, b=None, c=None, d=None):
+        """one coordinate-field function per element (op: include/amdmsm.h amdmsm_field_probe_device) on the cold
+        (impl 0) or the fully inlined (impl 1) element type; operands and result as stored words.  Returns (out, flag)."""
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        rest = [np.ascontiguousarray(x, dtype=np.uint64) if x is not None else None for x in (b, c, d)]
+        if any(x is not None and x.shape != a.shape for x in rest):
+            raise ValueError("operand arrays must have one shape")
+        out = np.zeros_like(a)
+        flag = np.zeros(a.shape[0], dtype=np.uint32)
+        ptrs = self._dev_arrays(a, *rest, out, flag)
+        try:
+            self._check(self.lib.amdmsm_field_probe_device(self.h, curve, group, int(impl), int(op), *ptrs,
+                                                           ctypes.c_size_t(a.shape[0])), "amdmsm_field_probe_device")
+            self.d2h(out, ptrs[4])
+            self.d2h(flag, ptrs[5])
+        finally:
+            for p in ptrs:
+                if p is not None:
+                    self.free(p)
+        return out, flag
+
+    def xyzz_probe(self, curve, group, impl, op, acc, pt=None):
+        """one extended-Jacobian function per lane (op: include/amdmsm.h amdmsm_xyzz_probe_device); acc and the
+        result are (n, 4 * coordinate words) arrays of (X, Y, ZZ, ZZZ) as stored words"""
+        acc = np.ascontiguousarray(acc, dtype=np.uint64)
+        pt = np.ascontiguousarray(pt, dtype=np.uint64) if pt is not None else None
+        if pt is not None and pt.shape[0] != acc.shape[0]:
+            raise ValueError("operand arrays must have one length")
+        out = np.zeros_like(acc)
+        ptrs = self._dev_arrays(acc, pt, out)
+        try:
+            self._check(self.lib.amdmsm_xyzz_probe_device(self.h, curve, group, int(impl), int(op), *ptrs,
+                                                          ctypes.c_size_t(acc.shape[0])), "amdmsm_xyzz_probe_device")
+            self.d2h(out, ptrs[2])
+        finally:
+            for p in ptrs:
                 if p is not None:
                     self.free(p)
         return out
