@@ -140,6 +140,13 @@ int amdmsm_plan_ex(int curve, int group, size_t n, int window_bits, int endomorp
    one piece (longer bins go chunk by chunk), out[4] = entries above which a coarse bin is spread over the whole grid */
 int amdmsm_plan_sort(int curve, int group, size_t n, int window_bits, int endomorphism, size_t out[5]);
 
+/* read-only: the top window of that plan, scalars_plain as in amdmsm_opts.  out[0] = tb, the bits its bucket index
+   |digit| - 1 can have -- a bound that holds for every admitted input, never taken from the data: the split's constants,
+   or the scalar field's bit length for Montgomery scalars, or the word length for plain ones without the split (k >= r
+   is valid input there) -- out[1] = fine bits the sort drops for that window (0 with AMDMSM_SORT_TOPSHIFT=0),
+   out[2] = c, out[3] = windows */
+int amdmsm_plan_top_window(int curve, int group, size_t n, int window_bits, int endomorphism, int scalars_plain, int out[4]);
+
 /* libff's own window heuristics, kept for API parity (multiexp.hpp:53-57) */
 size_t amdmsm_pippenger_optimal_c(size_t num_elements);
 size_t amdmsm_bdlo12_signed_optimal_c(size_t num_elements);

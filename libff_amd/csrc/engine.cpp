@@ -1222,6 +1222,28 @@ int amdmsm_plan_sort(int curve, int group, size_t n, int window_bits, int endomo
     return AMDMSM_OK;
 }
 
+int amdmsm_plan_top_window(int curve, int group, size_t n, int window_bits, int endomorphism, int scalars_plain, int out[4]) {
+    const group_vtable *vt = find_vt(curve, group);
+    if (!vt || !out) return AMDMSM_ERR_UNSUPPORTED;
+    amdmsm_opts o = AMDMSM_OPTS_INIT;
+    o.window_bits = window_bits;
+    o.endomorphism = endomorphism;
+    const bool glv = use_endomorphism(vt, n, &o, 0);
+    plan_req req;
+    req.entries = glv ? 2 * n : n;
+    req.c = window_bits;
+    req.glv = glv;
+    plan_t p;
+    const int rc = make_plan(vt, req, p);
+    if (rc) return rc;
+    if (p.c > 22) return AMDMSM_ERR_UNSUPPORTED;
+    // the sort launcher's own value (msm_group.hip sort_launch asks the same function)
+    out[1] = vt->sort_top_window(glv ? 2 : 0, scalars_plain ? 0 : 1, p.c, p.W, glv ? 2 * n : n, &out[0]);
+    out[2] = p.c;
+    out[3] = p.W;
+    return AMDMSM_OK;
+}
+
 int amdmsm_plan(int curve, int group, size_t n, int window_bits, int *c, int *num_windows, uint32_t *num_buckets,
                 size_t *workspace_bytes) {
     return amdmsm_plan_ex(curve, group, n, window_bits, 0, c, num_windows, num_buckets, workspace_bytes, nullptr);

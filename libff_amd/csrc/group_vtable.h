@@ -56,6 +56,31 @@ inline sort_geom sort_geometry(size_t n, int c, int W) {
     return g;
 }
 
+// The top window is short: its bucket index |digit| - 1 stays below 2^tb, a property of the plan and not of the data.
+// bound_log2_x1000 > 0 (endomorphism split): every half scalar is at most 2^(bound_log2_x1000 / 1000), so its top
+// window holds at most floor(2^e), e = bound - c (W - 1) bits, before the recoding carry of 1 -- an index of at most
+// floor(2^e) < 2^(floor(e) + 1).  Else the scalars are below 2^bits: the top window holds at most 2^(bits - c (W - 1)) - 1,
+// and with the carry the index stays below that power of two.  A window above the scalar sees the carry alone (index 0).
+inline int top_window_bits(int bound_log2_x1000, int bits, int c, int W) {
+    int tb;
+    if (bound_log2_x1000 > 0) {
+        const long e = (long)bound_log2_x1000 - 1000L * c * (W - 1);
+        tb = e < 0 ? 0 : (int)(e / 1000) + 1;
+    } else {
+        tb = bits - c * (W - 1);
+    }
+    return tb < 0 ? 0 : tb > c - 1 ? c - 1 : tb;
+}
+// The two-level sort of that window drops delta = min(fb, (c - 1) - tb) of its fine bits: coarse bin = index >> (fb -
+// delta), so that the 2^hb bins of the window are cut by the bits it really has and fill evenly, each with 2^(fb - delta)
+// fine buckets.  The bucket index itself is unchanged.  AMDMSM_SORT_TOPSHIFT=0: no shift (A/B runs).
+inline int sort_top_shift(int tb, int c, int W, int fb) {
+    static const bool on = !(getenv("AMDMSM_SORT_TOPSHIFT") && atoi(getenv("AMDMSM_SORT_TOPSHIFT")) == 0);
+    if (!on || W < 2) return 0;
+    const int spare = c - 1 - tb;
+    return spare < fb ? spare : fb;
+}
+
 // Queues of buckets whose entries span several accumulation lanes (k_accumulate_fixup):
 // spans of more than 32 lanes ("long") and of 3..32 lanes ("mid"), `lanes` = W * T.
 #ifdef __HIPCC__
@@ -257,6 +282,14 @@ struct group_vtable {
     // One extended-Jacobian function (XPROBE_*) per lane: acc and out are n (X, Y, ZZ, ZZZ) records of 4 * el_words
     // words; pt: n compact affine records, or n more (X, Y, ZZ, ZZZ) records for XPROBE_ADD (null where unused)
     void (*xyzz_probe)(hipStream_t, int impl, int op, const uint32_t* acc, const uint32_t* pt, uint32_t* out, size_t n);
+
+    // The top window of the sort that `sort` / `sort_sel` run for (mode, mont, c, W) over `columns` digit columns per
+    // window: returns the fine bits dropped there (sort_top_shift) -- the very value the launcher passes to its kernels --
+    // and, in *tb (may be null), the bound on that window's index bits it rests on.  The bound covers every input the
+    // entry points admit: the halves of the split obey theirs for any scalar of fr_words words; Montgomery scalars come
+    // out of the conversion below r; plain scalars without the split may be any integer of fr_words words (k >= r is
+    // documented input), so there only the word length bounds the top window.
+    int (*sort_top_window)(int mode, int mont, int c, int W, size_t columns, int* tb);
 };
 
 // op codes of field_probe: canonical operands in [0, p) per component ...

@@ -274,58 +274,76 @@ using GLV = typename GP::glv;
 constexpr int GLV_HW = GLV::HW;       // limbs of |k1|, |k2|
 constexpr int GLV_HC = GLV::HW + 1;   // working width: two's complement with room for the sign
 
-// 96-bit column accumulator for the schoolbook products below: acc += a * b is one v_mad_u64_u32
-// plus the carry into the top word
-struct glv_acc {
-    uint64_t lo;
-    uint32_t hi;
-};
-AMDMSM_DEV void glv_mac(glv_acc& s, uint32_t a, uint32_t b) {
-    const uint64_t t = (uint64_t)a * b + s.lo;
-    s.hi += t < s.lo ? 1u : 0u;
-    s.lo = t;
+// The schoolbook products below gather one 32-bit column at a time in a 96-bit accumulator (lo: 64, hi: 32) on the
+// carry chains of fp.cuh (mac_chain.inc): one v_mad_u64_u32 and one carry add per product, the per-lane operand in a
+// VGPR and the constant limb in an SGPR.  The constants are picked at compile time -- SEL 0 / 1: G1 / G2, 2 .. 5:
+// M[0] .. M[3] -- and their zero top limbs are left out of the chains.
+template <int SEL>
+constexpr uint32_t glv_const(int j) {
+    return SEL == 0 ? GLV::G1[j] : SEL == 1 ? GLV::G2[j] : GLV::M[SEL - 2][j];
 }
-AMDMSM_DEV void glv_add(glv_acc& s, uint32_t v) {
-    const uint64_t t = s.lo + v;
-    s.hi += t < s.lo ? 1u : 0u;
-    s.lo = t;
-}
-AMDMSM_DEV uint32_t glv_next_column(glv_acc& s) {   // emit the low word, shift down by one word
-    const uint32_t w = (uint32_t)s.lo;
-    s.lo = (s.lo >> 32) | ((uint64_t)s.hi << 32);
-    s.hi = 0;
+template <int SEL>
+constexpr int glv_const_width() {   // limbs up to the highest nonzero one
+    int w = 0;
+    for (int j = 0; j < (SEL < 2 ? GLV::GW : GLV_HC); ++j)
+        if (glv_const<SEL>(j) != 0) w = j + 1;
     return w;
 }
-// low GLV_HC limbs of (k G + 2^(s-1)) >> s, s = 32 (FRW + 1): Babai rounding of k b / r
-AMDMSM_DEV void glv_round_mul(uint32_t (&c)[GLV_HC], const uint32_t (&k)[FRW], const uint32_t (&G)[GLV::GW]) {
-    glv_acc s{0, 0};
-#pragma unroll
-    for (int col = 0; col < FRW + 1 + GLV_HC; ++col) {
-        if (col == FRW) glv_add(s, 0x80000000u);
-#pragma unroll
-        for (int i = 0; i < FRW; ++i) {
-            const int j = col - i;
-            if (j >= 0 && j < GLV::GW) glv_mac(s, k[i], G[j]);
-        }
-        const uint32_t w = glv_next_column(s);
-        if (col >= FRW + 1) c[col - FRW - 1] = w;
+// acc += sum_{i in [I0, I0 + CNT)} a[i] * const[K - i]
+template <int SEL, int K, int I0, size_t... J>
+AMDMSM_DEV void glv_mac_col(uint64_t& lo, uint32_t& hi, const uint32_t* a, std::index_sequence<J...>) {
+    mac_chain<(int)sizeof...(J)>::vs(lo, hi, a[I0 + (int)J]...,
+                                     std::integral_constant<uint32_t, glv_const<SEL>(K - I0 - (int)J)>::value...);
+}
+// i runs over [LO, HI) cut to the limbs the constant has: chunks of at most MAC_CHUNK products
+template <int SEL, int K, int LO, int HI>
+AMDMSM_DEV void glv_mac_range(uint64_t& lo, uint32_t& hi, const uint32_t* a) {
+    constexpr int L = K - glv_const_width<SEL>() + 1 > LO ? K - glv_const_width<SEL>() + 1 : LO;
+    if constexpr (L < HI) {
+        constexpr int CNT = (HI - L) < MAC_CHUNK ? (HI - L) : MAC_CHUNK;
+        glv_mac_col<SEL, K, L>(lo, hi, a, std::make_index_sequence<CNT>{});
+        glv_mac_range<SEL, K, L + CNT, HI>(lo, hi, a);
     }
 }
-// t = k (if ADD_K) + c1 * A + c2 * B  mod 2^(32 GLV_HC)
-template <bool ADD_K>
+AMDMSM_DEV uint32_t glv_next_column(uint64_t& lo, uint32_t& hi) {   // emit the low word, shift down by one word
+    const uint32_t w = (uint32_t)lo;
+    lo = (lo >> 32) | ((uint64_t)hi << 32);
+    hi = 0;
+    return w;
+}
+// (A 32-bit word added at the start of a column needs no carry: the accumulator is then the shifted-down rest of the
+// column before, whose top word counted that column's carries -- far below 2^63.)
+// low GLV_HC limbs of (k G + 2^(s-1)) >> s, s = 32 (FRW + 1): Babai rounding of k b / r
+template <int SEL, int COL>
+AMDMSM_DEV void glv_round_col(uint64_t& lo, uint32_t& hi, uint32_t (&c)[GLV_HC], const uint32_t* k) {
+    if constexpr (COL == FRW) lo += 0x80000000u;
+    glv_mac_range<SEL, COL, 0, (COL < FRW ? COL + 1 : FRW)>(lo, hi, k);
+    const uint32_t w = glv_next_column(lo, hi);
+    if constexpr (COL >= FRW + 1) c[COL - FRW - 1] = w;
+    if constexpr (COL + 1 < FRW + 1 + GLV_HC) glv_round_col<SEL, COL + 1>(lo, hi, c, k);
+}
+template <int SEL>
+AMDMSM_DEV void glv_round_mul(uint32_t (&c)[GLV_HC], const uint32_t (&k)[FRW]) {
+    uint64_t lo = 0;
+    uint32_t hi = 0;
+    glv_round_col<SEL, 0>(lo, hi, c, k);
+}
+// t = k (if ADD_K) + c1 * A + c2 * B  mod 2^(32 GLV_HC), A = M[SA], B = M[SA + 1]
+template <bool ADD_K, int SA, int COL>
+AMDMSM_DEV void glv_combine_col(uint64_t& lo, uint32_t& hi, uint32_t (&t)[GLV_HC], const uint32_t (&k)[FRW], const uint32_t* c1,
+                                const uint32_t* c2) {
+    if constexpr (ADD_K && COL < FRW) lo += k[COL];
+    glv_mac_range<2 + SA, COL, 0, COL + 1>(lo, hi, c1);
+    glv_mac_range<3 + SA, COL, 0, COL + 1>(lo, hi, c2);
+    t[COL] = glv_next_column(lo, hi);
+    if constexpr (COL + 1 < GLV_HC) glv_combine_col<ADD_K, SA, COL + 1>(lo, hi, t, k, c1, c2);
+}
+template <bool ADD_K, int SA>
 AMDMSM_DEV void glv_combine(uint32_t (&t)[GLV_HC], const uint32_t (&k)[FRW], const uint32_t (&c1)[GLV_HC],
-                            const uint32_t (&A)[GLV_HC], const uint32_t (&c2)[GLV_HC], const uint32_t (&B)[GLV_HC]) {
-    glv_acc s{0, 0};
-#pragma unroll
-    for (int col = 0; col < GLV_HC; ++col) {
-        if (ADD_K && col < FRW) glv_add(s, k[col]);
-#pragma unroll
-        for (int i = 0; i <= col; ++i) {
-            glv_mac(s, c1[i], A[col - i]);
-            glv_mac(s, c2[i], B[col - i]);
-        }
-        t[col] = glv_next_column(s);
-    }
+                            const uint32_t (&c2)[GLV_HC]) {
+    uint64_t lo = 0;
+    uint32_t hi = 0;
+    glv_combine_col<ADD_K, SA, 0>(lo, hi, t, k, c1, c2);
 }
 // two's complement t -> (|t|, sign)
 AMDMSM_DEV bool glv_magnitude(uint32_t (&m)[GLV_HW], const uint32_t (&t)[GLV_HC]) {
@@ -341,11 +359,11 @@ AMDMSM_DEV bool glv_magnitude(uint32_t (&m)[GLV_HW], const uint32_t (&t)[GLV_HC]
 }
 AMDMSM_DEV void glv_split(const uint32_t (&k)[FRW], uint32_t (&m1)[GLV_HW], bool& neg1, uint32_t (&m2)[GLV_HW], bool& neg2) {
     uint32_t c1[GLV_HC], c2[GLV_HC], t[GLV_HC];
-    glv_round_mul(c1, k, GLV::G1);
-    glv_round_mul(c2, k, GLV::G2);
-    glv_combine<true>(t, k, c1, GLV::M[0], c2, GLV::M[1]);
+    glv_round_mul<0>(c1, k);
+    glv_round_mul<1>(c2, k);
+    glv_combine<true, 0>(t, k, c1, c2);
     neg1 = glv_magnitude(m1, t);
-    glv_combine<false>(t, k, c1, GLV::M[2], c2, GLV::M[3]);
+    glv_combine<false, 2>(t, k, c1, c2);
     neg2 = glv_magnitude(m2, t);
 }
 // the two halves of scalar i, recoded: emit(half, w, d) -- half 0 belongs to P_i, half 1 to phi(P_i)
@@ -616,7 +634,8 @@ AMDMSM_DEV uint32_t block_exclusive_scan(const uint32_t* cnt, uint32_t* out, uin
 
 __global__ void __launch_bounds__(SORT_TPB) k_sort_digits(const uint32_t* __restrict__ scalars, size_t n, int mont, int c,
                                                           int W, int hb, uint32_t per_block, int32_t* __restrict__ digits,
-                                                          size_t stride, uint32_t* __restrict__ coarse_counts, int mode) {
+                                                          size_t stride, uint32_t* __restrict__ coarse_counts, int mode,
+                                                          int dtop) {
     // mode 1 (flat): the W digits of scalar i are entries i*W .. i*W+W-1 of ONE list (they index a
     // table of precomputed multiples [2^(jc)]P_i and share a single bucket set)
     // mode 2 (endomorphism): scalar i gives two columns of W digits, i (k1, for P_i) and n + i
@@ -624,7 +643,7 @@ __global__ void __launch_bounds__(SORT_TPB) k_sort_digits(const uint32_t* __rest
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];   // [W][2^hb]   (flat: [2^hb])
     const bool flat = mode == 1;
     const uint32_t nbin = 1u << hb;
-    const int fb = c - 1 - hb;
+    const int fb = c - 1 - hb, fbt = fb - dtop;   // fine bits; those of the top window (sort_top_shift; dtop = 0 when flat)
     const uint32_t nctr = flat ? nbin : (uint32_t)W * nbin;
     for (uint32_t j = threadIdx.x; j < nctr; j += SORT_TPB) smem[j] = 0;
     __syncthreads();
@@ -639,7 +658,7 @@ __global__ void __launch_bounds__(SORT_TPB) k_sort_digits(const uint32_t* __rest
                 digits[(size_t)w * stride + (h ? n + i : i)] = d;
                 if (d != 0) {
                     const uint32_t idx = (uint32_t)(d < 0 ? -d : d) - 1u;
-                    atomicAdd(&smem[(uint32_t)w * nbin + (idx >> fb)], 1u);
+                    atomicAdd(&smem[(uint32_t)w * nbin + (idx >> (w == W - 1 ? fbt : fb))], 1u);
                 }
             });
         } else {
@@ -647,7 +666,7 @@ __global__ void __launch_bounds__(SORT_TPB) k_sort_digits(const uint32_t* __rest
                 digits[flat ? i * (size_t)W + w : (size_t)w * stride + i] = d;
                 if (d != 0) {
                     const uint32_t idx = (uint32_t)(d < 0 ? -d : d) - 1u;
-                    atomicAdd(&smem[(flat ? 0u : (uint32_t)w * nbin) + (idx >> fb)], 1u);
+                    atomicAdd(&smem[(flat ? 0u : (uint32_t)w * nbin) + (idx >> (w == W - 1 ? fbt : fb))], 1u);
                 }
             });
         }
@@ -686,7 +705,7 @@ __global__ void __launch_bounds__(SORT_TPB) k_sort_digits_sel(const uint32_t* __
                                                               int W, int hb, uint32_t per_block, int32_t* __restrict__ digits,
                                                               size_t stride, uint32_t* __restrict__ coarse_counts, int mode,
                                                               const uint32_t* __restrict__ index, size_t offset,
-                                                              size_t shared_n, uint32_t* __restrict__ flag) {
+                                                              size_t shared_n, uint32_t* __restrict__ flag, int dtop) {
     const scalar_sel sel{index, offset, shared_n, flag};
     // mode 1 (flat): the W digits of scalar i are entries i*W .. i*W+W-1 of ONE list (they index a
     // table of precomputed multiples [2^(jc)]P_i and share a single bucket set)
@@ -695,7 +714,7 @@ __global__ void __launch_bounds__(SORT_TPB) k_sort_digits_sel(const uint32_t* __
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];   // [W][2^hb]   (flat: [2^hb])
     const bool flat = mode == 1;
     const uint32_t nbin = 1u << hb;
-    const int fb = c - 1 - hb;
+    const int fb = c - 1 - hb, fbt = fb - dtop;   // fine bits; those of the top window (sort_top_shift; dtop = 0 when flat)
     const uint32_t nctr = flat ? nbin : (uint32_t)W * nbin;
     for (uint32_t j = threadIdx.x; j < nctr; j += SORT_TPB) smem[j] = 0;
     __syncthreads();
@@ -710,7 +729,7 @@ __global__ void __launch_bounds__(SORT_TPB) k_sort_digits_sel(const uint32_t* __
                 digits[(size_t)w * stride + (h ? n + i : i)] = d;
                 if (d != 0) {
                     const uint32_t idx = (uint32_t)(d < 0 ? -d : d) - 1u;
-                    atomicAdd(&smem[(uint32_t)w * nbin + (idx >> fb)], 1u);
+                    atomicAdd(&smem[(uint32_t)w * nbin + (idx >> (w == W - 1 ? fbt : fb))], 1u);
                 }
             });
         } else {
@@ -718,7 +737,7 @@ __global__ void __launch_bounds__(SORT_TPB) k_sort_digits_sel(const uint32_t* __
                 digits[flat ? i * (size_t)W + w : (size_t)w * stride + i] = d;
                 if (d != 0) {
                     const uint32_t idx = (uint32_t)(d < 0 ? -d : d) - 1u;
-                    atomicAdd(&smem[(flat ? 0u : (uint32_t)w * nbin) + (idx >> fb)], 1u);
+                    atomicAdd(&smem[(flat ? 0u : (uint32_t)w * nbin) + (idx >> (w == W - 1 ? fbt : fb))], 1u);
                 }
             });
         }
@@ -942,7 +961,8 @@ constexpr uint32_t SORT_NONE = 0xffffffffu;
 template <typename SK>
 __global__ void __launch_bounds__(SORT_TPB, sizeof(SK) == 2 ? SORT_WAVES_2WG : SORT_TPB / 256)
     k_sort_coarse(const int32_t* __restrict__ digits, size_t n, size_t stride, int c, int hb, uint32_t* __restrict__ coarse,
-                  uint32_t* __restrict__ cursor, uint32_t* __restrict__ tmp_payload, sort_key_t* __restrict__ tmp_key) {
+                  uint32_t* __restrict__ cursor, uint32_t* __restrict__ tmp_payload, sort_key_t* __restrict__ tmp_key,
+                  int dtop) {
     // tmp_key: the fine part of the bucket index (fb <= 11 bits) -- all the second level needs
     constexpr bool WIDE = sizeof(SK) != 2;
     __shared__ uint32_t hist[1 << SORT_MAX_HB], lstart[1 << SORT_MAX_HB], wbase[1 << SORT_MAX_HB], tmp[SORT_TPB / 64 + 1];
@@ -951,8 +971,8 @@ __global__ void __launch_bounds__(SORT_TPB, sizeof(SK) == 2 ? SORT_WAVES_2WG : S
     __shared__ unsigned short st_pos[SORT_TILE];
     uint32_t* gbase = hist;   // hist[j] is dead once slot j's global base has been reserved
     const uint32_t nbin = 1u << hb;
-    const int fb = c - 1 - hb;
     const uint32_t w = blockIdx.y;
+    const int fb = c - 1 - hb - (w == gridDim.y - 1u ? dtop : 0);   // the top window keeps fewer fine bits (sort_top_shift)
     const size_t tile0 = (size_t)blockIdx.x * SORT_TILE;
     uint32_t* cw = coarse + (size_t)w * (nbin + 1);
     for (uint32_t j = threadIdx.x; j < nbin; j += SORT_TPB) {
@@ -1035,12 +1055,14 @@ __global__ void __launch_bounds__(NT, NT == SORT_TPB ? (PER < 16 ? SORT_WAVES_2W
                                                         const uint32_t* __restrict__ coarse, size_t stride, int c, int hb,
                                                         uint32_t chunk_cap, uint32_t big_thresh, uint32_t big_cap,
                                                         uint32_t perchunk_words, uint32_t* __restrict__ big,
-                                                        uint32_t* __restrict__ ends, uint32_t* __restrict__ lists) {
+                                                        uint32_t* __restrict__ ends, uint32_t* __restrict__ lists, int dtop) {
     // dynamic LDS: 4 arrays of nfine words, chunk_cap payload words, chunk_cap fine keys (u16), perchunk_words words
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     __shared__ uint32_t tmp[NT / 64 + 1];
     const uint32_t nbin = 1u << hb;
-    const int fb = c - 1 - hb;
+    const uint32_t bin = blockIdx.x, w = blockIdx.y;
+    const bool top = dtop != 0 && w == gridDim.y - 1u;
+    const int fb = c - 1 - hb - (top ? dtop : 0);   // the top window keeps fewer fine bits (sort_top_shift)
     const uint32_t nfine = 1u << fb, fmask = nfine - 1u;
     uint32_t* fstart = smem;
     uint32_t* chist = fstart + nfine;
@@ -1048,7 +1070,6 @@ __global__ void __launch_bounds__(NT, NT == SORT_TPB ? (PER < 16 ? SORT_WAVES_2W
     uint32_t* ccur = cstart + nfine;
     uint32_t* st_payload = ccur + nfine;
     unsigned short* st_fine = reinterpret_cast<unsigned short*>(st_payload + chunk_cap);
-    const uint32_t bin = blockIdx.x, w = blockIdx.y;
     const uint32_t* cs = coarse + (size_t)w * (nbin + 1);
     // (the same in every lane: as scalars they make key / pay / out uniform bases, and a load costs one offset register)
     const uint32_t b0 = __builtin_amdgcn_readfirstlane(cs[bin]), m = __builtin_amdgcn_readfirstlane(cs[bin + 1]) - b0;
@@ -1056,6 +1077,14 @@ __global__ void __launch_bounds__(NT, NT == SORT_TPB ? (PER < 16 ? SORT_WAVES_2W
     const uint32_t* pay = tmp_payload + (size_t)w * stride + b0;
     uint32_t* out = lists + (size_t)w * stride + b0;
     uint32_t* e = ends + (((size_t)w << (c - 1)) + ((size_t)bin << fb));
+    if (top) {
+        // the 2^hb bins of the shifted window cover the first 2^(c - 1 - dtop) buckets; the rest is empty and its ends are
+        // the window's total (k_accumulate reads the last one as the total, bucket_of_entry relies on the monotone tail):
+        // every workgroup fills an equal share of them
+        const uint32_t share = (1u << (fb + dtop)) - nfine, total = cs[nbin];
+        uint32_t* tail = ends + (((size_t)w << (c - 1)) + ((size_t)nbin << fb) + (size_t)bin * share);
+        for (uint32_t j = threadIdx.x; j < share; j += NT) tail[j] = total;
+    }
     if (m > big_thresh) {
         // oversized bin (many equal or clustered scalars): leave it to the cooperative kernels
         // below; its bucket counts are gathered in ends[] first, so clear them
@@ -1206,16 +1235,16 @@ AMDMSM_DEV bool big_find_tile(const uint32_t* __restrict__ big, const uint32_t* 
 __global__ void __launch_bounds__(SORT_TPB) k_sort_big_hist(const sort_key_t* __restrict__ tmp_key,
                                                             const uint32_t* __restrict__ coarse, size_t stride, int c,
                                                             int hb, const uint32_t* __restrict__ big,
-                                                            uint32_t* __restrict__ ends) {
+                                                            uint32_t* __restrict__ ends, uint32_t wtop, int dtop) {
     __shared__ uint32_t hist[1 << SORT_MAX_FB], sh[1];
     const uint32_t nbin = 1u << hb;
-    const int fb = c - 1 - hb;
-    const uint32_t nfine = 1u << fb, fmask = nfine - 1u;
     const uint32_t tiles = big[1];
     for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         big_tile bt;
         uint32_t b0;
         big_find_tile(big, coarse, nbin, tile, sh, bt, b0);
+        const int fb = c - 1 - hb - (bt.w == wtop ? dtop : 0);   // fine bits of the bin's window (sort_top_shift)
+        const uint32_t nfine = 1u << fb, fmask = nfine - 1u;
         for (uint32_t j = threadIdx.x; j < nfine; j += SORT_TPB) hist[j] = 0;
         __syncthreads();
         const sort_key_t* key = tmp_key + (size_t)bt.w * stride + b0 + bt.k0;
@@ -1229,18 +1258,19 @@ __global__ void __launch_bounds__(SORT_TPB) k_sort_big_hist(const sort_key_t* __
 
 __global__ void __launch_bounds__(SORT_TPB) k_sort_big_scan(const uint32_t* __restrict__ coarse, int c, int hb,
                                                             uint32_t big_cap, uint32_t* __restrict__ big,
-                                                            uint32_t* __restrict__ ends) {
+                                                            uint32_t* __restrict__ ends, uint32_t wtop, int dtop) {
     __shared__ uint32_t cnt[1 << SORT_MAX_FB], out[1 << SORT_MAX_FB], tmp[SORT_TPB / 64 + 1];
     const uint32_t nbin = 1u << hb;
-    const int fb = c - 1 - hb;
-    const uint32_t nfine = 1u << fb;
+    const int fb_row = c - 1 - hb;   // a record's cursor row keeps its full length
     const uint32_t nbig = big[0];
     for (uint32_t r = blockIdx.x; r < nbig; r += gridDim.x) {
         const uint32_t* rec = big + 4 + 4 * (size_t)r;
         const uint32_t w = rec[0], bin = rec[1];
         const uint32_t b0 = coarse[(size_t)w * (nbin + 1) + bin];
+        const int fb = fb_row - (w == wtop ? dtop : 0);
+        const uint32_t nfine = 1u << fb;
         uint32_t* e = ends + (((size_t)w << (c - 1)) + ((size_t)bin << fb));
-        uint32_t* cur = big + 4 + 4 * (size_t)big_cap + ((size_t)r << fb);
+        uint32_t* cur = big + 4 + 4 * (size_t)big_cap + ((size_t)r << fb_row);
         __syncthreads();
         for (uint32_t j = threadIdx.x; j < nfine; j += SORT_TPB) cnt[j] = e[j];
         __syncthreads();
@@ -1256,25 +1286,26 @@ __global__ void __launch_bounds__(SORT_TPB, SORT_WAVES_2WG) k_sort_big_scatter(c
                                                                const sort_key_t* __restrict__ tmp_key,
                                                                const uint32_t* __restrict__ coarse, size_t stride, int c,
                                                                int hb, uint32_t big_cap, uint32_t* __restrict__ big,
-                                                               uint32_t* __restrict__ lists) {
+                                                               uint32_t* __restrict__ lists, uint32_t wtop, int dtop) {
     // dynamic LDS: hist / lstart / lcur / gbase of 2^fb words, then SORT_TILE source positions and SORT_TILE fine keys,
     // 16 bits each as in k_sort_coarse: the payload is fetched at write-out from the tile the position names
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     __shared__ uint32_t tmp[SORT_TPB / 64 + 1], sh[1];
     const uint32_t nbin = 1u << hb;
-    const int fb = c - 1 - hb;
-    const uint32_t nfine = 1u << fb, fmask = nfine - 1u;
+    const int fb_row = c - 1 - hb;   // LDS layout and cursor rows keep the full length
     uint32_t* hist = smem;
-    uint32_t* lstart = hist + nfine;
-    uint32_t* lcur = lstart + nfine;
-    uint32_t* gbase = lcur + nfine;
-    unsigned short* st_src = reinterpret_cast<unsigned short*>(gbase + nfine);
+    uint32_t* lstart = hist + (1u << fb_row);
+    uint32_t* lcur = lstart + (1u << fb_row);
+    uint32_t* gbase = lcur + (1u << fb_row);
+    unsigned short* st_src = reinterpret_cast<unsigned short*>(gbase + (1u << fb_row));
     unsigned short* st_fine = st_src + SORT_TILE;
     const uint32_t tiles = big[1];
     for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         big_tile bt;
         uint32_t b0;
         big_find_tile(big, coarse, nbin, tile, sh, bt, b0);
+        const int fb = fb_row - (bt.w == wtop ? dtop : 0);   // fine bits of the bin's window (sort_top_shift)
+        const uint32_t nfine = 1u << fb, fmask = nfine - 1u;
         for (uint32_t j = threadIdx.x; j < nfine; j += SORT_TPB) hist[j] = 0;
         __syncthreads();
         const sort_key_t* key = tmp_key + (size_t)bt.w * stride + b0 + bt.k0;
@@ -1282,7 +1313,7 @@ __global__ void __launch_bounds__(SORT_TPB, SORT_WAVES_2WG) k_sort_big_scatter(c
         for (uint32_t k = threadIdx.x; k < bt.cm; k += SORT_TPB) atomicAdd(&hist[key[k] & fmask], 1u);
         __syncthreads();
         block_exclusive_scan(hist, lstart, nfine, tmp);
-        uint32_t* cur = big + 4 + 4 * (size_t)big_cap + ((size_t)bt.rec << fb);
+        uint32_t* cur = big + 4 + 4 * (size_t)big_cap + ((size_t)bt.rec << fb_row);
         for (uint32_t j = threadIdx.x; j < nfine; j += SORT_TPB) {
             const uint32_t h = hist[j];
             lcur[j] = lstart[j];
@@ -3596,6 +3627,13 @@ struct short_src {
 };
 template <int WB>
 size_t packed_items(const void* p, size_t n) { return packed_split<WB>(p, n).items(); }
+// group_vtable::sort_top_window; flat lists have one window
+int l_sort_top_window(int mode, int mont, int c, int W, size_t columns, int* tb_out) {
+    const bool flat = mode == 1;
+    const int tb = flat ? c - 1 : top_window_bits(mode == 2 ? GLV::BOUND_LOG2_X1000 : 0, mont ? FR::BITS : 32 * FRW, c, W);
+    if (tb_out) *tb_out = tb;
+    return flat ? 0 : sort_top_shift(tb, c, W, sort_geometry(columns, c, W).fb);
+}
 // digits / lists may alias (digits are dead once k_sort_coarse has run)
 // sel != null: the selecting form of the digit pass (group_vtable::sort_sel); everything behind it is the same
 void sort_launch(hipStream_t st, const uint32_t* scalars, size_t n, int mont, int c, int W, uint32_t* coarse,
@@ -3611,6 +3649,10 @@ void sort_launch(hipStream_t st, const uint32_t* scalars, size_t n, int mont, in
     const sort_geom sg = sort_geometry(ne, c, We);
     const int hb = sg.hb;
     const uint32_t nbin = 1u << hb;
+    // the top window sorted by the bits it really has (group_vtable.h sort_top_shift); short scalars size their windows
+    // by the data and have no bound of the plan's
+    const int dtop = ss ? 0 : l_sort_top_window(mode, mont, c, W, ne, nullptr);
+    const uint32_t wtop = (uint32_t)We - 1u;
     // scalars per k_sort_digits workgroup: enough workgroups for every CU, few enough global atomics
     uint32_t per_block = 8192;
     while (per_block > SORT_TPB && (n + per_block - 1) / per_block < 1024) per_block >>= 1;
@@ -3636,18 +3678,18 @@ void sort_launch(hipStream_t st, const uint32_t* scalars, size_t n, int mont, in
     } else if (sel)
         hipLaunchKernelGGL(k_sort_digits_sel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(SORT_TPB),
                            (size_t)(flat ? 1 : W) * nbin * 4, st, scalars, n, mont, c, W, hb, per_block, digits, stride, coarse,
-                           mode, sel->index, sel->offset, sel->shared_n, sel->flag);
+                           mode, sel->index, sel->offset, sel->shared_n, sel->flag, dtop);
     else
         hipLaunchKernelGGL(k_sort_digits, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(SORT_TPB),
-                           (size_t)(flat ? 1 : W) * nbin * 4, st, scalars, n, mont, c, W, hb, per_block, digits, stride, coarse, mode);
+                           (size_t)(flat ? 1 : W) * nbin * 4, st, scalars, n, mont, c, W, hb, per_block, digits, stride, coarse, mode, dtop);
     sort_key_t* tmp_key16 = reinterpret_cast<sort_key_t*>(tmp_key);   // W * stride fine keys
     const dim3 coarse_grid((unsigned)((ne + SORT_TILE - 1) / SORT_TILE), We);
     if (c <= 17)   // the bucket index has c - 1 bits
         hipLaunchKernelGGL(k_sort_coarse<unsigned short>, coarse_grid, dim3(SORT_TPB), 0, st, digits, ne, stride, c, hb, coarse,
-                           cursor, tmp_payload, tmp_key16);
+                           cursor, tmp_payload, tmp_key16, dtop);
     else
         hipLaunchKernelGGL(k_sort_coarse<uint32_t>, coarse_grid, dim3(SORT_TPB), 0, st, digits, ne, stride, c, hb, coarse,
-                           cursor, tmp_payload, tmp_key16);
+                           cursor, tmp_payload, tmp_key16, dtop);
     if (after_coarse) (void)hipEventRecord(after_coarse, st);
     // per-chunk histograms of a bin of up to 16 chunks, where they fit beside the staging area (<= 32 KiB)
     static const bool split_hist = !(getenv("AMDMSM_SORT_SPLIT_HIST") && atoi(getenv("AMDMSM_SORT_SPLIT_HIST")) == 0);
@@ -3676,7 +3718,7 @@ void sort_launch(hipStream_t st, const uint32_t* scalars, size_t n, int mont, in
     (void)reported;
 #define AMDMSM_LAUNCH_FINE(NT, PER)                                                                                          \
     hipLaunchKernelGGL((k_sort_fine<NT, PER>), dim3(nbin, We), dim3(NT), fine_lds, st, tmp_payload, tmp_key16, coarse, stride, c, \
-                       hb, sg.chunk_cap, sg.big_thresh, sg.big_cap, perchunk_words, big, ends, lists)
+                       hb, sg.chunk_cap, sg.big_thresh, sg.big_cap, perchunk_words, big, ends, lists, dtop)
     if (sg.chunk_cap <= 4096)
         AMDMSM_LAUNCH_FINE(256, 16);
     else if (sg.chunk_cap <= 8192)
@@ -3686,10 +3728,10 @@ void sort_launch(hipStream_t st, const uint32_t* scalars, size_t n, int mont, in
     else
         AMDMSM_LAUNCH_FINE(SORT_TPB, 16);
 #undef AMDMSM_LAUNCH_FINE
-    hipLaunchKernelGGL(k_sort_big_hist, dim3(512), dim3(SORT_TPB), 0, st, tmp_key16, coarse, stride, c, hb, big, ends);
-    hipLaunchKernelGGL(k_sort_big_scan, dim3(256), dim3(SORT_TPB), 0, st, coarse, c, hb, sg.big_cap, big, ends);
+    hipLaunchKernelGGL(k_sort_big_hist, dim3(512), dim3(SORT_TPB), 0, st, tmp_key16, coarse, stride, c, hb, big, ends, wtop, dtop);
+    hipLaunchKernelGGL(k_sort_big_scan, dim3(256), dim3(SORT_TPB), 0, st, coarse, c, hb, sg.big_cap, big, ends, wtop, dtop);
     hipLaunchKernelGGL(k_sort_big_scatter, dim3(512), dim3(SORT_TPB), big_lds, st, tmp_payload, tmp_key16, coarse, stride, c,
-                       hb, sg.big_cap, big, lists);
+                       hb, sg.big_cap, big, lists, wtop, dtop);
 }
 void l_sort(hipStream_t st, const uint32_t* scalars, size_t n, int mont, int c, int W, uint32_t* coarse,
             uint32_t* cursor, int32_t* digits, uint32_t* tmp_payload, uint32_t* tmp_key, uint32_t* ends, uint32_t* lists,
@@ -4012,6 +4054,7 @@ const group_vtable g_vt = {
     SMV_T, l_smv_table, l_smv_ladder,
     SMV_DIGITS, SEG_DS, l_seg_digits, l_seg_accumulate, l_seg_fold, l_seg_horner,
     l_field_probe, l_xyzz_probe,
+    l_sort_top_window,
 };
 
 }  // namespace

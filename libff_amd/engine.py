@@ -43,7 +43,7 @@ MAX_PHASES = 8
 
 EXPORTED_SYMBOLS = [
     "amdmsm_abi_version", "amdmsm_device_count", "amdmsm_ctx_create", "amdmsm_ctx_destroy", "amdmsm_strerror",
-    "amdmsm_last_error", "amdmsm_sizes", "amdmsm_plan", "amdmsm_plan_ex", "amdmsm_plan_sort", "amdmsm_endomorphism_info",
+    "amdmsm_last_error", "amdmsm_sizes", "amdmsm_plan", "amdmsm_plan_ex", "amdmsm_plan_sort", "amdmsm_plan_top_window", "amdmsm_endomorphism_info",
     "amdmsm_endomorphism_digits_device", "amdmsm_pippenger_optimal_c",
     "amdmsm_bdlo12_signed_optimal_c", "amdmsm_multi_exp", "amdmsm_multi_exp_batch", "amdmsm_multi_exp_batch_items",
     "amdmsm_msm_device_batch_items", "amdmsm_multi_exp_filter_one_zero",
