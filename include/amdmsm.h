@@ -186,6 +186,45 @@ int amdmsm_scalar_mul_vec_device(amdmsm_ctx *ctx, int curve, int group, const vo
                                  const void *d_scalars, size_t n, void *d_out_xyz,
                                  size_t chunk_points, const amdmsm_opts *opts);
 
+/* Fold of point vectors: k vectors of n points and k scalars give one vector of n points,
+ *   out[i] = scalars[0] * P_0[i] + ... + scalars[k-1] * P_(k-1)[i],   i < n,   1 <= k <= 8
+ * -- the generator fold of an inner-product round (G'[i] = x^-1 G_lo[i] + x G_hi[i]: k = 2, the halves of one array), a
+ * query vector times one scalar (k = 1), a random linear combination of k key or commitment vectors.  The scalars are
+ * shared by all elements, so every lane follows the same signed 4-bit digits: one doubling chain serves the k terms, and
+ * the windows above the highest nonzero digit of any scalar are skipped (a 128-bit challenge costs half).
+ *   points_xyz  k pointers in HOST memory to vectors of libff records; stride_bytes and base_form as for
+ *               amdmsm_multi_exp, the same for every vector.  The pointers may alias (one vector twice, the two halves
+ *               of one allocation); the output must not overlap an input
+ *   scalars     k Fr records in HOST memory (in the device entry too): Montgomery residues, or with opts->scalars_plain
+ *               any integers of fr_bytes (a value >= r means the multiple mod r, as in amdmsm_scalar_mul_vec)
+ *   out_xyz     n packed records in opts->out_form (AMDMSM_OUT_LIBFF by default; AMDMSM_OUT_AFFINE: special form,
+ *               normalised as amdmsm_batch_to_special does)
+ * opts->endomorphism follows the permission rule of the MSM (-1 never, 0 only where the whole curve group has order r,
+ * 1 / 2 the caller guarantees subgroup points, never for the MNT groups, AMDMSM_GLV=off honoured); where permitted the
+ * split is always used, whatever the size: phi(P)'s table is P's with x scaled, so 2k half-length digit rows share half
+ * the doublings (amdmsm_plan_fold tells).  opts->window_bits is accepted and ignored.
+ * Workspace: the table of amdmsm_scalar_mul_vec for each of the k vectors plus one table's worth of scratch, 8 (k + 1)
+ * compact affine records per element, so the vectors are worked through chunk_points elements at a time; 0 = the largest
+ * multiple of 256 elements that fits the 1 GiB rule of amdmsm_scalar_mul_vec.
+ * AMDMSM_ERR_UNSUPPORTED for (MNT6, G2), before the context is looked at.  AMDMSM_ERR_BAD_ARG, with amdmsm_last_error
+ * naming the vector, before anything is launched or written: k outside 1 .. 8, a null pointer array, a null vector,
+ * scalar or output pointer with n > 0, a bad stride, a wrong opts->struct_size.  n = 0 succeeds and writes nothing.
+ * With timing enabled: [0] import (with the upload), [1] digits and tables, [2] ladder, [3] normalisation / export --
+ * of the first chunk -- [4] the chunks after it, [AMDMSM_PH_TOTAL] the call. */
+int amdmsm_fold_vec(amdmsm_ctx *ctx, int curve, int group, int k, const void *const *points_xyz, size_t stride_bytes,
+                    int base_form, const void *scalars, size_t n, void *out_xyz, size_t chunk_points,
+                    const amdmsm_opts *opts);
+/* the same on device-resident inputs: k pointers (the array in host memory) to compact affine vectors in device memory
+ * (amdmsm_import_bases_device), n records written to d_out_xyz; enqueued on opts->stream (or the context's), not
+ * synchronised.  Rounds chain on the device: fold with AMDMSM_OUT_AFFINE, then amdmsm_import_bases_device(d_out_xyz,
+ * form special) gives the compact affine vector the next round folds (or its MSM reads). */
+int amdmsm_fold_vec_device(amdmsm_ctx *ctx, int curve, int group, int k, const void *const *d_points_affine,
+                           const void *scalars, size_t n, void *d_out_xyz, size_t chunk_points,
+                           const amdmsm_opts *opts);
+/* read-only, no context: out[0] = digit rows (k, or 2k with the split), out[1] = windows per row, out[2] = endomorphism
+   used (0/1), out[3] = elements per chunk for (n, chunk_points), out[4] = workspace bytes */
+int amdmsm_plan_fold(int curve, int group, int k, size_t n, size_t chunk_points, int endomorphism, size_t out[5]);
+
 /* Segmented MSM: m sums in one call, out[j] = sum of scalars[i] * base(i) over offsets[j] <= i < offsets[j + 1] -- the
  * shape of k proofs verified as a batch (sum of input_i * IC_i per proof), of row or column commitments, of the cross
  * terms of an inner-product argument.  A single MSM per segment would pay the fixed cost of its launch chain m times;

@@ -517,7 +517,7 @@ void record(amdmsm_ctx *ctx, ws_slot &, int idx, hipStream_t st) {
 // -1 = never.  Where permitted it is used when the cost model favours it (plan_cost).
 // AMDMSM_GLV=off switches it off everywhere; AMDMSM_GLV=on|force apply only where the caller left
 // the option at 0 (experiments; logged once) -- a caller's -1 is never overridden.
-bool use_endomorphism(const group_vtable *vt, size_t n, const amdmsm_opts *opts, int table_digits) {
+int glv_env() {
     static const int env = [] {
         const char *e = getenv("AMDMSM_GLV");
         int v = 0;
@@ -530,17 +530,28 @@ bool use_endomorphism(const group_vtable *vt, size_t n, const amdmsm_opts *opts,
                                "(off: everywhere); on / force assert that every base lies in the order-r subgroup\n", e);
         return v;
     }();
-    if (!vt->has_endomorphism) return false;   // MNT4 / MNT6: every amdmsm_opts.endomorphism value is ignored
-    if (table_digits || n == 0 || n >= ((size_t)1 << 30)) return false;
-    const int c_req = opts ? opts->window_bits : 0;
-    if (c_req > 22) return false;
+    return env;
+}
+// The permission half of the rule, without a cost model: 0 = the split may not be used, 1 = permitted, 2 = permitted
+// and asked for at every size.
+int endomorphism_permitted(const group_vtable *vt, const amdmsm_opts *opts) {
+    const int env = glv_env();
+    if (!vt->has_endomorphism) return 0;   // MNT4 / MNT6: every amdmsm_opts.endomorphism value is ignored
     int want = opts ? opts->endomorphism : 0;
     // The environment may switch the split off everywhere, and otherwise speaks only where the caller
     // expressed no choice (0): a caller's -1 (never) stays never, a caller's 1 / 2 keeps its meaning.
     if (env == -1) want = -1;
     else if ((env == 1 || env == 2) && want == 0) want = env;
-    if (want < 0 || (want == 0 && !vt->prime_order)) return false;
-    if (want >= 2) return true;
+    if (want < 0 || (want == 0 && !vt->prime_order)) return 0;
+    return want >= 2 ? 2 : 1;
+}
+bool use_endomorphism(const group_vtable *vt, size_t n, const amdmsm_opts *opts, int table_digits) {
+    const int permitted = endomorphism_permitted(vt, opts);
+    if (!permitted) return false;
+    if (table_digits || n == 0 || n >= ((size_t)1 << 30)) return false;
+    const int c_req = opts ? opts->window_bits : 0;
+    if (c_req > 22) return false;
+    if (permitted >= 2) return true;
     // permitted: used where the model says it pays (small and medium inputs)
     double full = 0, split = 0;
     if (c_req) {
@@ -3047,6 +3058,168 @@ int amdmsm_scalar_mul_vec(amdmsm_ctx *ctx, int curve, int group, const void *poi
                          (uint32_t *)ctx->hb_aff.p);
         rc = smv_chunk(ctx, vt, st, (const uint32_t *)ctx->hb_aff.p, (const uint32_t *)ctx->hb_sc.p, m, (uint32_t *)ctx->fb.out.p,
                        o.out_form, mont, (char *)sl->ws, *sl, off == 0);
+        if (rc) {
+            (void)hipDeviceSynchronize();   // nothing of this call may still touch the staging buffers
+            return rc;
+        }
+        HIP_TRY(ctx, hipMemcpyAsync((char *)out_xyz + off * xyz_bytes, ctx->fb.out.p, m * xyz_bytes, hipMemcpyDeviceToHost, st));
+        if (off == 0) record(ctx, *sl, 4, st);
+        // the next chunk reuses the staging buffers
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+    }
+    return smv_end(ctx, st, *sl);
+}
+
+}  // extern "C"
+
+// ---- fold of k point vectors by k shared scalars: out[i] = sum_j s_j * P_j[i] ---------------------------------------------
+namespace {
+
+// What a call runs: digit rows (two per scalar with the endomorphism split), windows per row, elements per chunk.  The
+// split follows the permission rule of use_endomorphism without its cost model -- the table of phi(P) is the table of P
+// with x scaled, so the 2 k half-length rows share half as many doublings at no other cost.  The workspace of a chunk is
+// the digit rows, the k tables and one table's worth of scratch, which the k table passes use one after the other:
+// (k + 1) * smv_entries compact affine records per element.  chunk_points = 0: the largest multiple of 256 elements that
+// fits SMV_WS_BUDGET (at least 256).
+struct fold_plan {
+    bool glv;
+    int rows, W;
+    size_t cn, ws_bytes;
+};
+size_t fold_ws_bytes(const group_vtable *vt, int k, size_t cn) {
+    return FOLD_DIGIT_BYTES + (size_t)(k + 1) * (size_t)vt->smv_entries * cn * (size_t)vt->el_words * 8;
+}
+fold_plan fold_make_plan(const group_vtable *vt, int k, size_t n, size_t chunk_points, const amdmsm_opts *opts) {
+    fold_plan p;
+    p.glv = endomorphism_permitted(vt, opts) != 0;
+    p.rows = p.glv ? 2 * k : k;
+    p.W = p.glv ? glv_windows(vt, 4) : vt->seg_windows;   // the ladder's 4-bit windows (msm_group.hip SMV_W)
+    size_t cn = chunk_points;
+    if (!cn) {
+        cn = (SMV_WS_BUDGET - FOLD_DIGIT_BYTES) / (fold_ws_bytes(vt, k, 1) - FOLD_DIGIT_BYTES) / 256 * 256;
+        if (cn < 256) cn = 256;
+    }
+    p.cn = cn < n ? cn : n;
+    p.ws_bytes = fold_ws_bytes(vt, k, p.cn);
+    return p;
+}
+
+// one chunk on device-resident inputs: the k tables (and, in the first chunk, the digit rows, which every chunk shares),
+// the ladder and -- for OUT_AFFINE -- the batch normalisation of smv_chunk, its affine records in the table scratch
+int fold_chunk(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, const fold_plan &p, int k, const uint32_t *const *d_aff,
+               size_t aff_off_words, const uint32_t *scalars, size_t cn, uint32_t *d_out, int form, int mont, char *ws,
+               ws_slot &sl, bool first) {
+    const size_t table_words = (size_t)vt->smv_entries * cn * (size_t)vt->el_words * 2;
+    uint32_t *digits = (uint32_t *)ws, *tables = (uint32_t *)(ws + FOLD_DIGIT_BYTES), *tmp = tables + (size_t)k * table_words;
+    if (first) {
+        record(ctx, sl, 1, st);
+        vt->fold_digits(st, scalars, k, mont, p.glv ? 1 : 0, p.W, digits);
+    }
+    for (int j = 0; j < k; ++j) vt->smv_table(st, d_aff[j] + aff_off_words, cn, tmp, tables + (size_t)j * table_words);
+    if (first) record(ctx, sl, 2, st);
+    vt->fold_ladder(st, tables, cn, digits, p.rows, p.glv ? 1 : 0, p.W, form == AMDMSM_OUT_AFFINE ? (int)AMDMSM_OUT_LIBFF : form,
+                    d_out);
+    if (first) record(ctx, sl, 3, st);
+    if (form == AMDMSM_OUT_AFFINE) {
+        vt->import_bases(st, d_out, (size_t)vt->el_words * 3, 0, cn, tmp);
+        vt->export_affine(st, tmp, cn, d_out);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return AMDMSM_OK;
+}
+
+// the argument rules both entries share; nothing is launched or written before they hold
+int fold_check(amdmsm_ctx *ctx, int k, const void *const *vectors, const void *scalars, size_t n, const void *out) {
+    if (k < 1 || k > FOLD_MAX_K) return fail(ctx, AMDMSM_ERR_BAD_ARG, "k = " + std::to_string(k) + ": 1 .. " + std::to_string(FOLD_MAX_K) + " vectors");
+    if (!vectors) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null pointer array");
+    if (!n) return AMDMSM_OK;
+    for (int j = 0; j < k; ++j)
+        if (!vectors[j]) return fail(ctx, AMDMSM_ERR_BAD_ARG, "vector " + std::to_string(j) + ": null pointer");
+    if (!scalars) return fail(ctx, AMDMSM_ERR_BAD_ARG, "scalars: null pointer");
+    if (!out) return fail(ctx, AMDMSM_ERR_BAD_ARG, "output: null pointer");
+    return AMDMSM_OK;
+}
+
+}   // namespace
+
+extern "C" {
+
+int amdmsm_plan_fold(int curve, int group, int k, size_t n, size_t chunk_points, int endomorphism, size_t out[5]) {
+    const group_vtable *vt = find_vt(curve, group);
+    if (!vt) return AMDMSM_ERR_UNSUPPORTED;
+    if (!out || k < 1 || k > FOLD_MAX_K) return AMDMSM_ERR_BAD_ARG;
+    amdmsm_opts o = AMDMSM_OPTS_INIT;
+    o.endomorphism = endomorphism;
+    const fold_plan p = fold_make_plan(vt, k, n, chunk_points, &o);
+    out[0] = (size_t)p.rows;
+    out[1] = (size_t)p.W;
+    out[2] = p.glv ? 1 : 0;
+    out[3] = p.cn;
+    out[4] = p.ws_bytes;
+    return AMDMSM_OK;
+}
+
+int amdmsm_fold_vec_device(amdmsm_ctx *ctx, int curve, int group, int k, const void *const *d_points_affine, const void *scalars,
+                           size_t n, void *d_out_xyz, size_t chunk_points, const amdmsm_opts *opts) {
+    SMV_REFUSE_UNKNOWN(ctx, curve, group);
+    GET_VT(ctx, curve, group);
+    CHECK_OPTS(ctx, opts);
+    int rc = fold_check(ctx, k, d_points_affine, scalars, n, d_out_xyz);
+    if (rc || !n) return rc;
+    hipStream_t st = stream_of(ctx, opts);
+    const int form = opts ? opts->out_form : AMDMSM_OUT_LIBFF;
+    const int mont = (opts && opts->scalars_plain) ? 0 : 1;
+    const size_t ew = (size_t)vt->el_words;
+    const fold_plan p = fold_make_plan(vt, k, n, chunk_points, opts);
+    ws_slot *sl = nullptr;
+    rc = slot_begin(ctx, st, p.ws_bytes, sl);
+    if (rc) return rc;
+    record(ctx, *sl, 0, st);
+    for (size_t o = 0; o < n; o += p.cn) {
+        const size_t m = n - o < p.cn ? n - o : p.cn;
+        rc = fold_chunk(ctx, vt, st, p, k, (const uint32_t *const *)d_points_affine, o * 2 * ew, (const uint32_t *)scalars, m,
+                        (uint32_t *)d_out_xyz + o * 3 * ew, form, mont, (char *)sl->ws, *sl, o == 0);
+        if (rc) return rc;
+        if (o == 0) record(ctx, *sl, 4, st);
+    }
+    return smv_end(ctx, st, *sl);
+}
+
+int amdmsm_fold_vec(amdmsm_ctx *ctx, int curve, int group, int k, const void *const *points_xyz, size_t stride_bytes, int base_form,
+                    const void *scalars, size_t n, void *out_xyz, size_t chunk_points, const amdmsm_opts *opts) {
+    SMV_REFUSE_UNKNOWN(ctx, curve, group);
+    GET_VT(ctx, curve, group);
+    CHECK_OPTS(ctx, opts);
+    const size_t xyz_bytes = (size_t)vt->el_words * 12, aff_bytes = (size_t)vt->el_words * 8;
+    if (stride_bytes == 0) stride_bytes = xyz_bytes;
+    if (stride_bytes % rec_align(vt) || stride_bytes < xyz_bytes) return fail(ctx, AMDMSM_ERR_BAD_ARG, "point stride");
+    int rc = fold_check(ctx, k, points_xyz, scalars, n, out_xyz);
+    if (rc || !n) return rc;
+    hipStream_t st = ctx->stream;
+    const amdmsm_opts o = opts_or_default(opts);
+    const int mont = o.scalars_plain ? 0 : 1;
+    const fold_plan p = fold_make_plan(vt, k, n, chunk_points, &o);
+    rc = ensure_buf(ctx, ctx->hb_src, p.cn * stride_bytes);
+    if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->hb_aff, (size_t)k * p.cn * aff_bytes);
+    if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->fb.out, p.cn * xyz_bytes);
+    ws_slot *sl = nullptr;
+    if (rc == AMDMSM_OK) rc = slot_begin(ctx, st, p.ws_bytes, sl);
+    if (rc) return rc;
+    const uint32_t *d_aff[FOLD_MAX_K];
+    for (int j = 0; j < k; ++j) d_aff[j] = (const uint32_t *)((const char *)ctx->hb_aff.p + (size_t)j * p.cn * aff_bytes);
+    record(ctx, *sl, 0, st);
+    for (size_t off = 0; off < n; off += p.cn) {
+        const size_t m = n - off < p.cn ? n - off : p.cn;
+        // vector after vector through the one staging buffer, in stream order; the last record of a strided vector ends
+        // with its coordinates: nothing past them is read
+        for (int j = 0; j < k; ++j) {
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_src.p, (const char *)points_xyz[j] + off * stride_bytes,
+                                        (m - 1) * stride_bytes + xyz_bytes, hipMemcpyHostToDevice, st));
+            vt->import_bases(st, (const uint32_t *)ctx->hb_src.p, stride_bytes / 4, base_form == AMDMSM_FORM_SPECIAL, m,
+                             (uint32_t *)d_aff[j]);
+        }
+        rc = fold_chunk(ctx, vt, st, p, k, d_aff, 0, (const uint32_t *)scalars, m, (uint32_t *)ctx->fb.out.p, o.out_form, mont,
+                        (char *)sl->ws, *sl, off == 0);
         if (rc) {
             (void)hipDeviceSynchronize();   // nothing of this call may still touch the staging buffers
             return rc;

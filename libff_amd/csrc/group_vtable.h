@@ -290,7 +290,23 @@ struct group_vtable {
     // out of the conversion below r; plain scalars without the split may be any integer of fr_words words (k >= r is
     // documented input), so there only the word length bounds the top window.
     int (*sort_top_window)(int mode, int mont, int c, int W, size_t columns, int* tb);
+
+    // Fold of k point vectors by k shared scalars, out[i] = sum_j s_j * P_j[i] (amdmsm_fold_vec), k <= FOLD_MAX_K.
+    // fold_digits: the signed 4-bit digits of the k scalars -- HOST memory, k records of fr_words words, passed to the
+    // kernel by value -- one signed byte each, digits[row * fold_digit_stride + w], w < W.  glv == 0: row j belongs to
+    // P_j and W = seg_windows (the carry digit included: a plain scalar may be any integer of fr_words words);
+    // glv != 0: rows 2 j and 2 j + 1 are the halves of the split and belong to P_j and phi(P_j), W windows cover the
+    // split's bound.  FOLD_DIGIT_BYTES bytes are enough for every k.
+    // fold_ladder: one lane per element and one doubling chain for all rows, from the highest window in which some row
+    // has a nonzero digit.  tables: the k tables of smv_table one after the other (smv_entries * n records each);
+    // rows = k or 2 k; out: n records in `form` as for smv_ladder.
+    int fold_digit_stride;
+    void (*fold_digits)(hipStream_t, const uint32_t* scalars_host, int k, int mont, int glv, int W, uint32_t* digits);
+    void (*fold_ladder)(hipStream_t, const uint32_t* tables, size_t n, const uint32_t* digits, int rows, int glv, int W,
+                        int form, uint32_t* out);
 };
+constexpr int FOLD_MAX_K = 8;
+constexpr size_t FOLD_DIGIT_BYTES = 2048;   // 2 FOLD_MAX_K rows of at most 100 bytes
 
 // op codes of field_probe: canonical operands in [0, p) per component ...
 enum {

@@ -3593,6 +3593,89 @@ __global__ void __launch_bounds__(64) k_seg_horner(const uint32_t* __restrict__ 
     if (threadIdx.x == 0) store_out(out + (size_t)blockIdx.x * XYZW, res, form);
 }
 
+// ---------------------------------------------------------------- fold of point vectors by shared scalars
+// out[i] = s_0 P_0[i] + ... + s_(k-1) P_(k-1)[i], one lane per element (amdmsm_fold_vec).  The k scalars are the same
+// for every element, so the digits are uniform over the grid: one doubling chain serves all rows (Straus), windows
+// above the highest nonzero digit are skipped by everybody, and no branch on a digit diverges.  Every P_j has the
+// ladder's table (k_smv_table); with the endomorphism split each scalar gives two half-length rows, and the row of
+// phi(P_j) reads P_j's table with x scaled by beta.
+constexpr int FOLD_DS = (SMV_DIGITS + 3) / 4 * 4;   // bytes between two digit rows
+static_assert(2 * FOLD_MAX_K * FOLD_DS <= (int)FOLD_DIGIT_BYTES, "the digit rows fit the buffer the engine sets aside");
+struct alignas(16) fold_scalars {
+    uint32_t w[FOLD_MAX_K * FRW];
+};
+
+// One lane per scalar.  digits[row * FOLD_DS + w] = digit w of the row as a signed byte, whole words written: without
+// the split row j holds the SMV_DIGITS digits of scalar j (the carry digit included), with it rows 2 j and 2 j + 1
+// hold the W digits of its halves, which belong to P_j and phi(P_j).
+__global__ void __launch_bounds__(64) k_fold_digits(const fold_scalars sc, int k, int mont, int glv, int W,
+                                                    uint32_t* __restrict__ digits) {
+    const int j = (int)threadIdx.x;
+    if (j >= k) return;
+    uint32_t s[FRW];
+    load_scalar(s, sc.w, (size_t)j, mont);
+    uint32_t word = 0;
+    auto put = [&](int row, int w, int32_t d) {
+        word |= ((uint32_t)d & 0xffu) << ((w & 3) * 8);
+        if ((w & 3) == 3 || w == W - 1) {
+            digits[row * (FOLD_DS / 4) + (w >> 2)] = word;
+            word = 0;
+        }
+    };
+    if (glv) {
+        if constexpr (GP::HAS_ENDO) for_each_glv_digit(s, SMV_W, W, [&](int h, int w, int32_t d) { put(2 * j + h, w, d); });
+    } else {
+        for_each_signed_digit(s, SMV_W, W, [&](int w, int32_t d) { put(j, w, d); });
+    }
+}
+
+// The ladder.  The digit buffer is read through addresses that depend on nothing but the kernel's arguments and the
+// loop counters: first a scan, four windows at a time, for the highest window in which some row has a nonzero digit
+// (none: n infinities, no table is read), then from there down SMV_W doublings per window and, for every row with a
+// nonzero digit d, the mixed addition of +-table_j[|d| - 1] -- the complete xyzz_madd, as in k_smv_ladder.
+__global__ void __launch_bounds__(TPB) k_fold_ladder(const uint32_t* __restrict__ tables, size_t n,
+                                                     const uint32_t* __restrict__ digits, int rows, int glv, int W,
+                                                     int form, uint32_t* __restrict__ out) {
+    const size_t i = gtid();
+    if (i >= n) return;
+    int top = -1;
+#pragma unroll 1
+    for (int q = (W + 3) / 4 - 1; q >= 0 && top < 0; --q) {
+        uint32_t any = 0;   // a byte of it is nonzero where some row has a nonzero digit in window 4 q + byte
+#pragma unroll 1
+        for (int r = 0; r < rows; ++r) any |= digits[r * (FOLD_DS / 4) + q];
+        if (any) top = 4 * q + (31 - __clz((int)any)) / 8;
+    }
+    const signed char* dg = (const signed char*)digits;
+    Xyzz<E> acc;
+    xyzz_set_inf(acc);
+    Aff<E> e;
+#pragma unroll 1
+    for (int w = top; w >= 0; --w) {
+        if (w != top) {
+#pragma unroll 1
+            for (int b = 0; b < SMV_W; ++b) xyzz_dbl(acc, acc);
+        }
+#pragma unroll 1
+        for (int r = 0; r < rows; ++r) {
+            const int d = dg[r * FOLD_DS + w];
+            if (d) {
+                const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
+                const size_t t = (size_t)(glv ? r >> 1 : r);
+                load_aff(e, tables + ((t * SMV_T + (mag - 1)) * n + i) * AFFW);
+                if constexpr (GP::HAS_ENDO) {
+                    if (glv && (r & 1)) scale_by_beta(e.x);   // phi(x, y) = (beta x, y); (0, 0) stays infinity
+                }
+                el_cneg(e.y, e.y, d < 0);
+                xyzz_madd(acc, e);
+            }
+        }
+    }
+    Jac<E> res;
+    xyzz_to_jac(res, acc);
+    store_out(out + i * XYZW, res, form);
+}
+
 // ---------------------------------------------------------------- launchers
 inline unsigned blocks_for(size_t n, int tpb = TPB) { return (unsigned)((n + tpb - 1) / tpb); }
 
@@ -4044,6 +4127,18 @@ void l_seg_horner(hipStream_t st, const uint32_t* winsum, size_t m, int form, ui
     if (!m) return;
     hipLaunchKernelGGL(k_seg_horner, dim3((unsigned)m), dim3(64), 0, st, winsum, form, out);
 }
+void l_fold_digits(hipStream_t st, const uint32_t* scalars_host, int k, int mont, int glv, int W, uint32_t* digits) {
+    if (k < 1 || k > FOLD_MAX_K) return;
+    fold_scalars sc = {};
+    std::copy(scalars_host, scalars_host + (size_t)k * FRW, sc.w);
+    hipLaunchKernelGGL(k_fold_digits, dim3(1), dim3(64), 0, st, sc, k, mont, GP::HAS_ENDO ? glv : 0, W, digits);
+}
+void l_fold_ladder(hipStream_t st, const uint32_t* tables, size_t n, const uint32_t* digits, int rows, int glv, int W, int form,
+                   uint32_t* out) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_fold_ladder, dim3(blocks_for(n)), dim3(TPB), 0, st, tables, n, digits, rows, GP::HAS_ENDO ? glv : 0, W,
+                       form, out);
+}
 
 const group_vtable g_vt = {
     GP::CURVE, GP::GROUP, FRW, EW, FQ::N, FR::BITS, GP::LIBFF_PROJECTIVE ? 1 : 0, (int)RED_FOLD, ZZS, FR::R,
@@ -4055,6 +4150,7 @@ const group_vtable g_vt = {
     SMV_DIGITS, SEG_DS, l_seg_digits, l_seg_accumulate, l_seg_fold, l_seg_horner,
     l_field_probe, l_xyzz_probe,
     l_sort_top_window,
+    FOLD_DS, l_fold_digits, l_fold_ladder,
 };
 
 }  // namespace

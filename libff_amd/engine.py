@@ -64,6 +64,7 @@ EXPORTED_SYMBOLS = [
     "amdmsm_plan_short", "amdmsm_scalar_bits_device", "amdmsm_multi_exp_short", "amdmsm_msm_device_short",
     "amdmsm_scalar_mul_vec", "amdmsm_scalar_mul_vec_device",
     "amdmsm_multi_exp_segments", "amdmsm_msm_device_segments", "amdmsm_set_segments_chunk_terms",
+    "amdmsm_fold_vec", "amdmsm_fold_vec_device", "amdmsm_plan_fold",
 ]
 SEG_SHARED_BASES = 1            # include/amdmsm.h AMDMSM_SEG_SHARED_BASES
 SEG_LONG_NEVER = 2 ** 64 - 1    # long_from = SIZE_MAX: no segment takes the single-MSM route
@@ -200,6 +201,19 @@ def plan_sort(curve, group, n, window_bits=0, endomorphism=0):
     if rc:
         raise AmdMsmError(f"amdmsm_plan_sort: {rc}")
     return {"columns": out[0], "coarse_bits": out[1], "fine_bits": out[2], "chunk_cap": out[3], "big_thresh": out[4]}
+
+
+def plan_fold(curve, group, k, n, chunk_points=0, endomorphism=0):
+    """What ``Engine.fold_vec`` runs for ``k`` vectors of ``n`` elements (``amdmsm_plan_fold``, read-only): digit rows (k,
+    or 2k with the endomorphism split), windows per row, whether the split is used, elements per chunk and the workspace
+    of a chunk."""
+    out = (ctypes.c_size_t * 5)()
+    rc = load_library().amdmsm_plan_fold(curve, group, int(k), ctypes.c_size_t(n), ctypes.c_size_t(chunk_points),
+                                         int(endomorphism), out)
+    if rc:
+        raise AmdMsmError(f"amdmsm_plan_fold: {rc}")
+    return {"rows": out[0], "num_windows": out[1], "endomorphism": bool(out[2]), "chunk_points": out[3],
+            "workspace_bytes": out[4]}
 
 
 def endomorphism_info(curve, group):
@@ -682,6 +696,41 @@ class Engine:
         self._check(rc, "amdmsm_multi_exp_segments")
         return out
 
+    def fold_vec(self, curve, group, points_list, scalars, base_form=multi_exp_base_form_normal, out_form=OUT_LIBFF,
+                 scalars_plain=False, chunk_points=0, stride_bytes=None, out=None):
+        """Fold of point vectors (``amdmsm_fold_vec``): ``out[i] = sum_j scalars[j] * points_list[j][i]``, k = 1 .. 8
+        vectors of one length and k scalars shared by all elements.  ``points_list``: k arrays of (n, 3 * coordinate
+        limbs) libff records in ``base_form`` (views of one array are fine); ``scalars``: (k, fr_limbs) Montgomery
+        residues, or with ``scalars_plain`` any integers of that width.  The endomorphism split follows
+        ``self.endomorphism`` (``plan_fold`` tells).  ``chunk_points``: elements worked through at a time, 0 = automatic.
+        ``stride_bytes``: bytes between two records of every vector (default: packed).  ``out``: result array to fill."""
+        s = sizes(curve, group)
+        gl = s["g_bytes"] // 8
+        vecs = [np.ascontiguousarray(p, dtype=np.uint64) for p in points_list]
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64)
+        k = len(vecs)
+        if stride_bytes is None:
+            n = int(vecs[0].shape[0]) if k and vecs[0].ndim == 2 else 0
+        else:
+            n = (vecs[0].nbytes - s["g_bytes"]) // stride_bytes + 1 if k and vecs[0].nbytes >= s["g_bytes"] else 0
+        if out is None:
+            out = np.zeros((n, gl), dtype=np.uint64)
+        assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape == (n, gl)
+        if n:
+            assert scalars.shape == (k, s["fr_bytes"] // 8), "scalars must be (k, fr_limbs) uint64"
+            for v in vecs:
+                assert v.nbytes == vecs[0].nbytes, "the vectors must have one length"
+                if stride_bytes is None:
+                    assert v.shape == (n, gl), "every vector must be (n, 3*coord_limbs) uint64"
+        ptrs = (ctypes.c_void_p * max(k, 1))(*[_np_ptr(v) if n else None for v in vecs])
+        o = self._opts(out_form=out_form, scalars_plain=scalars_plain)
+        rc = self.lib.amdmsm_fold_vec(self.h, curve, group, k, ptrs,
+                                      ctypes.c_size_t(s["g_bytes"] if stride_bytes is None else stride_bytes), base_form,
+                                      _np_ptr(scalars) if n else None, ctypes.c_size_t(n), _np_ptr(out) if n else None,
+                                      ctypes.c_size_t(chunk_points), ctypes.byref(o))
+        self._check(rc, "amdmsm_fold_vec")
+        return out
+
     def batch_exp_timings(self):
         """device times (ms) of the last batch_exp: inputs H2D, window table (0 = reused), exponentiations, results D2H"""
         ms = (ctypes.c_float * 4)()
@@ -798,6 +847,19 @@ class Engine:
         self._check(self.lib.amdmsm_scalar_mul_vec_device(self.h, curve, group, _vp(d_points_affine), _vp(d_scalars),
                                                           ctypes.c_size_t(n), _vp(d_out_xyz), ctypes.c_size_t(chunk_points),
                                                           ctypes.byref(o)), "amdmsm_scalar_mul_vec_device")
+
+    def fold_vec_device(self, curve, group, d_points_list, scalars, n, d_out_xyz, out_form=OUT_LIBFF, scalars_plain=False,
+                        chunk_points=0, stream=None):
+        """``fold_vec`` on device-resident compact affine vectors (a list of device pointers; ``scalars`` stays a host
+        array of k records); enqueued on ``stream``, not synchronised.  Rounds chain on the device: ``OUT_AFFINE``, then
+        ``import_bases_device(d_out_xyz, ..., multi_exp_base_form_special, ...)`` gives the next round's vector."""
+        k = len(d_points_list)
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64)
+        ptrs = (ctypes.c_void_p * max(k, 1))(*[_vp(x) for x in d_points_list])
+        o = self._opts(out_form=out_form, scalars_plain=scalars_plain, stream=stream)
+        self._check(self.lib.amdmsm_fold_vec_device(self.h, curve, group, k, ptrs, _np_ptr(scalars) if scalars.size else None,
+                                                    ctypes.c_size_t(n), _vp(d_out_xyz), ctypes.c_size_t(chunk_points),
+                                                    ctypes.byref(o)), "amdmsm_fold_vec_device")
 
     def msm_device_segments(self, curve, group, d_bases_affine, n_bases, d_scalars, n_terms, offsets, d_out, *,
                             shared_bases=False, long_from=0, out_form=OUT_LIBFF, scalars_plain=False, chunk_terms=0,
