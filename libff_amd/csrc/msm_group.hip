@@ -2385,11 +2385,65 @@ AMDMSM_DEV void horner_chain(Jac<EE>& res, const uint32_t* __restrict__ window_s
     }
 }
 
+// The same chain, all of it on the loose 28-bit limbs of wide28.cuh (prime field, N < 16, a = 0): every loaded point is
+// converted once (row r reads coordinate r, one product converts the three), the doublings (jac_dbl_28, runs of any
+// length) and the additions (jac_add_28) stay loose, and one conversion at the end gives the canonical words the
+// chain above produces.  The next window's point is loaded and converted before the doublings it does not depend on.
+// Z of a converted point and of a sum is all-zero exactly at infinity (jac_add_28), so the test that skips the
+// doublings is the one of the chain above.
+constexpr bool HORNER_LAZY_OK = GP::DEG == 1 && FQ::N < 16 && GP::COEFF_A == 0;
+template <class P, bool I>
+AMDMSM_DEV void horner_chain_lazy(Jac<Fp<P, I>>& res, const uint32_t* __restrict__ window_sums, int W, int c,
+                                  const uint32_t* __restrict__ init) {
+    const WideEnv<P> env = wide_env<P>();
+    const Env28<P, 10> v = env28<P, 10>(env);
+    const uint32_t sub4 = tab28_sel(A28<P>::SUB4, env.j);
+    const uint32_t row = (threadIdx.x & 63u) >> 4;
+    auto load = [&](const uint32_t* p, uint32_t& X, uint32_t& Y, uint32_t& Z) {
+        const uint32_t r = to28(v, (env.valid && row < 3u) ? p[row * EW + env.j] : 0u);
+        X = from_row(r, 0);
+        Y = from_row(r, 1);
+        Z = from_row(r, 2);
+    };
+    uint32_t X, Y, Z, X2, Y2, Z2;
+    int w = W - 1;
+    if (init) {
+        load(init, X, Y, Z);
+    } else {
+        load(window_sums + (size_t)w * XYZW, X, Y, Z);
+        --w;
+    }
+    for (; w >= 0; --w) {
+        load(window_sums + (size_t)w * XYZW, X2, Y2, Z2);
+        if (!wide_is_zero(Z)) for (int i = 0; i < c; ++i) jac_dbl_28<P>(v, X, Y, Z);
+        jac_add_28<P>(v, sub4, X, Y, Z, X2, Y2, Z2);
+    }
+    // Z may be twice a product (limbs up to 2^29 + 2^6): still a product operand
+    const uint32_t r = from28(v, row == 0 ? X : (row == 1 ? Y : Z));
+    wide_to_packed(res.x, from_row(r, 0));
+    wide_to_packed(res.y, from_row(r, 1));
+    wide_to_packed(res.z, from_row(r, 2));
+}
+// AMDMSM_HORNER_LAZY=0: the canonical chain (read once per process)
+inline bool horner_lazy() {
+    static const bool on = HORNER_LAZY_OK && !(getenv("AMDMSM_HORNER_LAZY") && atoi(getenv("AMDMSM_HORNER_LAZY")) == 0);
+    return on;
+}
+
 __global__ void __launch_bounds__(64) k_horner(const uint32_t* __restrict__ window_sums, int W, int c, int form,
                                                const uint32_t* __restrict__ init, uint32_t* __restrict__ out) {
     __builtin_amdgcn_s_setprio(3);
     Jac<E> res;
     horner_chain(res, window_sums, W, c, init);
+    if (threadIdx.x == 0) store_out(out, res, form);
+}
+// the kernels of the lazy chain are templates so that only the groups that launch them carry them
+template <class EE = E>
+__global__ void __launch_bounds__(64) k_horner_lazy(const uint32_t* __restrict__ window_sums, int W, int c, int form,
+                                                    const uint32_t* __restrict__ init, uint32_t* __restrict__ out) {
+    __builtin_amdgcn_s_setprio(3);
+    Jac<EE> res;
+    horner_chain_lazy(res, window_sums, W, c, init);
     if (threadIdx.x == 0) store_out(out, res, form);
 }
 
@@ -2413,6 +2467,23 @@ __global__ void __launch_bounds__(64 * WH_MAX_GROUPS) k_window_horner(const uint
     horner_chain(res, grp, ng, 4, nullptr);
     if (threadIdx.x == 0) store_jac(out + (size_t)blockIdx.x * XYZW, res);
 }
+template <class EE = E>
+__global__ void __launch_bounds__(64 * WH_MAX_GROUPS) k_window_horner_lazy(const uint32_t* __restrict__ planes, int c,
+                                                                            uint32_t* __restrict__ out) {
+    __shared__ uint32_t grp[WH_MAX_GROUPS * XYZW];
+    __builtin_amdgcn_s_setprio(3);
+    const int wave = (int)(threadIdx.x >> 6), ng = (c + 3) / 4;
+    Jac<EE> res;
+    if (wave < ng) {
+        const int k0 = 4 * wave, cnt = (c - k0 < 4) ? c - k0 : 4;
+        horner_chain_lazy(res, planes + ((size_t)blockIdx.x * c + k0) * XYZW, cnt, 1, nullptr);
+        if ((threadIdx.x & 63u) == 0) store_jac(grp + wave * XYZW, res);
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    horner_chain_lazy(res, grp, ng, 4, nullptr);
+    if (threadIdx.x == 0) store_jac(out + (size_t)blockIdx.x * XYZW, res);
+}
 
 // k Horner chains at once (amdmsm_msm_device_batch): block j folds the W window sums of MSM j
 struct horner_outs {
@@ -2423,6 +2494,17 @@ __global__ void __launch_bounds__(64) k_horner_batch(const uint32_t* __restrict_
     __builtin_amdgcn_s_setprio(3);
     Jac<E> res;
     horner_chain(res, window_sums + (size_t)blockIdx.x * W * XYZW, W, c, nullptr);
+    uint32_t* out = outs.p[0];
+#pragma unroll
+    for (int j = 1; j < 8; ++j) out = (blockIdx.x == (unsigned)j) ? outs.p[j] : out;
+    if (threadIdx.x == 0) store_out(out, res, form);
+}
+template <class EE = E>
+__global__ void __launch_bounds__(64) k_horner_batch_lazy(const uint32_t* __restrict__ window_sums, int W, int c, int form,
+                                                          horner_outs outs) {
+    __builtin_amdgcn_s_setprio(3);
+    Jac<EE> res;
+    horner_chain_lazy(res, window_sums + (size_t)blockIdx.x * W * XYZW, W, c, nullptr);
     uint32_t* out = outs.p[0];
 #pragma unroll
     for (int j = 1; j < 8; ++j) out = (blockIdx.x == (unsigned)j) ? outs.p[j] : out;
@@ -3592,6 +3674,57 @@ __global__ void __launch_bounds__(64) k_seg_horner(const uint32_t* __restrict__ 
     horner_chain(res, winsum + (size_t)blockIdx.x * SMV_DIGITS * XYZW, SMV_DIGITS, SMV_W, nullptr);
     if (threadIdx.x == 0) store_out(out + (size_t)blockIdx.x * XYZW, res, form);
 }
+template <class EE = E>
+__global__ void __launch_bounds__(64) k_seg_horner_lazy(const uint32_t* __restrict__ winsum, int form, uint32_t* __restrict__ out) {
+    Jac<EE> res;
+    horner_chain_lazy(res, winsum + (size_t)blockIdx.x * SMV_DIGITS * XYZW, SMV_DIGITS, SMV_W, nullptr);
+    if (threadIdx.x == 0) store_out(out + (size_t)blockIdx.x * XYZW, res, form);
+}
+
+// Launches of the Horner kernels: the lazy chain where the group has one and AMDMSM_HORNER_LAZY does not say 0.  The
+// kernel's element type hangs on OK so that the other groups never instantiate the lazy kernels.
+template <bool OK> struct horner_lazy_el { using type = E; };
+template <bool OK = HORNER_LAZY_OK>
+void launch_horner(hipStream_t st, const uint32_t* window_sums, int W, int c, int form, const uint32_t* init, uint32_t* out) {
+    if constexpr (OK) {
+        if (horner_lazy()) {
+            hipLaunchKernelGGL(k_horner_lazy<typename horner_lazy_el<OK>::type>, dim3(1), dim3(64), 0, st, window_sums, W, c, form, init, out);
+            return;
+        }
+    }
+    hipLaunchKernelGGL(k_horner, dim3(1), dim3(64), 0, st, window_sums, W, c, form, init, out);
+}
+template <bool OK = HORNER_LAZY_OK>
+void launch_horner_batch(hipStream_t st, const uint32_t* window_sums, int k, int W, int c, int form, const horner_outs& o) {
+    if constexpr (OK) {
+        if (horner_lazy()) {
+            hipLaunchKernelGGL(k_horner_batch_lazy<typename horner_lazy_el<OK>::type>, dim3((unsigned)k), dim3(64), 0, st, window_sums, W, c, form, o);
+            return;
+        }
+    }
+    hipLaunchKernelGGL(k_horner_batch, dim3((unsigned)k), dim3(64), 0, st, window_sums, W, c, form, o);
+}
+template <bool OK = HORNER_LAZY_OK>
+void launch_window_horner(hipStream_t st, const uint32_t* planes, int W, int c, uint32_t* out) {
+    const dim3 threads((unsigned)(64 * ((c + 3) / 4)));
+    if constexpr (OK) {
+        if (horner_lazy()) {
+            hipLaunchKernelGGL(k_window_horner_lazy<typename horner_lazy_el<OK>::type>, dim3((unsigned)W), threads, 0, st, planes, c, out);
+            return;
+        }
+    }
+    hipLaunchKernelGGL(k_window_horner, dim3((unsigned)W), threads, 0, st, planes, c, out);
+}
+template <bool OK = HORNER_LAZY_OK>
+void launch_seg_horner(hipStream_t st, const uint32_t* winsum, size_t m, int form, uint32_t* out) {
+    if constexpr (OK) {
+        if (horner_lazy()) {
+            hipLaunchKernelGGL(k_seg_horner_lazy<typename horner_lazy_el<OK>::type>, dim3((unsigned)m), dim3(64), 0, st, winsum, form, out);
+            return;
+        }
+    }
+    hipLaunchKernelGGL(k_seg_horner, dim3((unsigned)m), dim3(64), 0, st, winsum, form, out);
+}
 
 // ---------------------------------------------------------------- fold of point vectors by shared scalars
 // out[i] = s_0 P_0[i] + ... + s_(k-1) P_(k-1)[i], one lane per element (amdmsm_fold_vec).  The k scalars are the same
@@ -3970,15 +4103,15 @@ void l_reduce_rowcol(hipStream_t st, const uint32_t* buckets, int W, uint32_t B,
         threads = threads < 64 ? 64 : (threads > 256 ? 256 : threads);
         hipLaunchKernelGGL(k_plane_sums, dim3((unsigned)(W * c)), dim3(threads), 0, st, rc, W, c, h, planes);
     }
-    hipLaunchKernelGGL(k_window_horner, dim3((unsigned)W), dim3((unsigned)(64 * ((c + 3) / 4))), 0, st, planes, c, out);
+    launch_window_horner(st, planes, W, c, out);
 }
 void l_horner(hipStream_t st, const uint32_t* window_sums, int W, int c, int form, const uint32_t* init, uint32_t* out) {
-    hipLaunchKernelGGL(k_horner, dim3(1), dim3(64), 0, st, window_sums, W, c, form, init, out);
+    launch_horner(st, window_sums, W, c, form, init, out);
 }
 void l_horner_batch(hipStream_t st, const uint32_t* window_sums, int k, int W, int c, int form, uint32_t* const* outs) {
     horner_outs o = {};
     for (int j = 0; j < k && j < 8; ++j) o.p[j] = outs[j];
-    hipLaunchKernelGGL(k_horner_batch, dim3((unsigned)k), dim3(64), 0, st, window_sums, W, c, form, o);
+    launch_horner_batch(st, window_sums, k, W, c, form, o);
 }
 void l_sum_points(hipStream_t st, const uint32_t* pts, int k, int form, uint32_t* out) {
     hipLaunchKernelGGL(k_sum_points, dim3(1), dim3(64), 0, st, pts, k, form, out);
@@ -4125,7 +4258,7 @@ void l_seg_fold(hipStream_t st, const uint32_t* sums, const uint32_t* seg_first,
 }
 void l_seg_horner(hipStream_t st, const uint32_t* winsum, size_t m, int form, uint32_t* out) {
     if (!m) return;
-    hipLaunchKernelGGL(k_seg_horner, dim3((unsigned)m), dim3(64), 0, st, winsum, form, out);
+    launch_seg_horner(st, winsum, m, form, out);
 }
 void l_fold_digits(hipStream_t st, const uint32_t* scalars_host, int k, int mont, int glv, int W, uint32_t* digits) {
     if (k < 1 || k > FOLD_MAX_K) return;

@@ -288,6 +288,121 @@ AMDMSM_DEV void jac_dbl_run28(const WideEnv<P>& e, uint32_t& X, uint32_t& Y, uin
     }
 }
 
+// ---------------------------------------------------------------- general addition on loose limbs
+// add-2007-bl with the product sequence and row staging of jac_add_wide (sixteen products in five stages), operands
+// and result in the loose-limb domain of jac_dbl_28, so that a whole Horner chain -- doublings and additions -- converts
+// once per loaded point and once at its end.  The 13 canonical linear operations of jac_add_wide become v_adds and
+// lifted-p subtractions (4 p lifted by 2^30 for subtrahends below 2 p, SUB16 / SUB32 as in the doubling).
+// Bounds, with mul28's a b 2^(-28 L) + p < (alpha beta / 1024 + 1) p for a < alpha p, b < beta p (2^(28 L) >= 2^10 p):
+//   inputs X, Y < 19 p, Z < 4 p, limbs < 2^29.1 (the doubling's input domain; to28 gives < 2 p)
+//   Z1Z1, Z2Z2, Z1Z2 < 1.02 p;  U1, U2, Z^3, S1, S2 < 1.02 p
+//   H = U2 - U1 + 4 p < 5.02 p,  2H < 10.04 p,  I = (2H)^2 < 1.1 p,  Z1 Z2 H < 1.01 p
+//   r = 2 (S2 - S1 + 4 p) < 10.04 p,  r^2 < 1.1 p,  J = H I < 1.01 p,  V = U1 I < 1.01 p
+//   X3 = r^2 - (J + 2V) + 16 p < 17.1 p     (subtrahend < 3.03 p < 8 p, its limbs < 3 (2^28 + 2^5) < 2^30)
+//   V - X3 + 32 p < 33.01 p                 (subtrahend < 17.1 p < 18 p)
+//   Y3 = r (V - X3) - 2 S1 J + 16 p < (10.04 * 33.01 / 1024 + 1 + 16) p < 17.33 p
+//   Z3 = 2 Z1 Z2 H < 2.02 p
+// X3, Y3 come out of a carry28 (limbs < 2^28 + 2^3), Z3 is twice a product (limbs < 2^29 + 2^6): the outputs lie inside
+// the input domain of the doubling AND of the addition, and the doubling's outputs (X, Y < 18 p, Z < 4 p) inside the
+// addition's -- any interleaving is closed without a further carry28 (tests/test_wide28_bounds_cpu.py walks it).
+// Product operands: limbs below 2^29 + 2^6 everywhere here (2H, r, Z), below 3 (2^28 + 2^5) < 2^29.6 in the doubling.
+//
+// Decisions are exact.  A loose value that is 0 mod p is in general a nonzero multiple of p, so no test looks at
+// loose limbs: a product's result lies in [0, 2 p) with limbs < 2^28 + 2^5, and after from28's exact carry
+// normalisation it is 0 mod p iff its limbs are all 0 or all p's.  Z1 = 0 / Z2 = 0 are read off Z1^2 / Z2^2 (stage 1),
+// H = 0 off I = (2H)^2 (stage 3; p is odd) -- products the formulas need anyway -- and r = 0, looked at only when H = 0,
+// off one extra product.  So the same branch is taken as in jac_add_wide for the same inputs, also for a Z that a
+// doubling left as a nonzero multiple of p (2 T for a point T of order two, Y = 0 mod p).  Infinity leaves as an
+// all-zero Z: P + (-P) stores Z3 = 0 instead of the loose product Z1 Z2 H, and the doubling fallback normalises a
+// Z3 = 0 mod p; a chain can therefore test the Z of a sum (or of a converted point) limb by limb.
+template <class P>
+struct A28 {
+    using T = W28<P, 10>;
+    static constexpr tab28 SUB4 = T::lifted(2, 30);
+    static constexpr uint32_t PTOP = cb_limb28(T::modulus(), T::J, true) + 1;   // above the top limb of any value below p
+    // top limbs: 4 p covers subtrahends below 2 p (U1, S1), 16 p below 8 p (J + 2V, 2 S1 J), 32 p below 18 p (X3)
+    static_assert(SUB4.v[T::J] >= PTOP * 2 && T::SUB16.v[T::J] >= PTOP * 8 && T::SUB32.v[T::J] >= PTOP * 18, "top-limb headroom");
+    // lower limbs are lifted by 2^30 less the 4 handed down: above J + 2V, three limbs of a product's result
+    static_assert((1u << 30) - 4u >= 3u * ((1u << 28) + (1u << 5)), "lift covers a three-term subtrahend");
+    // no limb of a lifted difference wraps: minuend and constant below 2^28 + 2^5 and 2^30 + 2^28
+    static_assert((uint64_t)(1u << 28) + (1u << 5) + (1u << 30) + (1u << 28) < (1ull << 32), "lifted difference fits a lane");
+    // mul28 column: operand limbs below OP (2^29.7), m and p's limbs below 2^28, running column t below 2^32
+    static constexpr uint64_t OP = 872000000ull;
+    static_assert(3ull * ((1u << 28) + (1u << 5)) < OP && 2ull * ((1u << 28) + (1u << 5)) + (1u << 6) < OP, "operand limbs");
+    static_assert(OP * OP + (1ull << 56) + (1ull << 32) < (1ull << 63), "64-bit column");
+    static_assert(((OP * OP + (1ull << 56) + (1ull << 32)) >> 28) + (1ull << 28) < (1ull << 32), "shifted column");
+    // the radix leaves 10 bits above p: 2^(28 L) >= 2^10 p
+    static_assert(28 * T::L >= P::BITS + 10 && T::L < 16, "headroom of the radix; lane 15 of a row stays empty");
+};
+
+// exact carry normalisation of a product's result (from28): per lane, "limb differs from 0" / "limb differs from p's"
+template <class P>
+AMDMSM_DEV void exact28(const Env28<P, 10>& v, uint32_t r, unsigned long long& nz, unsigned long long& np) {
+    const uint32_t s = (r & MASK28) + row_up1<P>(v.e, r >> 28);
+    const unsigned long long cin = carry_in_mask((s >> 28) != 0u, s == MASK28);
+    const uint32_t n = (s + (__builtin_amdgcn_inverse_ballot_w64(cin) ? 1u : 0u)) & MASK28;
+    nz = __ballot(n != 0u);
+    np = __ballot(n != v.pj);
+}
+// the element in row ROW is 0 mod p (wave-uniform)
+template <int ROW>
+AMDMSM_DEV bool row_zero28(unsigned long long nz, unsigned long long np) {
+    return ((nz >> (16 * ROW)) & 0xffffull) == 0ull || ((np >> (16 * ROW)) & 0xffffull) == 0ull;
+}
+
+// (X1, Y1, Z1) <- (X1, Y1, Z1) + (X2, Y2, Z2), quads replicated in every row, loose limbs in and out (bounds above);
+// sub4: this lane's limb of A28<P>::SUB4
+template <class P>
+AMDMSM_DEV void jac_add_28(const Env28<P, 10>& v, uint32_t sub4, uint32_t& X1, uint32_t& Y1, uint32_t& Z1, uint32_t X2,
+                           uint32_t Y2, uint32_t Z2) {
+    const uint32_t row = (threadIdx.x & 63u) >> 4;
+    const bool r0 = row == 0, r1 = row == 1, r2 = row == 2;
+    unsigned long long nz, np;
+    // stage 1:  Z1^2 | Z2^2 | Z1*Z2
+    uint32_t r = mul28(v, r1 ? Z2 : Z1, r0 ? Z1 : Z2);
+    exact28(v, r, nz, np);
+    const bool inf1 = row_zero28<0>(nz, np), inf2 = row_zero28<1>(nz, np);
+    if (inf2) {
+        if (inf1) Z1 = 0u;
+        return;
+    }
+    if (inf1) {
+        X1 = X2;
+        Y1 = Y2;
+        Z1 = Z2;
+        return;
+    }
+    const uint32_t z1z1 = from_row(r, 0), z2z2 = from_row(r, 1), z1z2 = from_row(r, 2);
+    // stage 2:  U1 = X1*Z2Z2 | U2 = X2*Z1Z1 | Z2*Z2Z2 | Z1*Z1Z1
+    r = mul28(v, r0 ? X1 : (r1 ? X2 : (r2 ? Z2 : Z1)), (r0 || r2) ? z2z2 : z1z1);
+    const uint32_t u1 = from_row(r, 0), u2 = from_row(r, 1), t1 = from_row(r, 2), t2 = from_row(r, 3);
+    const uint32_t h = carry28(v, u2 + sub4 - u1), h2 = h + h;
+    // stage 3:  S1 = Y1*Z2^3 | S2 = Y2*Z1^3 | I = (2H)^2 | Z1*Z2*H
+    r = mul28(v, r0 ? Y1 : (r1 ? Y2 : (r2 ? h2 : z1z2)), r0 ? t1 : (r1 ? t2 : (r2 ? h2 : h)));
+    exact28(v, r, nz, np);
+    const bool hzero = row_zero28<2>(nz, np);
+    const uint32_t s1 = from_row(r, 0), s2 = from_row(r, 1), ii = from_row(r, 2), zh = from_row(r, 3);
+    const uint32_t d = carry28(v, s2 + sub4 - s1), rr = d + d;
+    if (hzero) {
+        exact28(v, mul28(v, rr, v.cout), nz, np);   // r times a unit
+        if (row_zero28<0>(nz, np)) {                // the same point: double it
+            jac_dbl_28<P>(v, X1, Y1, Z1);
+            exact28(v, mul28(v, Z1, v.cout), nz, np);
+            if (row_zero28<0>(nz, np)) Z1 = 0u;     // Y1 = 0 mod p: a point of order two
+            return;
+        }
+    }
+    // stage 4:  J = H*I | V = U1*I | r^2
+    r = mul28(v, r0 ? h : (r1 ? u1 : rr), r2 ? rr : ii);
+    const uint32_t J = from_row(r, 0), V = from_row(r, 1), R2 = from_row(r, 2);
+    X1 = sub28_16(v, R2, J + V + V);                                   // X3 = r^2 - J - 2V
+    // stage 5:  r*(V - X3) | S1*J
+    r = mul28(v, r0 ? rr : s1, r0 ? sub28_32(v, V, X1) : J);
+    const uint32_t sj = from_row(r, 1);
+    Y1 = sub28_16(v, from_row(r, 0), sj + sj);                         // Y3 = r(V - X3) - 2 S1 J
+    Z1 = hzero ? 0u : zh + zh;                                         // Z3 = 2 Z1 Z2 H; H = 0, r != 0: infinity
+}
+
 // ---------------------------------------------------------------- Fq2 runs (G2 groups)
 // A quad holds one Fq2 element as in WideFq2 (c0 in rows 0 and 2, c1 in rows 1 and 3), every row in
 // loose 28-bit limbs.  Products are Karatsuba (NR = -1: complex squaring) over mul28; all additions
