@@ -225,6 +225,52 @@ int amdmsm_fold_vec_device(amdmsm_ctx *ctx, int curve, int group, int k, const v
    used (0/1), out[3] = elements per chunk for (n, chunk_points), out[4] = workspace bytes */
 int amdmsm_plan_fold(int curve, int group, int k, size_t n, size_t chunk_points, int endomorphism, size_t out[5]);
 
+/* Radix-2 FFT over a vector of group elements:
+ *   out[j] = sum over i < n of w^(i j) * P_i,   j < n,   n a power of two, at most 2^28
+ * -- what a host does with libfqfft's radix-2 butterflies on libff group elements: a powers-of-tau SRS brought into
+ * Lagrange form (a KZG setup, the phase-2 setup of a Groth16 ceremony).  log2 n autosorting decimation-in-time stages of
+ * n / 2 butterflies (A, B, w) -> (A + w B, A - w B), one lane per butterfly: the table of B's multiples 1 B .. 8 B and the
+ * signed 4-bit ladder of amdmsm_scalar_mul_vec, then two complete mixed additions.  The first stage, whose twiddles are
+ * all 1, has no ladder: n / 2 (log2 n - 1) scalar multiplications in all.  Between stages the n results are normalised
+ * as a batch, as amdmsm_batch_to_special does.
+ *   points      n records.  Host entry: libff records, stride_bytes and base_form as for amdmsm_multi_exp.  Device entry:
+ *               compact affine records in device memory (amdmsm_import_bases_device)
+ *   twiddles    n / 2 Fr records w^0 .. w^(n/2 - 1), w a primitive n-th root of unity in Fr (w^(n/2) = -1): Montgomery
+ *               residues, or with opts->scalars_plain plain integers of fr_bytes (any integer: a value >= r means itself
+ *               mod r).  Host memory for the host entry, device memory for the device entry; may be NULL when n <= 2.
+ *               The library has no Fr multiplication and does not check that they are such powers: with other values
+ *               the result is unspecified, but the call stays memory-safe and writes only out
+ *   out_xyz     n packed records in natural order, in opts->out_form (AMDMSM_OUT_LIBFF by default; AMDMSM_OUT_AFFINE:
+ *               special form, normalised as amdmsm_batch_to_special does).  It must not overlap an input
+ * n = 0 succeeds and writes nothing, n = 1 copies the point (in special form, whichever form is asked for), n = 2 is one
+ * add / sub pair.  There is no inverse flag and no scale argument: the inverse transform is the same call with the
+ * powers of w^-1, followed by amdmsm_fold_vec[_device] with k = 1 and the scalar n^-1.  On the device that chain is
+ * amdmsm_group_fft_device with AMDMSM_OUT_AFFINE, amdmsm_import_bases_device(d_out_xyz, form special), then the fold --
+ * the chain of amdmsm_fold_vec_device's rounds.
+ * Workspace: two vectors of n compact affine records and one of n libff records, plus, per butterfly of a chunk, the 16
+ * records of amdmsm_scalar_mul_vec's table and scratch and one gathered operand -- so a stage is worked through
+ * chunk_points butterflies at a time; 0 = the largest multiple of 256 butterflies whose chunk part fits the 1 GiB rule
+ * of amdmsm_scalar_mul_vec, a caller's value is taken as given; never more than n / 2 (amdmsm_plan_group_fft tells).
+ * opts->window_bits and opts->endomorphism are accepted and ignored.
+ * AMDMSM_ERR_UNSUPPORTED for (MNT6, G2), before the context is looked at.  AMDMSM_ERR_BAD_ARG, with amdmsm_last_error
+ * saying which condition, before anything is launched or written: n not a power of two, a null points / out pointer
+ * with n > 0, null twiddles with n > 2, a bad stride, a wrong opts->struct_size.  AMDMSM_ERR_TOO_LARGE for n > 2^28.
+ * With timing enabled, summed over all stages and chunks of the context's last transform: [0] import (host entry: with
+ * the upload), [1] gathers and tables, [2] ladders and butterflies, [3] normalisations and export (host entry: with the
+ * download), [AMDMSM_PH_TOTAL] the call. */
+int amdmsm_group_fft(amdmsm_ctx *ctx, int curve, int group, const void *points_xyz, size_t stride_bytes, int base_form,
+                     size_t n, const void *twiddles, void *out_xyz, size_t chunk_points, const amdmsm_opts *opts);
+/* the same on device-resident inputs; enqueued on opts->stream (or the context's), not synchronised */
+int amdmsm_group_fft_device(amdmsm_ctx *ctx, int curve, int group, const void *d_points_affine, size_t n,
+                            const void *d_twiddles, void *d_out_xyz, size_t chunk_points, const amdmsm_opts *opts);
+/* read-only, no context: out[0] = stages (log2 n), out[1] = stages that run a ladder (max(log2 n - 1, 0)), out[2] =
+   scalar multiplications in total (n / 2 * out[1]), out[3] = butterflies per chunk for (n, chunk_points), out[4] =
+   workspace bytes, out[5] = the part of out[4] that scales with the chunk.  AMDMSM_ERR_BAD_ARG for n not a power of
+   two, AMDMSM_ERR_UNSUPPORTED for (MNT6, G2), AMDMSM_ERR_TOO_LARGE above 2^28 */
+int amdmsm_plan_group_fft(int curve, int group, size_t n, size_t chunk_points, size_t out[6]);
+/* the scalar-field modulus r of the group: fr_bytes, little-endian words, plain integer; no context */
+int amdmsm_fr_modulus(int curve, int group, void *r_plain);
+
 /* Segmented MSM: m sums in one call, out[j] = sum of scalars[i] * base(i) over offsets[j] <= i < offsets[j + 1] -- the
  * shape of k proofs verified as a batch (sum of input_i * IC_i per proof), of row or column commitments, of the cross
  * terms of an inner-product argument.  A single MSM per segment would pay the fixed cost of its launch chain m times;

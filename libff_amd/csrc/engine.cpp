@@ -126,6 +126,12 @@ struct amdmsm_ctx {
     fb_state fb;
     stream_state ss;
     hipEvent_t aux_ev[5] = {};                    // phases of the last amdmsm_batch_exp
+    // phase marks of the last timed amdmsm_group_fft: the time from a mark to the next belongs to the mark's phase, so the
+    // phases of all stages and chunks add up (grow-only; the ring above holds one set of six events per call)
+    std::vector<hipEvent_t> fft_ev;
+    std::vector<unsigned char> fft_phase;
+    size_t fft_marks = 0;
+    long long fft_ticket = -1;
     float aux_ms[4] = {};
     std::string err;
     std::recursive_mutex mu;                      // one call at a time per context (entries nest)
@@ -1153,6 +1159,7 @@ void amdmsm_ctx_destroy(amdmsm_ctx *ctx) {
         for (auto &e : ctx->aux_ev) {
             if (e) (void)hipEventDestroy(e);
         }
+        for (auto &e : ctx->fft_ev) (void)hipEventDestroy(e);
         for (int b = 0; b < stream_state::NB; ++b) {
             if (ctx->ss.h_stage[b]) (void)hipHostFree(ctx->ss.h_stage[b]);
             if (ctx->ss.streams[b]) (void)hipStreamDestroy(ctx->ss.streams[b]);
@@ -1341,6 +1348,17 @@ int amdmsm_get_timings_by_ticket(amdmsm_ctx *ctx, long long ticket, float ms[AMD
     hipEvent_t *ev = ctx->ring[(uint64_t)ticket % TIMING_RING];
     dev_guard g(ctx->device);
     HIP_TRY(ctx, hipEventSynchronize(ev[5]));
+    if (ticket == ctx->fft_ticket && ctx->fft_marks >= 2) {   // amdmsm_group_fft: phases summed over stages and chunks
+        const size_t last = ctx->fft_marks - 1;
+        HIP_TRY(ctx, hipEventSynchronize(ctx->fft_ev[last]));
+        for (size_t i = 0; i < last; ++i) {
+            float d = 0.f;
+            HIP_TRY(ctx, hipEventElapsedTime(&d, ctx->fft_ev[i], ctx->fft_ev[i + 1]));
+            ms[ctx->fft_phase[i]] += d;
+        }
+        HIP_TRY(ctx, hipEventElapsedTime(&ms[AMDMSM_PH_TOTAL], ctx->fft_ev[0], ctx->fft_ev[last]));
+        return AMDMSM_OK;
+    }
     for (int i = 0; i < 5; ++i) HIP_TRY(ctx, hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
     HIP_TRY(ctx, hipEventElapsedTime(&ms[AMDMSM_PH_TOTAL], ev[0], ev[5]));
     return AMDMSM_OK;
@@ -3230,6 +3248,223 @@ int amdmsm_fold_vec(amdmsm_ctx *ctx, int curve, int group, int k, const void *co
         HIP_TRY(ctx, hipStreamSynchronize(st));
     }
     return smv_end(ctx, st, *sl);
+}
+
+}  // extern "C"
+
+// ---- radix-2 FFT over a point vector: out[j] = sum_i w^(i j) P_i ------------------------------------------------------------
+namespace {
+
+// log2 n autosorting stages of n / 2 butterflies each (group_vtable::fft_butterfly).  A stage reads the vector as compact
+// affine records and writes libff records; the batch normalisation of smv_chunk (import_bases in normal form) brings
+// them back to compact affine for the next stage, into the other of two vectors.  The part of the workspace that is
+// linear in n is those two vectors and the vector of libff records; the part that scales with the chunk is, per
+// butterfly, smv_table's 2 * smv_entries records and the gathered B operand the table is built from.  chunk_points = 0:
+// the largest multiple of 256 butterflies whose chunk part fits SMV_WS_BUDGET (at least 256); never more than n / 2.
+constexpr size_t FFT_MAX_N = (size_t)1 << 28;
+constexpr size_t FFT_MAX_MARKS = (size_t)1 << 16;
+struct fft_plan {
+    int stages;
+    size_t cn, chunk_bytes, off_a, off_b, off_xyz, off_chunk, ws_bytes;
+};
+size_t fft_chunk_bytes(const group_vtable *vt, size_t cn) {
+    return (2 * (size_t)vt->smv_entries + 1) * cn * (size_t)vt->el_words * 8;
+}
+fft_plan fft_make_plan(const group_vtable *vt, size_t n, size_t chunk_points) {
+    fft_plan p = {};
+    while (((size_t)2 << p.stages) <= n) ++p.stages;
+    size_t cn = chunk_points;
+    if (!cn) {
+        cn = SMV_WS_BUDGET / fft_chunk_bytes(vt, 1) / 256 * 256;
+        if (cn < 256) cn = 256;
+    }
+    p.cn = cn < n / 2 ? cn : n / 2;
+    p.chunk_bytes = fft_chunk_bytes(vt, p.cn);
+    const size_t aff = align_up(n * (size_t)vt->el_words * 8, 256), xyz = align_up(n * (size_t)vt->el_words * 12, 256);
+    p.off_a = 0;
+    p.off_b = aff;
+    p.off_xyz = 2 * aff;
+    p.off_chunk = 2 * aff + xyz;
+    p.ws_bytes = p.off_chunk + p.chunk_bytes;
+    return p;
+}
+
+// phase mark of a timed call (amdmsm_ctx::fft_ev)
+void fft_mark(amdmsm_ctx *ctx, hipStream_t st, int phase, bool last = false) {
+    if (!ctx->timing) return;
+    if (ctx->fft_marks >= FFT_MAX_MARKS && !last) return;   // the time stays with the phase of the mark before
+    if (ctx->fft_marks == ctx->fft_ev.size()) {
+        hipEvent_t e = nullptr;
+        if (hipEventCreate(&e) != hipSuccess) return;
+        ctx->fft_ev.push_back(e);
+        ctx->fft_phase.push_back(0);
+    }
+    (void)hipEventRecord(ctx->fft_ev[ctx->fft_marks], st);
+    ctx->fft_phase[ctx->fft_marks++] = (unsigned char)phase;
+}
+
+// the argument rules all entries share; nothing is launched or written before they hold
+int fft_check(amdmsm_ctx *ctx, size_t n, const void *points, const void *twiddles, const void *out) {
+    if (n & (n - 1)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "n = " + std::to_string(n) + " is not a power of two");
+    if (n > FFT_MAX_N) return fail(ctx, AMDMSM_ERR_TOO_LARGE, "n = " + std::to_string(n) + ": at most 2^28 points");
+    if (!n) return AMDMSM_OK;
+    if (!points) return fail(ctx, AMDMSM_ERR_BAD_ARG, "points: null pointer");
+    if (!twiddles && n > 2) return fail(ctx, AMDMSM_ERR_BAD_ARG, "twiddles: null pointer");
+    if (!out) return fail(ctx, AMDMSM_ERR_BAD_ARG, "output: null pointer");
+    return AMDMSM_OK;
+}
+
+// the stages on device-resident inputs, n >= 1: d_in is read only (it may be the workspace's first vector), d_out
+// receives n records in `form`
+int fft_stages(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, const fft_plan &p, const uint32_t *d_in,
+               const uint32_t *d_tw, size_t n, uint32_t *d_out, int form, int mont, char *ws) {
+    uint32_t *buf_a = (uint32_t *)(ws + p.off_a), *buf_b = (uint32_t *)(ws + p.off_b), *xyz = (uint32_t *)(ws + p.off_xyz);
+    uint32_t *gathered = (uint32_t *)(ws + p.off_chunk);
+    uint32_t *table = gathered + p.cn * (size_t)vt->el_words * 2, *tmp = table + (size_t)vt->smv_entries * p.cn * (size_t)vt->el_words * 2;
+    const size_t xyz_words = (size_t)vt->el_words * 3, half = n / 2;
+    if (n == 1) {   // the point itself, in special form -- which is a libff record too
+        fft_mark(ctx, st, 3);
+        vt->export_affine(st, d_in, 1, d_out);
+        HIP_TRY(ctx, hipGetLastError());
+        return AMDMSM_OK;
+    }
+    const uint32_t *cur = d_in;
+    for (int t = 0; t < p.stages; ++t) {
+        const int rsh = p.stages - 1 - t;
+        const bool last = t == p.stages - 1;
+        uint32_t *dst = last ? d_out : xyz;
+        uint32_t *next = cur == buf_a ? buf_b : buf_a;
+        for (size_t b0 = 0; b0 < half; b0 += p.cn) {
+            const size_t m = half - b0 < p.cn ? half - b0 : p.cn;
+            if (t == 0) {   // every twiddle is 1
+                fft_mark(ctx, st, 2);
+                vt->fft_butterfly(st, nullptr, m, cur, b0, rsh, d_tw, mont, half, dst);
+            } else {
+                fft_mark(ctx, st, 1);
+                vt->fft_gather(st, cur, b0, m, rsh, gathered);
+                vt->smv_table(st, gathered, m, tmp, table);
+                fft_mark(ctx, st, 2);
+                vt->fft_butterfly(st, table, m, cur, b0, rsh, d_tw, mont, half, dst);
+            }
+        }
+        fft_mark(ctx, st, 3);
+        if (!last) {
+            vt->import_bases(st, dst, xyz_words, 0, n, next);
+            cur = next;
+        } else if (form == AMDMSM_OUT_AFFINE) {
+            vt->import_bases(st, dst, xyz_words, 0, n, next);
+            vt->export_affine(st, next, n, dst);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return AMDMSM_OK;
+}
+
+int fft_begin(amdmsm_ctx *ctx, hipStream_t st, const fft_plan &p, ws_slot *&sl) {
+    const int rc = slot_begin(ctx, st, p.ws_bytes, sl);
+    if (rc) return rc;
+    ctx->fft_marks = 0;
+    ctx->fft_ticket = -1;
+    record(ctx, *sl, 0, st);
+    fft_mark(ctx, st, 0);
+    return AMDMSM_OK;
+}
+int fft_end(amdmsm_ctx *ctx, hipStream_t st, ws_slot &sl) {
+    fft_mark(ctx, st, 3, true);
+    if (ctx->timing) ctx->fft_ticket = (long long)ctx->ticket;   // the ticket smv_end hands out
+    return smv_end(ctx, st, sl);
+}
+
+}   // namespace
+
+extern "C" {
+
+int amdmsm_fr_modulus(int curve, int group, void *r_plain) {
+    const group_vtable *vt = find_vt(curve, group);
+    if (!vt) return AMDMSM_ERR_UNSUPPORTED;
+    if (!r_plain) return AMDMSM_ERR_BAD_ARG;
+    memcpy(r_plain, vt->fr_modulus, (size_t)vt->fr_words * 4);
+    return AMDMSM_OK;
+}
+
+int amdmsm_plan_group_fft(int curve, int group, size_t n, size_t chunk_points, size_t out[6]) {
+    const group_vtable *vt = find_vt(curve, group);
+    if (!vt) return AMDMSM_ERR_UNSUPPORTED;
+    if (!out || (n & (n - 1))) return AMDMSM_ERR_BAD_ARG;
+    if (n > FFT_MAX_N) return AMDMSM_ERR_TOO_LARGE;
+    const fft_plan p = fft_make_plan(vt, n, chunk_points);
+    out[0] = (size_t)p.stages;
+    out[1] = p.stages > 1 ? (size_t)p.stages - 1 : 0;
+    out[2] = n / 2 * out[1];
+    out[3] = p.cn;
+    out[4] = p.ws_bytes;
+    out[5] = p.chunk_bytes;
+    return AMDMSM_OK;
+}
+
+int amdmsm_group_fft_device(amdmsm_ctx *ctx, int curve, int group, const void *d_points_affine, size_t n, const void *d_twiddles,
+                            void *d_out_xyz, size_t chunk_points, const amdmsm_opts *opts) {
+    SMV_REFUSE_UNKNOWN(ctx, curve, group);
+    GET_VT(ctx, curve, group);
+    CHECK_OPTS(ctx, opts);
+    int rc = fft_check(ctx, n, d_points_affine, d_twiddles, d_out_xyz);
+    if (rc || !n) return rc;
+    hipStream_t st = stream_of(ctx, opts);
+    const int form = opts ? opts->out_form : AMDMSM_OUT_LIBFF;
+    const int mont = (opts && opts->scalars_plain) ? 0 : 1;
+    const fft_plan p = fft_make_plan(vt, n, chunk_points);
+    ws_slot *sl = nullptr;
+    rc = fft_begin(ctx, st, p, sl);
+    if (rc) return rc;
+    rc = fft_stages(ctx, vt, st, p, (const uint32_t *)d_points_affine, (const uint32_t *)d_twiddles, n, (uint32_t *)d_out_xyz, form,
+                    mont, (char *)sl->ws);
+    if (rc) return rc;
+    return fft_end(ctx, st, *sl);
+}
+
+int amdmsm_group_fft(amdmsm_ctx *ctx, int curve, int group, const void *points_xyz, size_t stride_bytes, int base_form, size_t n,
+                     const void *twiddles, void *out_xyz, size_t chunk_points, const amdmsm_opts *opts) {
+    SMV_REFUSE_UNKNOWN(ctx, curve, group);
+    GET_VT(ctx, curve, group);
+    CHECK_OPTS(ctx, opts);
+    const size_t xyz_bytes = (size_t)vt->el_words * 12, fr_bytes = (size_t)vt->fr_words * 4;
+    if (stride_bytes == 0) stride_bytes = xyz_bytes;
+    if (stride_bytes % rec_align(vt) || stride_bytes < xyz_bytes) return fail(ctx, AMDMSM_ERR_BAD_ARG, "point stride");
+    int rc = fft_check(ctx, n, points_xyz, twiddles, out_xyz);
+    if (rc || !n) return rc;
+    hipStream_t st = ctx->stream;
+    const amdmsm_opts o = opts_or_default(opts);
+    const int mont = o.scalars_plain ? 0 : 1;
+    const fft_plan p = fft_make_plan(vt, n, chunk_points);
+    // the records go up through the staging buffer a piece at a time: two points per butterfly of a chunk
+    const size_t piece = n < 2 * p.cn || !p.cn ? n : 2 * p.cn;
+    rc = ensure_buf(ctx, ctx->hb_src, piece * stride_bytes);
+    if (rc == AMDMSM_OK && n > 2) rc = ensure_buf(ctx, ctx->hb_sc, n / 2 * fr_bytes);
+    ws_slot *sl = nullptr;
+    if (rc == AMDMSM_OK) rc = fft_begin(ctx, st, p, sl);
+    if (rc) return rc;
+    char *ws = (char *)sl->ws;
+    uint32_t *d_in = (uint32_t *)(ws + p.off_a), *d_res = (uint32_t *)(ws + p.off_xyz);
+    for (size_t off = 0; off < n; off += piece) {
+        const size_t m = n - off < piece ? n - off : piece;
+        // the last record of a strided vector ends with its coordinates: nothing past them is read
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_src.p, (const char *)points_xyz + off * stride_bytes, (m - 1) * stride_bytes + xyz_bytes,
+                                    hipMemcpyHostToDevice, st));
+        vt->import_bases(st, (const uint32_t *)ctx->hb_src.p, stride_bytes / 4, base_form == AMDMSM_FORM_SPECIAL, m,
+                         d_in + off * (size_t)vt->el_words * 2);
+        // the next piece reuses the staging buffer
+        if (off + piece < n) HIP_TRY(ctx, hipStreamSynchronize(st));
+    }
+    if (n > 2) HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_sc.p, twiddles, n / 2 * fr_bytes, hipMemcpyHostToDevice, st));
+    rc = fft_stages(ctx, vt, st, p, d_in, (const uint32_t *)ctx->hb_sc.p, n, d_res, o.out_form, mont, ws);
+    if (rc) {
+        (void)hipDeviceSynchronize();   // nothing of this call may still touch the staging buffers
+        return rc;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(out_xyz, d_res, n * xyz_bytes, hipMemcpyDeviceToHost, st));
+    rc = fft_end(ctx, st, *sl);
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return rc;
 }
 
 }  // extern "C"

@@ -304,6 +304,18 @@ struct group_vtable {
     void (*fold_digits)(hipStream_t, const uint32_t* scalars_host, int k, int mont, int glv, int W, uint32_t* digits);
     void (*fold_ladder)(hipStream_t, const uint32_t* tables, size_t n, const uint32_t* digits, int rows, int glv, int W,
                         int form, uint32_t* out);
+
+    // Radix-2 FFT over a point vector, out[j] = sum_i w^(i j) P_i (amdmsm_group_fft): autosorting decimation-in-time
+    // stages, one lane per butterfly.  Butterfly b < n / 2 of the stage with rsh = log2(n) - 1 - stage reads
+    // A = in[b + (b >> rsh << rsh)], B = in[that + 2^rsh] (compact affine) and w = twiddles[b >> rsh << rsh], and writes
+    // the libff records A + w B to out[b] and A - w B to out[b + half], half = n / 2.
+    // fft_gather: dst[i] = B of butterfly b0 + i, i < cn -- the base vector of smv_table.
+    // fft_butterfly: butterflies b0 .. b0 + cn - 1; table = smv_table's records of those cn B operands, or null for the
+    // stage whose twiddles are all 1 (rsh = log2(n) - 1: T = B, twiddles is not read).  Scalars as for smv_ladder.
+    void (*fft_gather)(hipStream_t, const uint32_t* in_affine, size_t b0, size_t cn, int rsh, uint32_t* dst_affine);
+    void (*fft_butterfly)(hipStream_t, const uint32_t* table, size_t cn, const uint32_t* in_affine, size_t b0, int rsh,
+                          const uint32_t* twiddles, int mont, size_t half, uint32_t* out);
+    const uint32_t* fr_modulus;    // the scalar-field modulus r, plain integer, fr_words words
 };
 constexpr int FOLD_MAX_K = 8;
 constexpr size_t FOLD_DIGIT_BYTES = 2048;   // 2 FOLD_MAX_K rows of at most 100 bytes

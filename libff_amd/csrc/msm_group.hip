@@ -3809,6 +3809,96 @@ __global__ void __launch_bounds__(TPB) k_fold_ladder(const uint32_t* __restrict_
     store_out(out + i * XYZW, res, form);
 }
 
+// ---------------------------------------------------------------- radix-2 FFT over a point vector
+// out[j] = sum_i w^(i j) P_i (amdmsm_group_fft), n = 2^L, as L autosorting decimation-in-time stages.  Before stage t
+// (h = 2^t, r = n / 2^t) record q + r k of the vector is value k of the length-h transform of the r-strided subsequence
+// that starts at q; the stage joins the subsequences q and q + r / 2.  With r2 = r / 2, butterfly b = q + r2 k of the
+// n / 2 (q < r2, k < h) reads
+//     A = in[q + r k] = in[b + (b & ~(r2 - 1))],   B = in[that + r2],   w = twiddles[k r2] = twiddles[b & ~(r2 - 1)]
+// and writes A + w B to record b and A - w B to record b + n / 2, so stage L - 1 leaves natural order and no index is
+// bit-reversed.  Stage 0 has k = 0 alone -- every twiddle is 1 -- and runs without table and ladder.  No index depends
+// on a twiddle's value.
+AMDMSM_DEV size_t fft_a_index(size_t b, int rsh) { return b + ((b >> rsh) << rsh); }   // rsh = log2 r2
+
+// dst[i] = the B operand of butterfly b0 + i, i < cn: the contiguous base vector k_smv_table wants.  One lane per 16 bytes.
+__global__ void __launch_bounds__(TPB) k_fft_gather(const uint32_t* __restrict__ in, size_t b0, size_t cn, int rsh,
+                                                    uint32_t* __restrict__ dst) {
+    constexpr size_t PARTS = AFFW / 4;
+    static_assert(AFFW % 4 == 0, "a compact affine record is a whole number of 16-byte parts");
+    const size_t t = gtid();
+    if (t >= cn * PARTS) return;
+    const size_t i = t / PARTS, part = t % PARTS;
+    const size_t ib = fft_a_index(b0 + i, rsh) + ((size_t)1 << rsh);
+    reinterpret_cast<uint4*>(dst)[t] = reinterpret_cast<const uint4*>(in + ib * AFFW)[part];
+}
+
+// One lane per butterfly b0 + i.  LADDER: T = w B by the ladder of k_smv_ladder -- its recoding, its loop, its live
+// state -- over the table of the chunk's B operands; else T = B.  Only then A is loaded, and both results go through the
+// complete mixed addition: T + A, and A - T as -(T + (-A)).  Infinite A or T, A = T (xyzz_madd doubles, with the a != 0
+// term) and A = -T take xyzz_madd's own branches.  out: libff records b and b + half of the stage's result vector.
+template <bool LADDER>
+__global__ void __launch_bounds__(TPB) k_fft_butterfly(const uint32_t* __restrict__ table, size_t cn,
+                                                       const uint32_t* __restrict__ in, size_t b0, int rsh,
+                                                       const uint32_t* __restrict__ twiddles, int mont, size_t half,
+                                                       uint32_t* __restrict__ out) {
+    const size_t i = gtid();
+    if (i >= cn) return;
+    const size_t b = b0 + i, ia = fft_a_index(b, rsh);
+    Xyzz<E> acc;
+    xyzz_set_inf(acc);
+    Aff<E> e;
+    if constexpr (LADDER) {
+        uint32_t s[FRW];
+        load_scalar(s, twiddles, (b >> rsh) << rsh, mont);
+        constexpr int PER = 32 / SMV_W;
+        constexpr uint32_t DMASK = (1u << SMV_W) - 1u;
+        uint32_t rec[FRW];
+        uint32_t top = 0;
+#pragma unroll
+        for (int j = 0; j < FRW; ++j) rec[j] = 0;
+        for_each_signed_digit(s, SMV_W, SMV_DIGITS, [&](int w, int32_t d) {
+            const uint32_t f = ((uint32_t)d & DMASK) << ((w % PER) * SMV_W);
+#pragma unroll
+            for (int j = 0; j < FRW; ++j) rec[j] |= (w / PER == j) ? f : 0u;
+            top |= (w / PER == FRW) ? f : 0u;
+        });
+        // the carry digit is 0 or 1
+        if (top) {
+            load_aff(e, table + i * AFFW);
+            xyzz_madd(acc, e);
+        }
+#pragma unroll 1
+        for (int w = SMV_DIGITS - 2; w >= 0; --w) {
+#pragma unroll 1
+            for (int k = 0; k < SMV_W; ++k) xyzz_dbl(acc, acc);
+            const uint32_t f = rec[FRW - 1] >> (32 - SMV_W);
+#pragma unroll
+            for (int j = FRW - 1; j >= 0; --j) rec[j] = (rec[j] << SMV_W) | (j ? rec[j - 1] >> (32 - SMV_W) : 0u);
+            const bool neg = (f >> (SMV_W - 1)) != 0;
+            const uint32_t mag = neg ? (1u << SMV_W) - f : f;
+            if (mag) {
+                load_aff(e, table + ((size_t)(mag - 1) * cn + i) * AFFW);
+                el_cneg(e.y, e.y, neg);
+                xyzz_madd(acc, e);
+            }
+        }
+    } else {
+        load_aff(e, in + (ia + ((size_t)1 << rsh)) * AFFW);
+        xyzz_madd(acc, e);
+    }
+    load_aff(e, in + ia * AFFW);
+    Xyzz<E> dif = acc;
+    Jac<E> res;
+    xyzz_madd(acc, e);
+    xyzz_to_jac(res, acc);
+    store_out(out + b * XYZW, res, OUT_LIBFF);
+    el_cneg(e.y, e.y, true);
+    xyzz_madd(dif, e);
+    el_cneg(dif.y, dif.y, true);
+    xyzz_to_jac(res, dif);
+    store_out(out + (b + half) * XYZW, res, OUT_LIBFF);
+}
+
 // ---------------------------------------------------------------- launchers
 inline unsigned blocks_for(size_t n, int tpb = TPB) { return (unsigned)((n + tpb - 1) / tpb); }
 
@@ -4272,6 +4362,20 @@ void l_fold_ladder(hipStream_t st, const uint32_t* tables, size_t n, const uint3
     hipLaunchKernelGGL(k_fold_ladder, dim3(blocks_for(n)), dim3(TPB), 0, st, tables, n, digits, rows, GP::HAS_ENDO ? glv : 0, W,
                        form, out);
 }
+void l_fft_gather(hipStream_t st, const uint32_t* in, size_t b0, size_t cn, int rsh, uint32_t* dst) {
+    if (!cn) return;
+    hipLaunchKernelGGL(k_fft_gather, dim3(blocks_for(cn * (AFFW / 4))), dim3(TPB), 0, st, in, b0, cn, rsh, dst);
+}
+void l_fft_butterfly(hipStream_t st, const uint32_t* table, size_t cn, const uint32_t* in, size_t b0, int rsh,
+                     const uint32_t* twiddles, int mont, size_t half, uint32_t* out) {
+    if (!cn) return;
+    if (table)
+        hipLaunchKernelGGL(k_fft_butterfly<true>, dim3(blocks_for(cn)), dim3(TPB), 0, st, table, cn, in, b0, rsh, twiddles, mont,
+                           half, out);
+    else
+        hipLaunchKernelGGL(k_fft_butterfly<false>, dim3(blocks_for(cn)), dim3(TPB), 0, st, table, cn, in, b0, rsh, twiddles, mont,
+                           half, out);
+}
 
 const group_vtable g_vt = {
     GP::CURVE, GP::GROUP, FRW, EW, FQ::N, FR::BITS, GP::LIBFF_PROJECTIVE ? 1 : 0, (int)RED_FOLD, ZZS, FR::R,
@@ -4284,6 +4388,7 @@ const group_vtable g_vt = {
     l_field_probe, l_xyzz_probe,
     l_sort_top_window,
     FOLD_DS, l_fold_digits, l_fold_ladder,
+    l_fft_gather, l_fft_butterfly, FR::P,
 };
 
 }  // namespace

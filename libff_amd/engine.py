@@ -65,6 +65,7 @@ EXPORTED_SYMBOLS = [
     "amdmsm_scalar_mul_vec", "amdmsm_scalar_mul_vec_device",
     "amdmsm_multi_exp_segments", "amdmsm_msm_device_segments", "amdmsm_set_segments_chunk_terms",
     "amdmsm_fold_vec", "amdmsm_fold_vec_device", "amdmsm_plan_fold",
+    "amdmsm_group_fft", "amdmsm_group_fft_device", "amdmsm_plan_group_fft", "amdmsm_fr_modulus",
 ]
 SEG_SHARED_BASES = 1            # include/amdmsm.h AMDMSM_SEG_SHARED_BASES
 SEG_LONG_NEVER = 2 ** 64 - 1    # long_from = SIZE_MAX: no segment takes the single-MSM route
@@ -214,6 +215,57 @@ def plan_fold(curve, group, k, n, chunk_points=0, endomorphism=0):
         raise AmdMsmError(f"amdmsm_plan_fold: {rc}")
     return {"rows": out[0], "num_windows": out[1], "endomorphism": bool(out[2]), "chunk_points": out[3],
             "workspace_bytes": out[4]}
+
+
+def plan_group_fft(curve, group, n, chunk_points=0):
+    """What ``Engine.group_fft`` runs for ``n`` points (``amdmsm_plan_group_fft``, read-only): stages, the stages that run
+    a ladder, scalar multiplications in total, butterflies per chunk, workspace bytes and the part of them that scales
+    with the chunk."""
+    out = (ctypes.c_size_t * 6)()
+    rc = load_library().amdmsm_plan_group_fft(curve, group, ctypes.c_size_t(n), ctypes.c_size_t(chunk_points), out)
+    if rc:
+        raise AmdMsmError(f"amdmsm_plan_group_fft: {rc}")
+    return {"stages": out[0], "ladder_stages": out[1], "scalar_muls": out[2], "chunk_points": out[3],
+            "workspace_bytes": out[4], "chunk_bytes": out[5]}
+
+
+def fr_modulus(curve, group):
+    """The scalar-field modulus r of the group (``amdmsm_fr_modulus``), as an int."""
+    r = (ctypes.c_uint8 * sizes(curve, group)["fr_bytes"])()
+    rc = load_library().amdmsm_fr_modulus(curve, group, r)
+    if rc:
+        raise AmdMsmError(f"amdmsm_fr_modulus: {rc}")
+    return int.from_bytes(bytes(r), "little")
+
+
+def fft_twiddles(curve, n, inverse=False):
+    """The twiddles of ``Engine.group_fft`` for ``n`` points (a power of two): the (n / 2, fr_limbs) uint64 array of the
+    plain powers w^0 .. w^(n/2 - 1) of an n-th root of unity w = g^((r - 1) / n), g the smallest of 2, 3, 5, ... for which
+    w^(n/2) = r - 1 -- pass them with ``scalars_plain=True``.  ``inverse``: the powers of w^-1 instead.  ValueError where
+    n does not divide the 2-part of r - 1."""
+    n = int(n)
+    r = fr_modulus(curve, G1)
+    limbs = sizes(curve, G1)["fr_bytes"] // 8
+    if n < 1 or n & (n - 1):
+        raise ValueError(f"n = {n} is not a power of two")
+    if (r - 1) % n:
+        raise ValueError(f"n = {n} does not divide r - 1 of {CURVE_NAMES.get(curve, curve)}: no n-th root of unity in Fr")
+    w = 1
+    if n > 1:
+        g = 2
+        while True:
+            if all(g % q for q in range(2, g)):   # g prime
+                w = pow(g, (r - 1) // n, r)
+                if pow(w, n // 2, r) == r - 1:
+                    break
+            g += 1
+    if inverse:
+        w = pow(w, r - 2, r)
+    buf, x = bytearray(), 1
+    for _ in range(n // 2):
+        buf += x.to_bytes(8 * limbs, "little")
+        x = x * w % r
+    return np.frombuffer(bytes(buf), dtype="<u8").astype(np.uint64).reshape(n // 2, limbs)
 
 
 def endomorphism_info(curve, group):
@@ -731,6 +783,38 @@ class Engine:
         self._check(rc, "amdmsm_fold_vec")
         return out
 
+    def group_fft(self, curve, group, points, twiddles, base_form=multi_exp_base_form_normal, out_form=OUT_LIBFF,
+                  scalars_plain=False, chunk_points=0, stride_bytes=None, out=None):
+        """Radix-2 FFT over a point vector (``amdmsm_group_fft``): ``out[j] = sum_i w^(i j) * points[i]``, n a power of
+        two.  ``points``: (n, 3 * coordinate limbs) libff records in ``base_form``; ``twiddles``: (n / 2, fr_limbs) powers
+        w^0 .. w^(n/2 - 1) of a primitive n-th root of unity, Montgomery residues or, with ``scalars_plain``, plain integers
+        (``fft_twiddles`` makes those); None will do for n <= 2.  The inverse transform: the powers of w^-1, then
+        ``fold_vec`` with k = 1 and the scalar n^-1.  ``chunk_points``: butterflies worked through at a time, 0 =
+        automatic (``plan_group_fft`` tells).  ``stride_bytes``: bytes between two records of ``points`` (default:
+        packed).  ``out``: result array to fill."""
+        s = sizes(curve, group)
+        gl = s["g_bytes"] // 8
+        points = np.ascontiguousarray(points, dtype=np.uint64)
+        if stride_bytes is None:
+            n = int(points.shape[0]) if points.ndim == 2 else 0
+        else:
+            n = (points.nbytes - s["g_bytes"]) // stride_bytes + 1 if points.nbytes >= s["g_bytes"] else 0
+        tw = None if twiddles is None else np.ascontiguousarray(twiddles, dtype=np.uint64)
+        if out is None:
+            out = np.zeros((n, gl), dtype=np.uint64)
+        assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape == (n, gl)
+        if n and stride_bytes is None:
+            assert points.shape == (n, gl), "points must be (n, 3*coord_limbs) uint64"
+        if tw is not None and tw.size:
+            assert tw.shape == (n // 2, s["fr_bytes"] // 8), "twiddles must be (n / 2, fr_limbs) uint64"
+        o = self._opts(out_form=out_form, scalars_plain=scalars_plain)
+        rc = self.lib.amdmsm_group_fft(self.h, curve, group, _np_ptr(points) if n else None,
+                                       ctypes.c_size_t(s["g_bytes"] if stride_bytes is None else stride_bytes), base_form,
+                                       ctypes.c_size_t(n), _np_ptr(tw) if tw is not None and tw.size else None,
+                                       _np_ptr(out) if n else None, ctypes.c_size_t(chunk_points), ctypes.byref(o))
+        self._check(rc, "amdmsm_group_fft")
+        return out
+
     def batch_exp_timings(self):
         """device times (ms) of the last batch_exp: inputs H2D, window table (0 = reused), exponentiations, results D2H"""
         ms = (ctypes.c_float * 4)()
@@ -860,6 +944,18 @@ class Engine:
         self._check(self.lib.amdmsm_fold_vec_device(self.h, curve, group, k, ptrs, _np_ptr(scalars) if scalars.size else None,
                                                     ctypes.c_size_t(n), _vp(d_out_xyz), ctypes.c_size_t(chunk_points),
                                                     ctypes.byref(o)), "amdmsm_fold_vec_device")
+
+    def group_fft_device(self, curve, group, d_points, n, d_twiddles, d_out_xyz, out_form=OUT_LIBFF, scalars_plain=False,
+                         chunk_points=0, stream=None):
+        """``group_fft`` on device-resident inputs: ``n`` compact affine points, ``n / 2`` twiddles (None will do for
+        n <= 2), ``n`` records written to ``d_out_xyz``; enqueued on ``stream``, not synchronised.  The inverse chains on
+        the device: ``OUT_AFFINE``, ``import_bases_device(d_out_xyz, ..., multi_exp_base_form_special, ...)``, then
+        ``fold_vec_device`` with k = 1 and the scalar n^-1."""
+        o = self._opts(out_form=out_form, scalars_plain=scalars_plain, stream=stream)
+        self._check(self.lib.amdmsm_group_fft_device(self.h, curve, group, None if d_points is None else _vp(d_points),
+                                                     ctypes.c_size_t(n), None if d_twiddles is None else _vp(d_twiddles),
+                                                     None if d_out_xyz is None else _vp(d_out_xyz),
+                                                     ctypes.c_size_t(chunk_points), ctypes.byref(o)), "amdmsm_group_fft_device")
 
     def msm_device_segments(self, curve, group, d_bases_affine, n_bases, d_scalars, n_terms, offsets, d_out, *,
                             shared_bases=False, long_from=0, out_form=OUT_LIBFF, scalars_plain=False, chunk_terms=0,
