@@ -2954,40 +2954,59 @@ int amdmsm_batch_to_special(amdmsm_ctx *ctx, int curve, int group, void *elems_x
 // ---- element-wise scalar multiplication: out[i] = k_i * P_i ---------------------------------------------------------
 namespace {
 
-// The per-element table (group_vtable::smv_table) and its scratch are 2 * smv_entries compact affine records per element,
-// so a vector is worked through in chunks.  chunk_points = 0 picks the chunk from a workspace budget of 1 GiB: the
-// largest multiple of 256 elements whose table and scratch fit (at least 256).
+// What the point-vector entries (this one, fold_vec, group_fft, the segmented MSM) share.
+//
+// The per-element table (group_vtable::smv_table) is smv_entries compact affine records per element, and its scratch as
+// much again, so a vector is worked through in chunks.  chunk_points = 0 picks the chunk from a workspace budget of
+// 1 GiB: the largest multiple of 256 elements that fits beside the call's fixed part (at least 256); never more than
+// `limit` elements.
 constexpr size_t SMV_WS_BUDGET = (size_t)1 << 30;
-size_t smv_ws_bytes(const group_vtable *vt, size_t cn) { return 2 * (size_t)vt->smv_entries * cn * (size_t)vt->el_words * 8; }
-size_t smv_chunk_points(const group_vtable *vt, size_t n, size_t chunk_points) {
+size_t smv_table_bytes(const group_vtable *vt, size_t cn) { return (size_t)vt->smv_entries * cn * (size_t)vt->el_words * 8; }
+size_t vec_chunk_points(size_t bytes_per_element, size_t fixed_bytes, size_t limit, size_t chunk_points) {
     size_t cn = chunk_points;
     if (!cn) {
-        cn = SMV_WS_BUDGET / smv_ws_bytes(vt, 1) / 256 * 256;
+        cn = (SMV_WS_BUDGET - fixed_bytes) / bytes_per_element / 256 * 256;
         if (cn < 256) cn = 256;
     }
-    return cn < n ? cn : n;
+    return cn < limit ? cn : limit;
 }
 
-// one chunk on device-resident inputs: table, ladder and -- for OUT_AFFINE -- the batch normalisation of
-// amdmsm_batch_to_special (import_bases of the ladder's libff records, one inversion per IMPORT_K of them, then
-// export_affine), its affine records in the table scratch, which the ladder no longer needs
-int smv_chunk(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, const uint32_t *d_aff, const uint32_t *d_sc, size_t cn,
-              uint32_t *d_out, int form, int mont, char *ws, ws_slot &sl, bool timed) {
-    uint32_t *table = (uint32_t *)ws, *tmp = (uint32_t *)(ws + smv_ws_bytes(vt, cn) / 2);
-    if (timed) record(ctx, sl, 1, st);
-    vt->smv_table(st, d_aff, cn, tmp, table);
-    if (timed) record(ctx, sl, 2, st);
-    vt->smv_ladder(st, table, cn, d_sc, mont, form == AMDMSM_OUT_AFFINE ? (int)AMDMSM_OUT_LIBFF : form, d_out);
-    if (timed) record(ctx, sl, 3, st);
-    if (form == AMDMSM_OUT_AFFINE) {
-        vt->import_bases(st, d_out, (size_t)vt->el_words * 3, 0, cn, tmp);
-        vt->export_affine(st, tmp, cn, d_out);
-    }
-    HIP_TRY(ctx, hipGetLastError());
+// What the kernels are told of the caller's options: whether the scalars are in Montgomery form, and the form of the
+// results.  The kernels write libff records when the caller wants affine ones; vec_finish then runs the batch
+// normalisation of amdmsm_batch_to_special over them (import_bases in normal form, one inversion per IMPORT_K records,
+// then export_affine), its n affine records in `scratch`.
+struct vec_opts {
+    int mont, form, kernel_form;
+};
+vec_opts vec_opts_of(const amdmsm_opts *opts) {
+    const int form = opts ? opts->out_form : AMDMSM_OUT_LIBFF;
+    return {(opts && opts->scalars_plain) ? 0 : 1, form, form == AMDMSM_OUT_AFFINE ? (int)AMDMSM_OUT_LIBFF : form};
+}
+void vec_finish(const group_vtable *vt, hipStream_t st, const vec_opts &vo, uint32_t *d_xyz, size_t n, uint32_t *scratch) {
+    if (vo.form != AMDMSM_OUT_AFFINE) return;
+    vt->import_bases(st, d_xyz, (size_t)vt->el_words * 3, 0, n, scratch);
+    vt->export_affine(st, scratch, n, d_xyz);
+}
+
+// A strided host vector of libff records: the stride a caller left out, and what a stride has to be
+int vec_check_stride(amdmsm_ctx *ctx, const group_vtable *vt, size_t &stride_bytes, const char *what) {
+    const size_t xyz_bytes = (size_t)vt->el_words * 12;
+    if (stride_bytes == 0) stride_bytes = xyz_bytes;
+    if (stride_bytes % rec_align(vt) || stride_bytes < xyz_bytes) return fail(ctx, AMDMSM_ERR_BAD_ARG, what);
+    return AMDMSM_OK;
+}
+// records [first, first + m) of such a vector, through the staging buffer hb_src (which the caller has sized) into
+// compact affine records at d_aff
+int vec_upload(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, const void *points_xyz, size_t stride_bytes, int base_form,
+               size_t first, size_t m, void *d_aff) {
+    // the last record of a strided vector ends with its coordinates: nothing past them is read
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_src.p, (const char *)points_xyz + first * stride_bytes,
+                                (m - 1) * stride_bytes + (size_t)vt->el_words * 12, hipMemcpyHostToDevice, st));
+    vt->import_bases(st, (const uint32_t *)ctx->hb_src.p, stride_bytes / 4, base_form == AMDMSM_FORM_SPECIAL, m, (uint32_t *)d_aff);
     return AMDMSM_OK;
 }
 
-// the workspace slot of a call, sized for chunks of cn elements
+// the workspace slot of a call, and the end of the call in it
 int slot_begin(amdmsm_ctx *ctx, hipStream_t st, size_t bytes, ws_slot *&slp) {
     const int slot_idx = (int)(ctx->next++ % (unsigned)ctx->depth);
     ws_slot &sl = ctx->slots[slot_idx];
@@ -2996,18 +3015,56 @@ int slot_begin(amdmsm_ctx *ctx, hipStream_t st, size_t bytes, ws_slot *&slp) {
     slp = &sl;
     return ensure_ws(ctx, sl, bytes);
 }
-int smv_begin(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, size_t cn, ws_slot *&slp) {
-    return slot_begin(ctx, st, smv_ws_bytes(vt, cn), slp);
-}
-// Phase times of a timed call, through the MSM's timing calls: [0] import (host entry: with the upload), [1] table,
-// [2] ladder, [3] normalisation / export (host entry: with the download) -- those four of the first chunk -- [4] the
-// chunks after the first, [AMDMSM_PH_TOTAL] the call.
-int smv_end(amdmsm_ctx *ctx, hipStream_t st, ws_slot &sl) {
+int slot_end(amdmsm_ctx *ctx, hipStream_t st, ws_slot &sl) {
     record(ctx, sl, 5, st);
     if (ctx->timing) sl.last_ticket = (long long)ctx->ticket++;
     sl.ev_valid = ctx->timing;
     HIP_TRY(ctx, hipEventRecord(sl.done, st));
     sl.used = true;
+    return AMDMSM_OK;
+}
+
+// The chunk loop of scalar_mul_vec and fold_vec.  chunk(slot, off, m, first) enqueues elements [off, off + m) and, in
+// the first chunk, records the marks 1 .. 3 between its passes.  Phase times of a timed call, through the MSM's timing
+// calls: [0] import (host entry: with the upload), [1] table, [2] ladder, [3] normalisation / export (host entry: with
+// the download) -- those four of the first chunk -- [4] the chunks after the first, [AMDMSM_PH_TOTAL] the call.
+// h_out == nullptr, a device entry: the chunk has written the caller's vector and nothing waits for it.  Otherwise a
+// host entry, whose chunk uploads into the staging buffers and writes fb.out: the results go down to h_out, and the
+// stream is drained before the next chunk reuses the buffers.
+template <class Chunk>
+int vec_run_chunks(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, size_t ws_bytes, size_t n, size_t cn, void *h_out,
+                   Chunk &&chunk) {
+    const size_t xyz_bytes = (size_t)vt->el_words * 12;
+    ws_slot *sl = nullptr;
+    int rc = slot_begin(ctx, st, ws_bytes, sl);
+    if (rc) return rc;
+    record(ctx, *sl, 0, st);
+    for (size_t off = 0; off < n; off += cn) {
+        const size_t m = n - off < cn ? n - off : cn;
+        rc = chunk(*sl, off, m, off == 0);
+        if (rc) {
+            if (h_out) (void)hipDeviceSynchronize();   // nothing of this call may still touch the staging buffers
+            return rc;
+        }
+        if (h_out) HIP_TRY(ctx, hipMemcpyAsync((char *)h_out + off * xyz_bytes, ctx->fb.out.p, m * xyz_bytes, hipMemcpyDeviceToHost, st));
+        if (off == 0) record(ctx, *sl, 4, st);
+        if (h_out) HIP_TRY(ctx, hipStreamSynchronize(st));
+    }
+    return slot_end(ctx, st, *sl);
+}
+
+// one chunk on device-resident inputs: table, ladder and the results in the caller's form, the table scratch -- which
+// the ladder no longer needs -- lent to vec_finish
+int smv_chunk(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, const uint32_t *d_aff, const uint32_t *d_sc, size_t cn,
+              uint32_t *d_out, const vec_opts &vo, ws_slot &sl, bool timed) {
+    uint32_t *table = (uint32_t *)sl.ws, *tmp = (uint32_t *)((char *)sl.ws + smv_table_bytes(vt, cn));
+    if (timed) record(ctx, sl, 1, st);
+    vt->smv_table(st, d_aff, cn, tmp, table);
+    if (timed) record(ctx, sl, 2, st);
+    vt->smv_ladder(st, table, cn, d_sc, vo.mont, vo.kernel_form, d_out);
+    if (timed) record(ctx, sl, 3, st);
+    vec_finish(vt, st, vo, d_out, cn, tmp);
+    HIP_TRY(ctx, hipGetLastError());
     return AMDMSM_OK;
 }
 
@@ -3027,21 +3084,12 @@ int amdmsm_scalar_mul_vec_device(amdmsm_ctx *ctx, int curve, int group, const vo
     if (n && (!d_points_affine || !d_scalars || !d_out_xyz)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null pointer");
     if (!n) return AMDMSM_OK;
     hipStream_t st = stream_of(ctx, opts);
-    const int form = opts ? opts->out_form : AMDMSM_OUT_LIBFF;
-    const int mont = (opts && opts->scalars_plain) ? 0 : 1;
-    const size_t ew = (size_t)vt->el_words, cn = smv_chunk_points(vt, n, chunk_points);
-    ws_slot *sl = nullptr;
-    int rc = smv_begin(ctx, vt, st, cn, sl);
-    if (rc) return rc;
-    record(ctx, *sl, 0, st);
-    for (size_t o = 0; o < n; o += cn) {
-        const size_t m = n - o < cn ? n - o : cn;
-        rc = smv_chunk(ctx, vt, st, (const uint32_t *)d_points_affine + o * 2 * ew, (const uint32_t *)d_scalars + o * vt->fr_words, m,
-                       (uint32_t *)d_out_xyz + o * 3 * ew, form, mont, (char *)sl->ws, *sl, o == 0);
-        if (rc) return rc;
-        if (o == 0) record(ctx, *sl, 4, st);
-    }
-    return smv_end(ctx, st, *sl);
+    const vec_opts vo = vec_opts_of(opts);
+    const size_t ew = (size_t)vt->el_words, per = 2 * smv_table_bytes(vt, 1), cn = vec_chunk_points(per, 0, n, chunk_points);
+    return vec_run_chunks(ctx, vt, st, cn * per, n, cn, nullptr, [&](ws_slot &sl, size_t off, size_t m, bool first) {
+        return smv_chunk(ctx, vt, st, (const uint32_t *)d_points_affine + off * 2 * ew, (const uint32_t *)d_scalars + off * vt->fr_words,
+                         m, (uint32_t *)d_out_xyz + off * 3 * ew, vo, sl, first);
+    });
 }
 
 int amdmsm_scalar_mul_vec(amdmsm_ctx *ctx, int curve, int group, const void *points_xyz, size_t stride_bytes, int base_form,
@@ -3050,42 +3098,24 @@ int amdmsm_scalar_mul_vec(amdmsm_ctx *ctx, int curve, int group, const void *poi
     GET_VT(ctx, curve, group);
     CHECK_OPTS(ctx, opts);
     if (n && (!points_xyz || !scalars || !out_xyz)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null pointer");
-    const size_t xyz_bytes = (size_t)vt->el_words * 12, aff_bytes = (size_t)vt->el_words * 8, fr_bytes = (size_t)vt->fr_words * 4;
-    if (stride_bytes == 0) stride_bytes = xyz_bytes;
-    if (stride_bytes % rec_align(vt) || stride_bytes < xyz_bytes) return fail(ctx, AMDMSM_ERR_BAD_ARG, "point stride");
-    if (!n) return AMDMSM_OK;
+    int rc = vec_check_stride(ctx, vt, stride_bytes, "point stride");
+    if (rc || !n) return rc;
     hipStream_t st = ctx->stream;
-    const amdmsm_opts o = opts_or_default(opts);
-    const int mont = o.scalars_plain ? 0 : 1;
-    const size_t cn = smv_chunk_points(vt, n, chunk_points);
-    int rc = ensure_buf(ctx, ctx->hb_src, cn * stride_bytes);
+    const vec_opts vo = vec_opts_of(opts);
+    const size_t xyz_bytes = (size_t)vt->el_words * 12, aff_bytes = (size_t)vt->el_words * 8, fr_bytes = (size_t)vt->fr_words * 4;
+    const size_t per = 2 * smv_table_bytes(vt, 1), cn = vec_chunk_points(per, 0, n, chunk_points);
+    rc = ensure_buf(ctx, ctx->hb_src, cn * stride_bytes);
     if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->hb_aff, cn * aff_bytes);
     if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->hb_sc, cn * fr_bytes);
     if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->fb.out, cn * xyz_bytes);
-    ws_slot *sl = nullptr;
-    if (rc == AMDMSM_OK) rc = smv_begin(ctx, vt, st, cn, sl);
     if (rc) return rc;
-    record(ctx, *sl, 0, st);
-    for (size_t off = 0; off < n; off += cn) {
-        const size_t m = n - off < cn ? n - off : cn;
-        // the last record of a strided vector ends with its coordinates: nothing past them is read
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_src.p, (const char *)points_xyz + off * stride_bytes, (m - 1) * stride_bytes + xyz_bytes,
-                                    hipMemcpyHostToDevice, st));
+    return vec_run_chunks(ctx, vt, st, cn * per, n, cn, out_xyz, [&](ws_slot &sl, size_t off, size_t m, bool first) {
+        const int up = vec_upload(ctx, vt, st, points_xyz, stride_bytes, base_form, off, m, ctx->hb_aff.p);
+        if (up) return up;
         HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_sc.p, (const char *)scalars + off * fr_bytes, m * fr_bytes, hipMemcpyHostToDevice, st));
-        vt->import_bases(st, (const uint32_t *)ctx->hb_src.p, stride_bytes / 4, base_form == AMDMSM_FORM_SPECIAL, m,
-                         (uint32_t *)ctx->hb_aff.p);
-        rc = smv_chunk(ctx, vt, st, (const uint32_t *)ctx->hb_aff.p, (const uint32_t *)ctx->hb_sc.p, m, (uint32_t *)ctx->fb.out.p,
-                       o.out_form, mont, (char *)sl->ws, *sl, off == 0);
-        if (rc) {
-            (void)hipDeviceSynchronize();   // nothing of this call may still touch the staging buffers
-            return rc;
-        }
-        HIP_TRY(ctx, hipMemcpyAsync((char *)out_xyz + off * xyz_bytes, ctx->fb.out.p, m * xyz_bytes, hipMemcpyDeviceToHost, st));
-        if (off == 0) record(ctx, *sl, 4, st);
-        // the next chunk reuses the staging buffers
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-    }
-    return smv_end(ctx, st, *sl);
+        return smv_chunk(ctx, vt, st, (const uint32_t *)ctx->hb_aff.p, (const uint32_t *)ctx->hb_sc.p, m, (uint32_t *)ctx->fb.out.p, vo,
+                         sl, first);
+    });
 }
 
 }  // extern "C"
@@ -3097,51 +3127,39 @@ namespace {
 // split follows the permission rule of use_endomorphism without its cost model -- the table of phi(P) is the table of P
 // with x scaled, so the 2 k half-length rows share half as many doublings at no other cost.  The workspace of a chunk is
 // the digit rows, the k tables and one table's worth of scratch, which the k table passes use one after the other:
-// (k + 1) * smv_entries compact affine records per element.  chunk_points = 0: the largest multiple of 256 elements that
-// fits SMV_WS_BUDGET (at least 256).
+// (k + 1) * smv_entries compact affine records per element, which is what vec_chunk_points is given.
 struct fold_plan {
     bool glv;
     int rows, W;
     size_t cn, ws_bytes;
 };
-size_t fold_ws_bytes(const group_vtable *vt, int k, size_t cn) {
-    return FOLD_DIGIT_BYTES + (size_t)(k + 1) * (size_t)vt->smv_entries * cn * (size_t)vt->el_words * 8;
-}
 fold_plan fold_make_plan(const group_vtable *vt, int k, size_t n, size_t chunk_points, const amdmsm_opts *opts) {
     fold_plan p;
     p.glv = endomorphism_permitted(vt, opts) != 0;
     p.rows = p.glv ? 2 * k : k;
     p.W = p.glv ? glv_windows(vt, 4) : vt->seg_windows;   // the ladder's 4-bit windows (msm_group.hip SMV_W)
-    size_t cn = chunk_points;
-    if (!cn) {
-        cn = (SMV_WS_BUDGET - FOLD_DIGIT_BYTES) / (fold_ws_bytes(vt, k, 1) - FOLD_DIGIT_BYTES) / 256 * 256;
-        if (cn < 256) cn = 256;
-    }
-    p.cn = cn < n ? cn : n;
-    p.ws_bytes = fold_ws_bytes(vt, k, p.cn);
+    const size_t per = (size_t)(k + 1) * smv_table_bytes(vt, 1);
+    p.cn = vec_chunk_points(per, FOLD_DIGIT_BYTES, n, chunk_points);
+    p.ws_bytes = FOLD_DIGIT_BYTES + p.cn * per;
     return p;
 }
 
 // one chunk on device-resident inputs: the k tables (and, in the first chunk, the digit rows, which every chunk shares),
-// the ladder and -- for OUT_AFFINE -- the batch normalisation of smv_chunk, its affine records in the table scratch
+// the ladder and the results in the caller's form, the table scratch lent to vec_finish
 int fold_chunk(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, const fold_plan &p, int k, const uint32_t *const *d_aff,
-               size_t aff_off_words, const uint32_t *scalars, size_t cn, uint32_t *d_out, int form, int mont, char *ws,
-               ws_slot &sl, bool first) {
-    const size_t table_words = (size_t)vt->smv_entries * cn * (size_t)vt->el_words * 2;
-    uint32_t *digits = (uint32_t *)ws, *tables = (uint32_t *)(ws + FOLD_DIGIT_BYTES), *tmp = tables + (size_t)k * table_words;
+               size_t aff_off_words, const uint32_t *scalars, size_t cn, uint32_t *d_out, const vec_opts &vo, ws_slot &sl,
+               bool first) {
+    const size_t table_words = smv_table_bytes(vt, cn) / 4;
+    uint32_t *digits = (uint32_t *)sl.ws, *tables = (uint32_t *)((char *)sl.ws + FOLD_DIGIT_BYTES), *tmp = tables + (size_t)k * table_words;
     if (first) {
         record(ctx, sl, 1, st);
-        vt->fold_digits(st, scalars, k, mont, p.glv ? 1 : 0, p.W, digits);
+        vt->fold_digits(st, scalars, k, vo.mont, p.glv ? 1 : 0, p.W, digits);
     }
     for (int j = 0; j < k; ++j) vt->smv_table(st, d_aff[j] + aff_off_words, cn, tmp, tables + (size_t)j * table_words);
     if (first) record(ctx, sl, 2, st);
-    vt->fold_ladder(st, tables, cn, digits, p.rows, p.glv ? 1 : 0, p.W, form == AMDMSM_OUT_AFFINE ? (int)AMDMSM_OUT_LIBFF : form,
-                    d_out);
+    vt->fold_ladder(st, tables, cn, digits, p.rows, p.glv ? 1 : 0, p.W, vo.kernel_form, d_out);
     if (first) record(ctx, sl, 3, st);
-    if (form == AMDMSM_OUT_AFFINE) {
-        vt->import_bases(st, d_out, (size_t)vt->el_words * 3, 0, cn, tmp);
-        vt->export_affine(st, tmp, cn, d_out);
-    }
+    vec_finish(vt, st, vo, d_out, cn, tmp);
     HIP_TRY(ctx, hipGetLastError());
     return AMDMSM_OK;
 }
@@ -3185,22 +3203,13 @@ int amdmsm_fold_vec_device(amdmsm_ctx *ctx, int curve, int group, int k, const v
     int rc = fold_check(ctx, k, d_points_affine, scalars, n, d_out_xyz);
     if (rc || !n) return rc;
     hipStream_t st = stream_of(ctx, opts);
-    const int form = opts ? opts->out_form : AMDMSM_OUT_LIBFF;
-    const int mont = (opts && opts->scalars_plain) ? 0 : 1;
+    const vec_opts vo = vec_opts_of(opts);
     const size_t ew = (size_t)vt->el_words;
     const fold_plan p = fold_make_plan(vt, k, n, chunk_points, opts);
-    ws_slot *sl = nullptr;
-    rc = slot_begin(ctx, st, p.ws_bytes, sl);
-    if (rc) return rc;
-    record(ctx, *sl, 0, st);
-    for (size_t o = 0; o < n; o += p.cn) {
-        const size_t m = n - o < p.cn ? n - o : p.cn;
-        rc = fold_chunk(ctx, vt, st, p, k, (const uint32_t *const *)d_points_affine, o * 2 * ew, (const uint32_t *)scalars, m,
-                        (uint32_t *)d_out_xyz + o * 3 * ew, form, mont, (char *)sl->ws, *sl, o == 0);
-        if (rc) return rc;
-        if (o == 0) record(ctx, *sl, 4, st);
-    }
-    return smv_end(ctx, st, *sl);
+    return vec_run_chunks(ctx, vt, st, p.ws_bytes, n, p.cn, nullptr, [&](ws_slot &sl, size_t off, size_t m, bool first) {
+        return fold_chunk(ctx, vt, st, p, k, (const uint32_t *const *)d_points_affine, off * 2 * ew, (const uint32_t *)scalars, m,
+                          (uint32_t *)d_out_xyz + off * 3 * ew, vo, sl, first);
+    });
 }
 
 int amdmsm_fold_vec(amdmsm_ctx *ctx, int curve, int group, int k, const void *const *points_xyz, size_t stride_bytes, int base_form,
@@ -3208,46 +3217,28 @@ int amdmsm_fold_vec(amdmsm_ctx *ctx, int curve, int group, int k, const void *co
     SMV_REFUSE_UNKNOWN(ctx, curve, group);
     GET_VT(ctx, curve, group);
     CHECK_OPTS(ctx, opts);
-    const size_t xyz_bytes = (size_t)vt->el_words * 12, aff_bytes = (size_t)vt->el_words * 8;
-    if (stride_bytes == 0) stride_bytes = xyz_bytes;
-    if (stride_bytes % rec_align(vt) || stride_bytes < xyz_bytes) return fail(ctx, AMDMSM_ERR_BAD_ARG, "point stride");
-    int rc = fold_check(ctx, k, points_xyz, scalars, n, out_xyz);
+    int rc = vec_check_stride(ctx, vt, stride_bytes, "point stride");
+    if (rc) return rc;
+    rc = fold_check(ctx, k, points_xyz, scalars, n, out_xyz);
     if (rc || !n) return rc;
     hipStream_t st = ctx->stream;
-    const amdmsm_opts o = opts_or_default(opts);
-    const int mont = o.scalars_plain ? 0 : 1;
-    const fold_plan p = fold_make_plan(vt, k, n, chunk_points, &o);
+    const vec_opts vo = vec_opts_of(opts);
+    const size_t xyz_bytes = (size_t)vt->el_words * 12, aff_bytes = (size_t)vt->el_words * 8;
+    const fold_plan p = fold_make_plan(vt, k, n, chunk_points, opts);
     rc = ensure_buf(ctx, ctx->hb_src, p.cn * stride_bytes);
     if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->hb_aff, (size_t)k * p.cn * aff_bytes);
     if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->fb.out, p.cn * xyz_bytes);
-    ws_slot *sl = nullptr;
-    if (rc == AMDMSM_OK) rc = slot_begin(ctx, st, p.ws_bytes, sl);
     if (rc) return rc;
-    const uint32_t *d_aff[FOLD_MAX_K];
-    for (int j = 0; j < k; ++j) d_aff[j] = (const uint32_t *)((const char *)ctx->hb_aff.p + (size_t)j * p.cn * aff_bytes);
-    record(ctx, *sl, 0, st);
-    for (size_t off = 0; off < n; off += p.cn) {
-        const size_t m = n - off < p.cn ? n - off : p.cn;
-        // vector after vector through the one staging buffer, in stream order; the last record of a strided vector ends
-        // with its coordinates: nothing past them is read
+    uint32_t *d_aff[FOLD_MAX_K];
+    for (int j = 0; j < k; ++j) d_aff[j] = (uint32_t *)((char *)ctx->hb_aff.p + (size_t)j * p.cn * aff_bytes);
+    return vec_run_chunks(ctx, vt, st, p.ws_bytes, n, p.cn, out_xyz, [&](ws_slot &sl, size_t off, size_t m, bool first) {
+        // vector after vector through the one staging buffer, in stream order
         for (int j = 0; j < k; ++j) {
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_src.p, (const char *)points_xyz[j] + off * stride_bytes,
-                                        (m - 1) * stride_bytes + xyz_bytes, hipMemcpyHostToDevice, st));
-            vt->import_bases(st, (const uint32_t *)ctx->hb_src.p, stride_bytes / 4, base_form == AMDMSM_FORM_SPECIAL, m,
-                             (uint32_t *)d_aff[j]);
+            const int up = vec_upload(ctx, vt, st, points_xyz[j], stride_bytes, base_form, off, m, d_aff[j]);
+            if (up) return up;
         }
-        rc = fold_chunk(ctx, vt, st, p, k, d_aff, 0, (const uint32_t *)scalars, m, (uint32_t *)ctx->fb.out.p, o.out_form, mont,
-                        (char *)sl->ws, *sl, off == 0);
-        if (rc) {
-            (void)hipDeviceSynchronize();   // nothing of this call may still touch the staging buffers
-            return rc;
-        }
-        HIP_TRY(ctx, hipMemcpyAsync((char *)out_xyz + off * xyz_bytes, ctx->fb.out.p, m * xyz_bytes, hipMemcpyDeviceToHost, st));
-        if (off == 0) record(ctx, *sl, 4, st);
-        // the next chunk reuses the staging buffers
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-    }
-    return smv_end(ctx, st, *sl);
+        return fold_chunk(ctx, vt, st, p, k, d_aff, 0, (const uint32_t *)scalars, m, (uint32_t *)ctx->fb.out.p, vo, sl, first);
+    });
 }
 
 }  // extern "C"
@@ -3256,29 +3247,22 @@ int amdmsm_fold_vec(amdmsm_ctx *ctx, int curve, int group, int k, const void *co
 namespace {
 
 // log2 n autosorting stages of n / 2 butterflies each (group_vtable::fft_butterfly).  A stage reads the vector as compact
-// affine records and writes libff records; the batch normalisation of smv_chunk (import_bases in normal form) brings
+// affine records and writes libff records; the batch normalisation of vec_finish (import_bases in normal form) brings
 // them back to compact affine for the next stage, into the other of two vectors.  The part of the workspace that is
 // linear in n is those two vectors and the vector of libff records; the part that scales with the chunk is, per
-// butterfly, smv_table's 2 * smv_entries records and the gathered B operand the table is built from.  chunk_points = 0:
-// the largest multiple of 256 butterflies whose chunk part fits SMV_WS_BUDGET (at least 256); never more than n / 2.
+// butterfly, smv_table's 2 * smv_entries records and the gathered B operand the table is built from: that part is what
+// vec_chunk_points is given, a chunk being at most the n / 2 butterflies of a stage.
 constexpr size_t FFT_MAX_N = (size_t)1 << 28;
 constexpr size_t FFT_MAX_MARKS = (size_t)1 << 16;
 struct fft_plan {
     int stages;
     size_t cn, chunk_bytes, off_a, off_b, off_xyz, off_chunk, ws_bytes;
 };
-size_t fft_chunk_bytes(const group_vtable *vt, size_t cn) {
-    return (2 * (size_t)vt->smv_entries + 1) * cn * (size_t)vt->el_words * 8;
-}
+size_t fft_chunk_bytes(const group_vtable *vt, size_t cn) { return 2 * smv_table_bytes(vt, cn) + cn * (size_t)vt->el_words * 8; }
 fft_plan fft_make_plan(const group_vtable *vt, size_t n, size_t chunk_points) {
     fft_plan p = {};
     while (((size_t)2 << p.stages) <= n) ++p.stages;
-    size_t cn = chunk_points;
-    if (!cn) {
-        cn = SMV_WS_BUDGET / fft_chunk_bytes(vt, 1) / 256 * 256;
-        if (cn < 256) cn = 256;
-    }
-    p.cn = cn < n / 2 ? cn : n / 2;
+    p.cn = vec_chunk_points(fft_chunk_bytes(vt, 1), 0, n / 2, chunk_points);
     p.chunk_bytes = fft_chunk_bytes(vt, p.cn);
     const size_t aff = align_up(n * (size_t)vt->el_words * 8, 256), xyz = align_up(n * (size_t)vt->el_words * 12, 256);
     p.off_a = 0;
@@ -3317,10 +3301,10 @@ int fft_check(amdmsm_ctx *ctx, size_t n, const void *points, const void *twiddle
 // the stages on device-resident inputs, n >= 1: d_in is read only (it may be the workspace's first vector), d_out
 // receives n records in `form`
 int fft_stages(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, const fft_plan &p, const uint32_t *d_in,
-               const uint32_t *d_tw, size_t n, uint32_t *d_out, int form, int mont, char *ws) {
+               const uint32_t *d_tw, size_t n, uint32_t *d_out, const vec_opts &vo, char *ws) {
     uint32_t *buf_a = (uint32_t *)(ws + p.off_a), *buf_b = (uint32_t *)(ws + p.off_b), *xyz = (uint32_t *)(ws + p.off_xyz);
     uint32_t *gathered = (uint32_t *)(ws + p.off_chunk);
-    uint32_t *table = gathered + p.cn * (size_t)vt->el_words * 2, *tmp = table + (size_t)vt->smv_entries * p.cn * (size_t)vt->el_words * 2;
+    uint32_t *table = gathered + p.cn * (size_t)vt->el_words * 2, *tmp = table + smv_table_bytes(vt, p.cn) / 4;
     const size_t xyz_words = (size_t)vt->el_words * 3, half = n / 2;
     if (n == 1) {   // the point itself, in special form -- which is a libff record too
         fft_mark(ctx, st, 3);
@@ -3338,22 +3322,21 @@ int fft_stages(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, const ff
             const size_t m = half - b0 < p.cn ? half - b0 : p.cn;
             if (t == 0) {   // every twiddle is 1
                 fft_mark(ctx, st, 2);
-                vt->fft_butterfly(st, nullptr, m, cur, b0, rsh, d_tw, mont, half, dst);
+                vt->fft_butterfly(st, nullptr, m, cur, b0, rsh, d_tw, vo.mont, half, dst);
             } else {
                 fft_mark(ctx, st, 1);
                 vt->fft_gather(st, cur, b0, m, rsh, gathered);
                 vt->smv_table(st, gathered, m, tmp, table);
                 fft_mark(ctx, st, 2);
-                vt->fft_butterfly(st, table, m, cur, b0, rsh, d_tw, mont, half, dst);
+                vt->fft_butterfly(st, table, m, cur, b0, rsh, d_tw, vo.mont, half, dst);
             }
         }
         fft_mark(ctx, st, 3);
         if (!last) {
             vt->import_bases(st, dst, xyz_words, 0, n, next);
             cur = next;
-        } else if (form == AMDMSM_OUT_AFFINE) {
-            vt->import_bases(st, dst, xyz_words, 0, n, next);
-            vt->export_affine(st, next, n, dst);
+        } else {
+            vec_finish(vt, st, vo, dst, n, next);
         }
         HIP_TRY(ctx, hipGetLastError());
     }
@@ -3371,8 +3354,8 @@ int fft_begin(amdmsm_ctx *ctx, hipStream_t st, const fft_plan &p, ws_slot *&sl) 
 }
 int fft_end(amdmsm_ctx *ctx, hipStream_t st, ws_slot &sl) {
     fft_mark(ctx, st, 3, true);
-    if (ctx->timing) ctx->fft_ticket = (long long)ctx->ticket;   // the ticket smv_end hands out
-    return smv_end(ctx, st, sl);
+    if (ctx->timing) ctx->fft_ticket = (long long)ctx->ticket;   // the ticket slot_end hands out
+    return slot_end(ctx, st, sl);
 }
 
 }   // namespace
@@ -3410,14 +3393,12 @@ int amdmsm_group_fft_device(amdmsm_ctx *ctx, int curve, int group, const void *d
     int rc = fft_check(ctx, n, d_points_affine, d_twiddles, d_out_xyz);
     if (rc || !n) return rc;
     hipStream_t st = stream_of(ctx, opts);
-    const int form = opts ? opts->out_form : AMDMSM_OUT_LIBFF;
-    const int mont = (opts && opts->scalars_plain) ? 0 : 1;
     const fft_plan p = fft_make_plan(vt, n, chunk_points);
     ws_slot *sl = nullptr;
     rc = fft_begin(ctx, st, p, sl);
     if (rc) return rc;
-    rc = fft_stages(ctx, vt, st, p, (const uint32_t *)d_points_affine, (const uint32_t *)d_twiddles, n, (uint32_t *)d_out_xyz, form,
-                    mont, (char *)sl->ws);
+    rc = fft_stages(ctx, vt, st, p, (const uint32_t *)d_points_affine, (const uint32_t *)d_twiddles, n, (uint32_t *)d_out_xyz,
+                    vec_opts_of(opts), (char *)sl->ws);
     if (rc) return rc;
     return fft_end(ctx, st, *sl);
 }
@@ -3427,14 +3408,12 @@ int amdmsm_group_fft(amdmsm_ctx *ctx, int curve, int group, const void *points_x
     SMV_REFUSE_UNKNOWN(ctx, curve, group);
     GET_VT(ctx, curve, group);
     CHECK_OPTS(ctx, opts);
-    const size_t xyz_bytes = (size_t)vt->el_words * 12, fr_bytes = (size_t)vt->fr_words * 4;
-    if (stride_bytes == 0) stride_bytes = xyz_bytes;
-    if (stride_bytes % rec_align(vt) || stride_bytes < xyz_bytes) return fail(ctx, AMDMSM_ERR_BAD_ARG, "point stride");
-    int rc = fft_check(ctx, n, points_xyz, twiddles, out_xyz);
+    int rc = vec_check_stride(ctx, vt, stride_bytes, "point stride");
+    if (rc) return rc;
+    rc = fft_check(ctx, n, points_xyz, twiddles, out_xyz);
     if (rc || !n) return rc;
     hipStream_t st = ctx->stream;
-    const amdmsm_opts o = opts_or_default(opts);
-    const int mont = o.scalars_plain ? 0 : 1;
+    const size_t xyz_bytes = (size_t)vt->el_words * 12, fr_bytes = (size_t)vt->fr_words * 4;
     const fft_plan p = fft_make_plan(vt, n, chunk_points);
     // the records go up through the staging buffer a piece at a time: two points per butterfly of a chunk
     const size_t piece = n < 2 * p.cn || !p.cn ? n : 2 * p.cn;
@@ -3447,16 +3426,13 @@ int amdmsm_group_fft(amdmsm_ctx *ctx, int curve, int group, const void *points_x
     uint32_t *d_in = (uint32_t *)(ws + p.off_a), *d_res = (uint32_t *)(ws + p.off_xyz);
     for (size_t off = 0; off < n; off += piece) {
         const size_t m = n - off < piece ? n - off : piece;
-        // the last record of a strided vector ends with its coordinates: nothing past them is read
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_src.p, (const char *)points_xyz + off * stride_bytes, (m - 1) * stride_bytes + xyz_bytes,
-                                    hipMemcpyHostToDevice, st));
-        vt->import_bases(st, (const uint32_t *)ctx->hb_src.p, stride_bytes / 4, base_form == AMDMSM_FORM_SPECIAL, m,
-                         d_in + off * (size_t)vt->el_words * 2);
+        rc = vec_upload(ctx, vt, st, points_xyz, stride_bytes, base_form, off, m, d_in + off * (size_t)vt->el_words * 2);
+        if (rc) return rc;
         // the next piece reuses the staging buffer
         if (off + piece < n) HIP_TRY(ctx, hipStreamSynchronize(st));
     }
     if (n > 2) HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_sc.p, twiddles, n / 2 * fr_bytes, hipMemcpyHostToDevice, st));
-    rc = fft_stages(ctx, vt, st, p, d_in, (const uint32_t *)ctx->hb_sc.p, n, d_res, o.out_form, mont, ws);
+    rc = fft_stages(ctx, vt, st, p, d_in, (const uint32_t *)ctx->hb_sc.p, n, d_res, vec_opts_of(opts), ws);
     if (rc) {
         (void)hipDeviceSynchronize();   // nothing of this call may still touch the staging buffers
         return rc;
@@ -3497,7 +3473,7 @@ seg_layout seg_chunk_layout(const group_vtable *vt, bool shared, size_t ct, size
     seg_layout l;
     size_t off = 0;
     l.table = off;
-    if (!shared) off = align_up(off + smv_ws_bytes(vt, ct), 256);   // table and its scratch
+    if (!shared) off = align_up(off + 2 * smv_table_bytes(vt, ct), 256);   // table and its scratch
     l.digits = off;
     off = align_up(off + ct * (size_t)vt->seg_digit_stride, 256);
     l.sums = off;
@@ -3538,8 +3514,7 @@ int seg_check(amdmsm_ctx *ctx, const void *bases, size_t n_bases, const void *sc
 int seg_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_bases, size_t n_bases, const uint32_t *d_scalars,
                     const uint64_t *offsets, size_t m, unsigned flags, size_t long_from, uint32_t *d_out, const amdmsm_opts *opts) {
     hipStream_t st = stream_of(ctx, opts);
-    const int form = opts ? opts->out_form : AMDMSM_OUT_LIBFF;
-    const int mont = (opts && opts->scalars_plain) ? 0 : 1;
+    const vec_opts vo = vec_opts_of(opts);
     const bool shared = (flags & AMDMSM_SEG_SHARED_BASES) != 0;
     if (!long_from) long_from = seg_long_from_default(vt);
     const size_t ew = (size_t)vt->el_words, xyzw = 3 * ew, affw = 2 * ew, frw = (size_t)vt->fr_words;
@@ -3599,8 +3574,8 @@ int seg_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_b
     if (!chunks.empty()) {
         // workspace: descriptors of every chunk | shared table | one chunk's area (the shared table's scratch lies there too)
         const size_t desc_bytes = align_up(desc.size() * 4, 256);
-        const size_t shared_bytes = shared ? align_up(smv_ws_bytes(vt, n_bases) / 2, 256) : 0;
-        if (shared) chunk_area = std::max(chunk_area, smv_ws_bytes(vt, n_bases) / 2);
+        const size_t shared_bytes = shared ? align_up(smv_table_bytes(vt, n_bases), 256) : 0;
+        if (shared) chunk_area = std::max(chunk_area, smv_table_bytes(vt, n_bases));
         ws_slot *sl = nullptr;
         int rc = slot_begin(ctx, st, desc_bytes + shared_bytes + chunk_area, sl);
         if (rc) return rc;
@@ -3630,23 +3605,20 @@ int seg_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_b
             uint32_t *digits = (uint32_t *)(area + l.digits), *sums = (uint32_t *)(area + l.sums);
             uint32_t *winsum = (uint32_t *)(area + l.winsum), *norm = (uint32_t *)(area + l.norm);
             uint32_t *out = d_out + c.j0 * xyzw;
-            if (!shared) vt->smv_table(st, d_bases + c.t0 * affw, c.ct, (uint32_t *)(area + l.table + smv_ws_bytes(vt, c.ct) / 2), table);
+            if (!shared) vt->smv_table(st, d_bases + c.t0 * affw, c.ct, (uint32_t *)(area + l.table + smv_table_bytes(vt, c.ct)), table);
             if (first) record(ctx, *sl, 1, st);
-            vt->seg_digits(st, d_scalars + c.t0 * frw, c.ct, mont, digits);
+            vt->seg_digits(st, d_scalars + c.t0 * frw, c.ct, vo.mont, digits);
             if (first) record(ctx, *sl, 2, st);
             vt->seg_accumulate(st, table, shared ? n_bases : c.ct, digits, d_desc + c.desc, c.ns, sums);
             vt->seg_fold(st, sums, d_desc + c.desc + 4 * c.ns, mc, winsum);
             if (first) record(ctx, *sl, 3, st);
-            vt->seg_horner(st, winsum, mc, form == AMDMSM_OUT_AFFINE ? (int)AMDMSM_OUT_LIBFF : form, out);
+            vt->seg_horner(st, winsum, mc, vo.kernel_form, out);
             if (first) record(ctx, *sl, 4, st);
-            if (form == AMDMSM_OUT_AFFINE) {   // the batch normalisation of amdmsm_batch_to_special, as smv_chunk does it
-                vt->import_bases(st, out, xyzw, 0, mc, norm);
-                vt->export_affine(st, norm, mc, out);
-            }
+            vec_finish(vt, st, vo, out, mc, norm);
             HIP_TRY(ctx, hipGetLastError());
             first = false;
         }
-        rc = smv_end(ctx, st, *sl);
+        rc = slot_end(ctx, st, *sl);
         if (rc) return rc;
     }
     for (size_t j : longs) {
@@ -3688,9 +3660,9 @@ int amdmsm_multi_exp_segments(amdmsm_ctx *ctx, int curve, int group, const void 
     GET_VT(ctx, curve, group);
     CHECK_OPTS(ctx, opts);
     const size_t xyz_bytes = (size_t)vt->el_words * 12, aff_bytes = (size_t)vt->el_words * 8, fr_bytes = (size_t)vt->fr_words * 4;
-    if (base_stride_bytes == 0) base_stride_bytes = xyz_bytes;
-    if (base_stride_bytes % rec_align(vt) || base_stride_bytes < xyz_bytes) return fail(ctx, AMDMSM_ERR_BAD_ARG, "base stride");
-    int rc = seg_check(ctx, bases_xyz, n_bases, scalars, n_terms, offsets, m, flags, out);
+    int rc = vec_check_stride(ctx, vt, base_stride_bytes, "base stride");
+    if (rc) return rc;
+    rc = seg_check(ctx, bases_xyz, n_bases, scalars, n_terms, offsets, m, flags, out);
     if (rc || !m) return rc;
     // only the terms some segment names are staged: offsets are rebased to the first of them
     const bool shared = (flags & AMDMSM_SEG_SHARED_BASES) != 0;
@@ -3711,12 +3683,9 @@ int amdmsm_multi_exp_segments(amdmsm_ctx *ctx, int curve, int group, const void 
     if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->fb.out, m * xyz_bytes);
     if (rc) return rc;
     if (nb) {
-        // the last record of a strided vector ends with its coordinates: nothing past them is read
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_src.p, (const char *)bases_xyz + b0 * base_stride_bytes,
-                                    (nb - 1) * base_stride_bytes + xyz_bytes, hipMemcpyHostToDevice, st));
+        rc = vec_upload(ctx, vt, st, bases_xyz, base_stride_bytes, base_form, b0, nb, ctx->hb_aff.p);
+        if (rc) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(ctx->hb_sc.p, (const char *)scalars + t0 * fr_bytes, nt * fr_bytes, hipMemcpyHostToDevice, st));
-        vt->import_bases(st, (const uint32_t *)ctx->hb_src.p, base_stride_bytes / 4, base_form == AMDMSM_FORM_SPECIAL, nb,
-                         (uint32_t *)ctx->hb_aff.p);
     }
     rc = seg_device_impl(ctx, vt, (const uint32_t *)ctx->hb_aff.p, nb, (const uint32_t *)ctx->hb_sc.p, offs.data(), m, flags,
                          long_from, (uint32_t *)ctx->fb.out.p, &o);

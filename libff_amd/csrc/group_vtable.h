@@ -296,7 +296,8 @@ struct group_vtable {
     // kernel by value -- one signed byte each, digits[row * fold_digit_stride + w], w < W.  glv == 0: row j belongs to
     // P_j and W = seg_windows (the carry digit included: a plain scalar may be any integer of fr_words words);
     // glv != 0: rows 2 j and 2 j + 1 are the halves of the split and belong to P_j and phi(P_j), W windows cover the
-    // split's bound.  FOLD_DIGIT_BYTES bytes are enough for every k.
+    // split's bound.  FOLD_DIGIT_BYTES bytes are enough for every k.  The rows are laid out as seg_digits lays them out,
+    // so fold_digit_stride has the value of seg_digit_stride.
     // fold_ladder: one lane per element and one doubling chain for all rows, from the highest window in which some row
     // has a nonzero digit.  tables: the k tables of smv_table one after the other (smv_entries * n records each);
     // rows = k or 2 k; out: n records in `form` as for smv_ladder.

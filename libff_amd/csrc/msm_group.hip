@@ -3484,6 +3484,17 @@ constexpr int SMV_W = 4;                      // window width
 constexpr int SMV_T = 1 << (SMV_W - 1);       // table entries per element: 1 P .. 2^(w-1) P
 constexpr int SMV_DIGITS = (32 * FRW + SMV_W - 1) / SMV_W + 1;   // the last digit is the carry out of the top window
 static_assert(32 % SMV_W == 0, "the digits are packed whole into 32-bit words");
+// A scalar's digits as a row of signed bytes (segmented MSM, fold): bytes between two rows, whole words
+constexpr int SMV_DS = (SMV_DIGITS + 3) / 4 * 4;
+// row[w] = digit w of W, as the calls of for_each_signed_digit hand them over: `word` gathers four of them and goes out
+// behind the fourth, or behind the last
+AMDMSM_DEV void put_digit_byte(uint32_t* row, uint32_t& word, int w, int W, int32_t d) {
+    word |= ((uint32_t)d & 0xffu) << ((w & 3) * 8);
+    if ((w & 3) == 3 || w == W - 1) {
+        row[w >> 2] = word;
+        word = 0;
+    }
+}
 
 // table[j * n + i] = (j + 1) P_i, affine.  The multiples are built in Jacobian coordinates by repeated mixed addition of
 // P_i (the first addition copies P_i, the second meets the equal point and doubles) and made affine with one inversion per
@@ -3540,14 +3551,10 @@ __global__ void __launch_bounds__(TPB) k_smv_table(const uint32_t* __restrict__ 
 // top: w doublings of the XYZZ accumulator, then the mixed addition of +-table[|d| - 1] -- xyzz_madd, whose equal-point
 // branch doubles with the a != 0 term and whose opposite-point branch gives infinity.  A digit lies in [-2^(w-1),
 // 2^(w-1)), so it is kept as a w-bit two's-complement field; the packed digits are shifted up window by window and no
-// private array is indexed at run time.
-__global__ void __launch_bounds__(TPB) k_smv_ladder(const uint32_t* __restrict__ table, size_t n,
-                                                    const uint32_t* __restrict__ scalars, int mont, int form,
-                                                    uint32_t* __restrict__ out) {
-    const size_t i = gtid();
-    if (i >= n) return;
-    uint32_t s[FRW];
-    load_scalar(s, scalars, i, mont);
+// private array is indexed at run time.  acc, infinity on entry, becomes s * P_i, P_i being element i of the n the table
+// holds; e is the caller's record for the table's entries.
+AMDMSM_DEV void smv_ladder_run(Xyzz<E>& acc, Aff<E>& e, const uint32_t* __restrict__ table, size_t n, size_t i,
+                               const uint32_t (&s)[FRW]) {
     constexpr int PER = 32 / SMV_W;
     constexpr uint32_t DMASK = (1u << SMV_W) - 1u;
     uint32_t rec[FRW];
@@ -3560,9 +3567,6 @@ __global__ void __launch_bounds__(TPB) k_smv_ladder(const uint32_t* __restrict__
         for (int j = 0; j < FRW; ++j) rec[j] |= (w / PER == j) ? f : 0u;
         top |= (w / PER == FRW) ? f : 0u;
     });
-    Xyzz<E> acc;
-    xyzz_set_inf(acc);
-    Aff<E> e;
     // the carry digit is 0 or 1
     if (top) {
         load_aff(e, table + i * AFFW);
@@ -3583,6 +3587,19 @@ __global__ void __launch_bounds__(TPB) k_smv_ladder(const uint32_t* __restrict__
             xyzz_madd(acc, e);
         }
     }
+}
+
+__global__ void __launch_bounds__(TPB) k_smv_ladder(const uint32_t* __restrict__ table, size_t n,
+                                                    const uint32_t* __restrict__ scalars, int mont, int form,
+                                                    uint32_t* __restrict__ out) {
+    const size_t i = gtid();
+    if (i >= n) return;
+    uint32_t s[FRW];
+    load_scalar(s, scalars, i, mont);
+    Xyzz<E> acc;
+    xyzz_set_inf(acc);
+    Aff<E> e;
+    smv_ladder_run(acc, e, table, n, i, s);
     Jac<E> res;
     xyzz_to_jac(res, acc);
     store_out(out + i * XYZW, res, form);
@@ -3594,9 +3611,8 @@ __global__ void __launch_bounds__(TPB) k_smv_ladder(const uint32_t* __restrict__
 // pair instead of one term: it adds +-table[|d| - 1] of every term of its slice -- a slice is a segment, or a piece of
 // a long one -- and no lane doubles anything.  The doublings are paid once per segment, in the Horner chain over its
 // SMV_DIGITS window sums.
-constexpr int SEG_DS = (SMV_DIGITS + 3) / 4 * 4;   // bytes between the digit rows of two terms
 
-// digits[t * SEG_DS + w] = digit w of scalar t as a signed byte: the lanes of one segment, which step through its terms
+// digits[t * SMV_DS + w] = digit w of scalar t as a signed byte: the lanes of one segment, which step through its terms
 // together and differ only in w, read one term's digits from neighbouring bytes.  One pass of its own: recoding inside
 // the accumulation lane would repeat the scalar's Montgomery reduction SMV_DIGITS times per term.
 __global__ void __launch_bounds__(TPB) k_seg_digits(const uint32_t* __restrict__ scalars, size_t n, int mont,
@@ -3605,15 +3621,9 @@ __global__ void __launch_bounds__(TPB) k_seg_digits(const uint32_t* __restrict__
     if (i >= n) return;
     uint32_t s[FRW];
     load_scalar(s, scalars, i, mont);
-    uint32_t* row = digits + i * (SEG_DS / 4);
+    uint32_t* row = digits + i * (SMV_DS / 4);
     uint32_t word = 0;
-    for_each_signed_digit(s, SMV_W, SMV_DIGITS, [&](int w, int32_t d) {
-        word |= ((uint32_t)d & 0xffu) << ((w & 3) * 8);
-        if ((w & 3) == 3 || w == SMV_DIGITS - 1) {
-            row[w >> 2] = word;
-            word = 0;
-        }
-    });
+    for_each_signed_digit(s, SMV_W, SMV_DIGITS, [&](int w, int32_t d) { put_digit_byte(row, word, w, SMV_DIGITS, d); });
 }
 
 // Lane L = slice * SMV_DIGITS + w.  slices[s] = (first term, end term, table column of the first term, -): terms count
@@ -3633,10 +3643,10 @@ __global__ void __launch_bounds__(TPB) k_seg_accumulate(const uint32_t* __restri
     Xyzz<E> acc;
     xyzz_set_inf(acc);
     Aff<E> e;
-    const signed char* dp = digits + (size_t)s.x * SEG_DS + w;
+    const signed char* dp = digits + (size_t)s.x * SMV_DS + w;
     size_t col = s.z;
 #pragma unroll 1
-    for (uint32_t t = s.x; t < s.y; ++t, ++col, dp += SEG_DS) {
+    for (uint32_t t = s.x; t < s.y; ++t, ++col, dp += SMV_DS) {
         const int d = *dp;
         if (d) {
             const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
@@ -3732,13 +3742,12 @@ void launch_seg_horner(hipStream_t st, const uint32_t* winsum, size_t m, int for
 // above the highest nonzero digit are skipped by everybody, and no branch on a digit diverges.  Every P_j has the
 // ladder's table (k_smv_table); with the endomorphism split each scalar gives two half-length rows, and the row of
 // phi(P_j) reads P_j's table with x scaled by beta.
-constexpr int FOLD_DS = (SMV_DIGITS + 3) / 4 * 4;   // bytes between two digit rows
-static_assert(2 * FOLD_MAX_K * FOLD_DS <= (int)FOLD_DIGIT_BYTES, "the digit rows fit the buffer the engine sets aside");
+static_assert(2 * FOLD_MAX_K * SMV_DS <= (int)FOLD_DIGIT_BYTES, "the digit rows fit the buffer the engine sets aside");
 struct alignas(16) fold_scalars {
     uint32_t w[FOLD_MAX_K * FRW];
 };
 
-// One lane per scalar.  digits[row * FOLD_DS + w] = digit w of the row as a signed byte, whole words written: without
+// One lane per scalar.  digits[row * SMV_DS + w] = digit w of the row as a signed byte, whole words written: without
 // the split row j holds the SMV_DIGITS digits of scalar j (the carry digit included), with it rows 2 j and 2 j + 1
 // hold the W digits of its halves, which belong to P_j and phi(P_j).
 __global__ void __launch_bounds__(64) k_fold_digits(const fold_scalars sc, int k, int mont, int glv, int W,
@@ -3748,13 +3757,7 @@ __global__ void __launch_bounds__(64) k_fold_digits(const fold_scalars sc, int k
     uint32_t s[FRW];
     load_scalar(s, sc.w, (size_t)j, mont);
     uint32_t word = 0;
-    auto put = [&](int row, int w, int32_t d) {
-        word |= ((uint32_t)d & 0xffu) << ((w & 3) * 8);
-        if ((w & 3) == 3 || w == W - 1) {
-            digits[row * (FOLD_DS / 4) + (w >> 2)] = word;
-            word = 0;
-        }
-    };
+    auto put = [&](int row, int w, int32_t d) { put_digit_byte(digits + row * (SMV_DS / 4), word, w, W, d); };
     if (glv) {
         if constexpr (GP::HAS_ENDO) for_each_glv_digit(s, SMV_W, W, [&](int h, int w, int32_t d) { put(2 * j + h, w, d); });
     } else {
@@ -3776,7 +3779,7 @@ __global__ void __launch_bounds__(TPB) k_fold_ladder(const uint32_t* __restrict_
     for (int q = (W + 3) / 4 - 1; q >= 0 && top < 0; --q) {
         uint32_t any = 0;   // a byte of it is nonzero where some row has a nonzero digit in window 4 q + byte
 #pragma unroll 1
-        for (int r = 0; r < rows; ++r) any |= digits[r * (FOLD_DS / 4) + q];
+        for (int r = 0; r < rows; ++r) any |= digits[r * (SMV_DS / 4) + q];
         if (any) top = 4 * q + (31 - __clz((int)any)) / 8;
     }
     const signed char* dg = (const signed char*)digits;
@@ -3791,7 +3794,7 @@ __global__ void __launch_bounds__(TPB) k_fold_ladder(const uint32_t* __restrict_
         }
 #pragma unroll 1
         for (int r = 0; r < rows; ++r) {
-            const int d = dg[r * FOLD_DS + w];
+            const int d = dg[r * SMV_DS + w];
             if (d) {
                 const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
                 const size_t t = (size_t)(glv ? r >> 1 : r);
@@ -3832,10 +3835,10 @@ __global__ void __launch_bounds__(TPB) k_fft_gather(const uint32_t* __restrict__
     reinterpret_cast<uint4*>(dst)[t] = reinterpret_cast<const uint4*>(in + ib * AFFW)[part];
 }
 
-// One lane per butterfly b0 + i.  LADDER: T = w B by the ladder of k_smv_ladder -- its recoding, its loop, its live
-// state -- over the table of the chunk's B operands; else T = B.  Only then A is loaded, and both results go through the
-// complete mixed addition: T + A, and A - T as -(T + (-A)).  Infinite A or T, A = T (xyzz_madd doubles, with the a != 0
-// term) and A = -T take xyzz_madd's own branches.  out: libff records b and b + half of the stage's result vector.
+// One lane per butterfly b0 + i.  LADDER: T = w B by smv_ladder_run over the table of the chunk's B operands; else
+// T = B.  Only then A is loaded, and both results go through the complete mixed addition: T + A, and A - T as
+// -(T + (-A)).  Infinite A or T, A = T (xyzz_madd doubles, with the a != 0 term) and A = -T take xyzz_madd's own
+// branches.  out: libff records b and b + half of the stage's result vector.
 template <bool LADDER>
 __global__ void __launch_bounds__(TPB) k_fft_butterfly(const uint32_t* __restrict__ table, size_t cn,
                                                        const uint32_t* __restrict__ in, size_t b0, int rsh,
@@ -3850,38 +3853,7 @@ __global__ void __launch_bounds__(TPB) k_fft_butterfly(const uint32_t* __restric
     if constexpr (LADDER) {
         uint32_t s[FRW];
         load_scalar(s, twiddles, (b >> rsh) << rsh, mont);
-        constexpr int PER = 32 / SMV_W;
-        constexpr uint32_t DMASK = (1u << SMV_W) - 1u;
-        uint32_t rec[FRW];
-        uint32_t top = 0;
-#pragma unroll
-        for (int j = 0; j < FRW; ++j) rec[j] = 0;
-        for_each_signed_digit(s, SMV_W, SMV_DIGITS, [&](int w, int32_t d) {
-            const uint32_t f = ((uint32_t)d & DMASK) << ((w % PER) * SMV_W);
-#pragma unroll
-            for (int j = 0; j < FRW; ++j) rec[j] |= (w / PER == j) ? f : 0u;
-            top |= (w / PER == FRW) ? f : 0u;
-        });
-        // the carry digit is 0 or 1
-        if (top) {
-            load_aff(e, table + i * AFFW);
-            xyzz_madd(acc, e);
-        }
-#pragma unroll 1
-        for (int w = SMV_DIGITS - 2; w >= 0; --w) {
-#pragma unroll 1
-            for (int k = 0; k < SMV_W; ++k) xyzz_dbl(acc, acc);
-            const uint32_t f = rec[FRW - 1] >> (32 - SMV_W);
-#pragma unroll
-            for (int j = FRW - 1; j >= 0; --j) rec[j] = (rec[j] << SMV_W) | (j ? rec[j - 1] >> (32 - SMV_W) : 0u);
-            const bool neg = (f >> (SMV_W - 1)) != 0;
-            const uint32_t mag = neg ? (1u << SMV_W) - f : f;
-            if (mag) {
-                load_aff(e, table + ((size_t)(mag - 1) * cn + i) * AFFW);
-                el_cneg(e.y, e.y, neg);
-                xyzz_madd(acc, e);
-            }
-        }
+        smv_ladder_run(acc, e, table, cn, i, s);
     } else {
         load_aff(e, in + (ia + ((size_t)1 << rsh)) * AFFW);
         xyzz_madd(acc, e);
@@ -4384,10 +4356,10 @@ const group_vtable g_vt = {
     l_gen_bases_seq, l_export_affine, l_ffi_decode_points, l_ffi_decode_scalars, l_ffi_encode_point, l_disk_decode, l_disk_decode_compressed, l_fixed_base_exp, l_field_op, l_group_op, l_digits, l_mul_bench, l_madd_bench,
     GP::HAS_ENDO ? 1 : 0, GP::COEFF_A != 0 ? 1 : 0, l_sort_sel, l_gather_scalars, l_scalar_bits, l_sort_short,
     SMV_T, l_smv_table, l_smv_ladder,
-    SMV_DIGITS, SEG_DS, l_seg_digits, l_seg_accumulate, l_seg_fold, l_seg_horner,
+    SMV_DIGITS, SMV_DS, l_seg_digits, l_seg_accumulate, l_seg_fold, l_seg_horner,
     l_field_probe, l_xyzz_probe,
     l_sort_top_window,
-    FOLD_DS, l_fold_digits, l_fold_ladder,
+    SMV_DS, l_fold_digits, l_fold_ladder,
     l_fft_gather, l_fft_butterfly, FR::P,
 };
 

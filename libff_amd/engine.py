@@ -344,6 +344,21 @@ def _np_ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _records(a, stride_bytes, g_bytes):
+    """libff records in the array ``a``, ``stride_bytes`` apart (None: the rows of a packed 2-d array)"""
+    if stride_bytes is None:
+        return int(a.shape[0]) if a.ndim == 2 else 0
+    return (a.nbytes - g_bytes) // stride_bytes + 1 if a.nbytes >= g_bytes else 0
+
+
+def _result_array(out, rows, g_bytes):
+    """``out``, or a fresh array when the caller gave none: ``rows`` libff records"""
+    if out is None:
+        out = np.zeros((rows, g_bytes // 8), dtype=np.uint64)
+    assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape == (rows, g_bytes // 8)
+    return out
+
+
 class Engine:
     """One amdmsm context (device, stream, workspace).  Fails loudly without a GPU."""
 
@@ -691,9 +706,7 @@ class Engine:
         points = np.ascontiguousarray(points, dtype=np.uint64)
         scalars = np.ascontiguousarray(scalars, dtype=np.uint64)
         n = scalars.shape[0]
-        if out is None:
-            out = np.zeros((n, s["g_bytes"] // 8), dtype=np.uint64)
-        assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape == (n, s["g_bytes"] // 8)
+        out = _result_array(out, n, s["g_bytes"])
         if n:
             assert scalars.shape == (n, s["fr_bytes"] // 8), "scalars must be (n, fr_limbs) uint64"
             if stride_bytes is None:
@@ -723,14 +736,8 @@ class Engine:
         offs = np.ascontiguousarray(offsets, dtype=np.uint64)
         m = max(int(offs.shape[0]) - 1, 0)
         n_terms = int(scalars.shape[0])
-        gl = s["g_bytes"] // 8
-        if stride_bytes is None:
-            n_bases = int(bases.shape[0]) if bases.ndim == 2 else 0
-        else:
-            n_bases = (bases.nbytes - s["g_bytes"]) // stride_bytes + 1 if bases.nbytes >= s["g_bytes"] else 0
-        if out is None:
-            out = np.zeros((m, gl), dtype=np.uint64)
-        assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape == (m, gl)
+        n_bases = _records(bases, stride_bytes, s["g_bytes"])
+        out = _result_array(out, m, s["g_bytes"])
         if n_terms:
             assert scalars.shape == (n_terms, s["fr_bytes"] // 8), "scalars must be (n_terms, fr_limbs) uint64"
         o = self._opts(out_form=out_form, scalars_plain=scalars_plain)
@@ -761,13 +768,8 @@ class Engine:
         vecs = [np.ascontiguousarray(p, dtype=np.uint64) for p in points_list]
         scalars = np.ascontiguousarray(scalars, dtype=np.uint64)
         k = len(vecs)
-        if stride_bytes is None:
-            n = int(vecs[0].shape[0]) if k and vecs[0].ndim == 2 else 0
-        else:
-            n = (vecs[0].nbytes - s["g_bytes"]) // stride_bytes + 1 if k and vecs[0].nbytes >= s["g_bytes"] else 0
-        if out is None:
-            out = np.zeros((n, gl), dtype=np.uint64)
-        assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape == (n, gl)
+        n = _records(vecs[0], stride_bytes, s["g_bytes"]) if k else 0
+        out = _result_array(out, n, s["g_bytes"])
         if n:
             assert scalars.shape == (k, s["fr_bytes"] // 8), "scalars must be (k, fr_limbs) uint64"
             for v in vecs:
@@ -795,14 +797,9 @@ class Engine:
         s = sizes(curve, group)
         gl = s["g_bytes"] // 8
         points = np.ascontiguousarray(points, dtype=np.uint64)
-        if stride_bytes is None:
-            n = int(points.shape[0]) if points.ndim == 2 else 0
-        else:
-            n = (points.nbytes - s["g_bytes"]) // stride_bytes + 1 if points.nbytes >= s["g_bytes"] else 0
+        n = _records(points, stride_bytes, s["g_bytes"])
         tw = None if twiddles is None else np.ascontiguousarray(twiddles, dtype=np.uint64)
-        if out is None:
-            out = np.zeros((n, gl), dtype=np.uint64)
-        assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape == (n, gl)
+        out = _result_array(out, n, s["g_bytes"])
         if n and stride_bytes is None:
             assert points.shape == (n, gl), "points must be (n, 3*coord_limbs) uint64"
         if tw is not None and tw.size:
