@@ -271,6 +271,62 @@ int amdmsm_plan_group_fft(int curve, int group, size_t n, size_t chunk_points, s
 /* the scalar-field modulus r of the group: fr_bytes, little-endian words, plain integer; no context */
 int amdmsm_fr_modulus(int curve, int group, void *r_plain);
 
+/* Radix-2 FFT over a vector of Fr scalars -- the transforms in front of a prover's large MSMs, so that the scalars stay
+ * in device memory from the witness evaluations to the MSM result:
+ *   out[j] = post^j * scale * sum over i < n of pre^i * a_i * w^(i j),   j < n,   n a power of two, at most 2^28
+ * Fr belongs to the curve, so these entries take no group; all six curve ids are served, AMDMSM_CURVE_MNT6 included.
+ *   values, out  n Fr records of fr_bytes (amdmsm_sizes of the curve's G1), natural order in and out: libff's in-memory
+ *                Fr, canonical Montgomery residues below r, or with opts->scalars_plain plain integers below r -- the
+ *                data, the output and the four parameters alike; the conversion happens at the first load and the last
+ *                store.  A record >= r gives an unspecified value; it never causes an access outside out.
+ *                Device entry: d_out == d_values is allowed (the transform then runs in place); any other overlap of
+ *                the two ranges is AMDMSM_ERR_BAD_ARG.  The kernels move the 32- and 48-byte records 16 bytes at a
+ *                time and the 40-byte records of MNT4 / MNT6 8 bytes at a time: d_values and d_out must be aligned to
+ *                16 and 8 bytes respectively (what amdmsm_malloc and hipMalloc return is), or the call is
+ *                AMDMSM_ERR_BAD_ARG; the same holds for the device vectors of amdmsm_fr_powers_device and
+ *                amdmsm_fr_muladd_device.  The host entry's arrays need no alignment
+ *   omega        a primitive n-th root of unity, one record in host memory (amdmsm_fr_root_of_unity gives libff's); may
+ *                be NULL when n <= 1.  Checked on the host: omega^(n/2) must be r - 1
+ *   pre, post, scale   one record each in host memory, NULL = 1.  All NULL: libfqfft's FFT.  pre = g: the coset FFT by
+ *                g.  omega^-1 and scale = n^-1: the inverse FFT; with post = g^-1 as well: the inverse coset FFT.  The
+ *                library has no Fr inversion: the caller supplies the inverses
+ *   tile_log2    butterfly stages of one global pass, 0 = the default; amdmsm_plan_fr_fft reports the range
+ * A transform is ceil(log2 n / tile) passes; a pass reads every record once and writes it once, pre^i is applied as the
+ * first pass loads and post^j * scale as the last pass stores.  Workspace, from the context's slots: one vector of n
+ * records (two for an in-place call of an odd number of passes above one; the host entry adds the uploaded vector),
+ * and the powers of pre and post a pass needs: (n >> stages) + 2^stages records of its first / last pass.  The n / 2
+ * powers of omega are kept with the context for the last two (curve, n, omega) it served and freed with it.
+ * n = 0 succeeds and writes nothing; n = 1 writes scale * a_0.
+ * AMDMSM_ERR_UNSUPPORTED for an unknown curve.  AMDMSM_ERR_BAD_ARG, with amdmsm_last_error naming the condition, before
+ * anything is launched or written: n not a power of two, a null vector pointer with n > 0, null omega with n > 1, an
+ * omega with omega^(n/2) != r - 1 (which every n above the field's 2-adicity fails), a nonzero tile_log2 outside the
+ * plan's range, a wrong opts->struct_size, ranges that overlap without being equal, a misaligned device vector.  AMDMSM_ERR_TOO_LARGE for
+ * n > 2^28.  These are looked at before the context is.
+ * With timing enabled (amdmsm_get_timings): [0] the powers of omega, pre and post (host entry: with the upload), [1] the
+ * passes, [2] the download (host entry), [AMDMSM_PH_TOTAL] the call. */
+int amdmsm_fr_fft(amdmsm_ctx *ctx, int curve, const void *values, size_t n, const void *omega, const void *pre,
+                  const void *post, const void *scale, int tile_log2, const amdmsm_opts *opts, void *out);
+/* the same on device-resident vectors (omega, pre, post, scale stay in host memory); enqueued on opts->stream (or the
+   context's), not synchronised */
+int amdmsm_fr_fft_device(amdmsm_ctx *ctx, int curve, const void *d_values, size_t n, const void *omega, const void *pre,
+                         const void *post, const void *scale, int tile_log2, const amdmsm_opts *opts, void *d_out);
+/* read-only, no context: out[0] = tile (log2) in use, out[1] / out[2] = smallest / largest tile the unit supports,
+   out[3] = global passes, out[4] = butterflies (n / 2 * log2 n), out[5] = workspace bytes of an out-of-place device
+   call with pre and post given.  AMDMSM_ERR_BAD_ARG for n not a power of two or a tile out of range,
+   AMDMSM_ERR_TOO_LARGE above 2^28 */
+int amdmsm_plan_fr_fft(int curve, size_t n, int tile_log2, size_t out[6]);
+/* libff's get_root_of_unity<Fr>(2^log2_n) -- Fr::root_of_unity squared s - log2_n times, s the 2-adicity of r - 1 -- as
+   a plain integer of fr_bytes; no context.  AMDMSM_ERR_BAD_ARG beyond s */
+int amdmsm_fr_root_of_unity(int curve, int log2_n, void *r_plain_out);
+/* d_out[i] = base^i, i < n (any n): the builder of the transform's twiddles, which also gives amdmsm_group_fft_device
+   its twiddles and amdmsm_scalar_mul_vec_device the powers of a coset generator.  base: one record in host memory;
+   records in the form opts->scalars_plain says.  Enqueued, not synchronised */
+int amdmsm_fr_powers_device(amdmsm_ctx *ctx, int curve, const void *base, size_t n, const amdmsm_opts *opts, void *d_out);
+/* d_out[i] = (a_i * b_i - c_i) * k, i < n: the element-wise step between the coset transforms of a quotient.  d_c and k
+   (one record in host memory) may be NULL: 0 and 1.  d_out may be any of the inputs.  Enqueued, not synchronised */
+int amdmsm_fr_muladd_device(amdmsm_ctx *ctx, int curve, size_t n, const void *d_a, const void *d_b, const void *d_c,
+                            const void *k, const amdmsm_opts *opts, void *d_out);
+
 /* Segmented MSM: m sums in one call, out[j] = sum of scalars[i] * base(i) over offsets[j] <= i < offsets[j + 1] -- the
  * shape of k proofs verified as a batch (sum of input_i * IC_i per proof), of row or column commitments, of the cross
  * terms of an inner-product argument.  A single MSM per segment would pay the fixed cost of its launch chain m times;

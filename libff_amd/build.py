@@ -1,7 +1,8 @@
 """Build libff_amd/libamdmsm.so for gfx950 with hipcc (in-tree, no JIT cache).
 
 One translation unit per (curve, group) pair -- msm_group.hip compiled with
--DAMDMSM_GROUP=... -- plus the host engine; the eight device TUs build in parallel.
+-DAMDMSM_GROUP=... -- one per scalar field -- fr_ntt.hip compiled with -DAMDMSM_FR=... --
+plus the host engine; the device TUs build in parallel.
 Objects are cached under libff_amd/csrc/build/ keyed by source mtimes.
 """
 import concurrent.futures
@@ -66,11 +67,14 @@ for _g in ("mnt4_g1", "mnt6_g1"):
     GROUP_FLAGS[_g] = GROUP_FLAGS[_g] + ["-DAMDMSM_COLD_INLINE=1", "-DAMDMSM_ACC_WAVES=3"]
 # MNT4 G2 (Fq2 = Fq[u]/(u^2 - 17), a' = 34): the 32-bit loop with whole Fq2 elements per lane, two waves per SIMD
 GROUP_FLAGS["mnt4_g2"] = GROUP_FLAGS["mnt4_g2"] + ["-DAMDMSM_ACC_WAVES=2"]
+# scalar-field units (fr_ntt.hip: the FFT over Fr, its powers and product step), one per curve id
+FR_UNITS = {"alt_bn128": 0, "bls12_377": 1, "bw6_761": 2, "bls12_381": 3, "mnt4": 4, "mnt6": 5}
 ARCH = "gfx950"
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I" + INCLUDE, "-I" + CSRC,
           "-Wno-unused-result"]
 DEVICE_DEPS = ["msm_group.hip", "rr.cuh", "rr_chain.inc", "fp.cuh", "fp2.cuh", "fp2h.cuh", "ec.cuh", "wide.cuh", "wide28.cuh", "mac_chain.inc", "curve_params.h", "group_vtable.h", os.path.join(HERE, "build.py")]
-HOST_DEPS = ["engine.cpp", "ffi.cpp", "engine_internal.h", "group_vtable.h", os.path.join(INCLUDE, "amdmsm.h"),
+FR_DEPS = ["fr_ntt.hip", "fp.cuh", "curve_params.h", "fr_vtable.h", os.path.join(HERE, "build.py")]
+HOST_DEPS = ["engine.cpp", "ffi.cpp", "engine_internal.h", "group_vtable.h", "fr_vtable.h", os.path.join(INCLUDE, "amdmsm.h"),
              os.path.join(INCLUDE, "libff_amd_ffi.h")]
 
 
@@ -114,6 +118,12 @@ def build(force=False, verbose=True, jobs=None):
             own = [f for f in GROUP_FLAGS.get(g, []) if f.split("=")[0] not in names]
             tasks.append([cc, *COMMON, "-c", os.path.join(CSRC, "msm_group.hip"),
                           f"-DAMDMSM_GROUP={g}", f"-DAMDMSM_VT=vt_{g}", *own, *extra, "-o", o])
+    for c, cid in FR_UNITS.items():
+        o = os.path.join(OBJ, f"fr_{c}.o")
+        objs.append(o)
+        if force or _newer(o, FR_DEPS):
+            tasks.append([cc, *COMMON, "-c", os.path.join(CSRC, "fr_ntt.hip"), f"-DAMDMSM_FR={c}_fr",
+                          f"-DAMDMSM_FR_VT=frvt_{c}", f"-DAMDMSM_FR_CURVE={cid}", "-o", o])
     # AMDMSM_FFI_NO_REFERENCE_SYMBOLS=1: leave out the reference's own FFI names (<curve>_init / _g1_add /
     # _g1_mul, include/libff_amd_ffi.h) so that the library can sit next to libff-ffi
     no_ref = os.environ.get("AMDMSM_FFI_NO_REFERENCE_SYMBOLS", "0") not in ("", "0")

@@ -1,9 +1,11 @@
 // Host side of the amdmsm C ABI (include/amdmsm.h): context, workspace, the MSM
-// pipeline schedule and the host-buffer entry points.  All arithmetic happens in
-// the kernels of msm_group.hip; there is no CPU arithmetic path in this library.
+// pipeline schedule and the host-buffer entry points.  All arithmetic on vectors happens in
+// the kernels of msm_group.hip and fr_ntt.hip; there is no CPU arithmetic path in this library
+// (the scalar FFT's host side squares its handful of parameters, nothing more).
 #include "../../include/amdmsm.h"
 #include "engine_internal.h"
 #include "group_vtable.h"
+#include "fr_vtable.h"
 
 #include <hip/hip_runtime.h>
 
@@ -16,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -89,6 +92,16 @@ struct stream_state {
     hipStream_t streams[NB] = {};
 };
 
+// the n / 2 powers of omega a scalar FFT has used, kept for the next one over the same domain (amdmsm_fr_fft)
+struct fr_tw_entry {
+    int curve = -1;
+    size_t n = 0;
+    uint32_t omega[amdmsm::FR_MAX_WORDS] = {};
+    grow_buf buf;
+    hipEvent_t ev = nullptr;   // behind the last call that built or read buf
+    uint64_t last_use = 0;
+};
+
 struct amdmsm_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -133,6 +146,8 @@ struct amdmsm_ctx {
     size_t fft_marks = 0;
     long long fft_ticket = -1;
     float aux_ms[4] = {};
+    fr_tw_entry fr_tw[2];                         // a prover alternates omega and omega^-1 over one domain
+    uint64_t fr_clock = 0;
     std::string err;
     std::recursive_mutex mu;                      // one call at a time per context (entries nest)
 };
@@ -1160,6 +1175,10 @@ void amdmsm_ctx_destroy(amdmsm_ctx *ctx) {
             if (e) (void)hipEventDestroy(e);
         }
         for (auto &e : ctx->fft_ev) (void)hipEventDestroy(e);
+        for (auto &t : ctx->fr_tw) {
+            if (t.buf.p) (void)hipFree(t.buf.p);
+            if (t.ev) (void)hipEventDestroy(t.ev);
+        }
         for (int b = 0; b < stream_state::NB; ++b) {
             if (ctx->ss.h_stage[b]) (void)hipHostFree(ctx->ss.h_stage[b]);
             if (ctx->ss.streams[b]) (void)hipStreamDestroy(ctx->ss.streams[b]);
@@ -3343,8 +3362,9 @@ int fft_stages(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, const ff
     return AMDMSM_OK;
 }
 
-int fft_begin(amdmsm_ctx *ctx, hipStream_t st, const fft_plan &p, ws_slot *&sl) {
-    const int rc = slot_begin(ctx, st, p.ws_bytes, sl);
+// the slot and the first mark of a call whose phases are marked (group_fft, fr_fft); the last mark and the end of the call
+int fft_begin(amdmsm_ctx *ctx, hipStream_t st, size_t ws_bytes, ws_slot *&sl) {
+    const int rc = slot_begin(ctx, st, ws_bytes, sl);
     if (rc) return rc;
     ctx->fft_marks = 0;
     ctx->fft_ticket = -1;
@@ -3352,8 +3372,8 @@ int fft_begin(amdmsm_ctx *ctx, hipStream_t st, const fft_plan &p, ws_slot *&sl) 
     fft_mark(ctx, st, 0);
     return AMDMSM_OK;
 }
-int fft_end(amdmsm_ctx *ctx, hipStream_t st, ws_slot &sl) {
-    fft_mark(ctx, st, 3, true);
+int fft_end(amdmsm_ctx *ctx, hipStream_t st, ws_slot &sl, int last_phase = 3) {
+    fft_mark(ctx, st, last_phase, true);
     if (ctx->timing) ctx->fft_ticket = (long long)ctx->ticket;   // the ticket slot_end hands out
     return slot_end(ctx, st, sl);
 }
@@ -3395,7 +3415,7 @@ int amdmsm_group_fft_device(amdmsm_ctx *ctx, int curve, int group, const void *d
     hipStream_t st = stream_of(ctx, opts);
     const fft_plan p = fft_make_plan(vt, n, chunk_points);
     ws_slot *sl = nullptr;
-    rc = fft_begin(ctx, st, p, sl);
+    rc = fft_begin(ctx, st, p.ws_bytes, sl);
     if (rc) return rc;
     rc = fft_stages(ctx, vt, st, p, (const uint32_t *)d_points_affine, (const uint32_t *)d_twiddles, n, (uint32_t *)d_out_xyz,
                     vec_opts_of(opts), (char *)sl->ws);
@@ -3420,7 +3440,7 @@ int amdmsm_group_fft(amdmsm_ctx *ctx, int curve, int group, const void *points_x
     rc = ensure_buf(ctx, ctx->hb_src, piece * stride_bytes);
     if (rc == AMDMSM_OK && n > 2) rc = ensure_buf(ctx, ctx->hb_sc, n / 2 * fr_bytes);
     ws_slot *sl = nullptr;
-    if (rc == AMDMSM_OK) rc = fft_begin(ctx, st, p, sl);
+    if (rc == AMDMSM_OK) rc = fft_begin(ctx, st, p.ws_bytes, sl);
     if (rc) return rc;
     char *ws = (char *)sl->ws;
     uint32_t *d_in = (uint32_t *)(ws + p.off_a), *d_res = (uint32_t *)(ws + p.off_xyz);
@@ -3699,6 +3719,393 @@ int amdmsm_multi_exp_segments(amdmsm_ctx *ctx, int curve, int group, const void 
         return rc ? rc : fail(ctx, AMDMSM_ERR_HIP, hipGetErrorString(e));
     }
     memcpy(out, h_out.data(), m * xyz_bytes);
+    return AMDMSM_OK;
+}
+
+}  // extern "C"
+
+// ---- radix-2 FFT over a vector of Fr scalars: out[j] = post^j scale sum_i pre^i a_i w^(i j) --------------------------------
+namespace {
+
+using fr_getter = const fr_vtable *(*)();
+const fr_vtable *find_frvt(int curve) {
+    static const fr_getter getters[] = {frvt_alt_bn128, frvt_bls12_377, frvt_bw6_761, frvt_bls12_381, frvt_mnt4, frvt_mnt6};
+    for (fr_getter g : getters) {
+        if (!g) continue;
+        const fr_vtable *v = g();
+        if (v->curve == curve) return v;
+    }
+    return nullptr;
+}
+
+// The host's share of the arithmetic: a handful of Montgomery products on 32-bit words (the root check, the squarings
+// behind the power tables), on the constants the field's unit exports.  Operands are words of the field's width;
+// a canonical result for canonical operands, some value below 2^(32 words) for any others.
+struct fr_rec {
+    uint32_t v[FR_MAX_WORDS] = {};
+};
+fr_rec fr_mul(const fr_vtable *f, const fr_rec &a, const fr_rec &b) {
+    const int N = f->words;
+    const uint32_t *p = f->modulus;
+    uint32_t t[FR_MAX_WORDS + 2] = {};
+    for (int i = 0; i < N; ++i) {
+        uint64_t c = 0;
+        for (int j = 0; j < N; ++j) {
+            const uint64_t s = (uint64_t)a.v[j] * b.v[i] + t[j] + c;
+            t[j] = (uint32_t)s;
+            c = s >> 32;
+        }
+        uint64_t s = (uint64_t)t[N] + c;
+        t[N] = (uint32_t)s;
+        t[N + 1] = (uint32_t)(s >> 32);
+        const uint32_t m = t[0] * f->inv;
+        c = ((uint64_t)m * p[0] + t[0]) >> 32;
+        for (int j = 1; j < N; ++j) {
+            s = (uint64_t)m * p[j] + t[j] + c;
+            t[j - 1] = (uint32_t)s;
+            c = s >> 32;
+        }
+        s = (uint64_t)t[N] + c;
+        t[N - 1] = (uint32_t)s;
+        t[N] = t[N + 1] + (uint32_t)(s >> 32);
+        t[N + 1] = 0;
+    }
+    bool ge = t[N] != 0;
+    if (!ge) {
+        ge = true;
+        for (int j = N - 1; j >= 0; --j) {
+            if (t[j] != p[j]) {
+                ge = t[j] > p[j];
+                break;
+            }
+        }
+    }
+    fr_rec r;
+    uint64_t borrow = 0;
+    for (int j = 0; j < N; ++j) {
+        const uint64_t d = (uint64_t)t[j] - (ge ? p[j] : 0) - borrow;
+        r.v[j] = (uint32_t)d;
+        borrow = (d >> 63) & 1u;
+    }
+    return r;
+}
+fr_rec fr_from_words(const fr_vtable *f, const uint32_t *w) {
+    fr_rec r;
+    memcpy(r.v, w, (size_t)f->words * 4);
+    return r;
+}
+bool fr_same(const fr_vtable *f, const fr_rec &a, const fr_rec &b) { return memcmp(a.v, b.v, (size_t)f->words * 4) == 0; }
+// a caller's record as a Montgomery residue
+fr_rec fr_read(const fr_vtable *f, const void *rec, bool plain) {
+    const fr_rec r = fr_from_words(f, (const uint32_t *)rec);
+    return plain ? fr_mul(f, r, fr_from_words(f, f->r2)) : r;
+}
+// base^(2^(shift + b)), b < FR_POW_TABLE, packed records of the field's width: what fr_vtable::powers takes for the
+// powers of base^(2^shift)
+std::vector<uint32_t> fr_pow_table(const fr_vtable *f, fr_rec x, int shift) {
+    std::vector<uint32_t> t((size_t)FR_POW_TABLE * f->words);
+    for (int b = 0; b < shift; ++b) x = fr_mul(f, x, x);
+    for (int b = 0; b < FR_POW_TABLE; ++b) {
+        memcpy(&t[(size_t)b * f->words], x.v, (size_t)f->words * 4);
+        x = fr_mul(f, x, x);
+    }
+    return t;
+}
+
+constexpr size_t FR_FFT_MAX_N = (size_t)1 << 28;
+int log2_exact(size_t n) {
+    int l = 0;
+    while (((size_t)1 << l) < n) ++l;
+    return l;
+}
+
+// The passes of a transform: `tile` stages each, the last one the rest.  The workspace: one vector, the four vectors of
+// powers of pre and post, and behind them the second vector that only an in-place call of an odd number of passes
+// above one needs (frfft_ws_bytes).
+struct frfft_plan {
+    int log_n = 0, tile = 0, passes = 1, t_first = 0, t_last = 0;
+    size_t rec = 0, vec = 0, off_w2 = 0, off_pre_col = 0, off_pre_row = 0, off_post_col = 0, off_post_row = 0, ws_all = 0, ws_plain = 0;
+};
+int frfft_make_plan(const fr_vtable *f, size_t n, int tile_log2, frfft_plan &p) {
+    if (tile_log2 && (tile_log2 < FR_TILE_MIN || tile_log2 > FR_TILE_MAX)) return AMDMSM_ERR_BAD_ARG;
+    p.log_n = log2_exact(n ? n : 1);
+    p.tile = tile_log2 ? tile_log2 : FR_TILE_DEFAULT;
+    p.passes = p.log_n ? (p.log_n + p.tile - 1) / p.tile : 1;
+    p.t_first = std::min(p.tile, p.log_n);
+    p.t_last = p.log_n - (p.passes - 1) * p.tile;
+    p.rec = (size_t)f->words * 4;
+    p.vec = align_up((n ? n : 1) * p.rec, 256);
+    p.off_pre_col = p.vec;
+    p.off_pre_row = p.off_pre_col + align_up((n >> p.t_first) * p.rec, 256);
+    p.off_post_col = p.off_pre_row + align_up(((size_t)1 << p.t_first) * p.rec, 256);
+    p.off_post_row = p.off_post_col + align_up((n >> p.t_last) * p.rec, 256);
+    p.off_w2 = p.off_post_row + align_up(((size_t)1 << p.t_last) * p.rec, 256);
+    p.ws_plain = p.off_w2;           // without the second vector
+    p.ws_all = p.off_w2 + p.vec;
+    return AMDMSM_OK;
+}
+
+bool frfft_third(const frfft_plan &p, bool in_place) { return in_place && p.passes > 1 && p.passes % 2 == 1; }
+size_t frfft_ws_bytes(const frfft_plan &p, bool in_place) { return frfft_third(p, in_place) ? p.ws_all : p.ws_plain; }
+
+// what a call is given, as Montgomery residues
+struct frfft_params {
+    bool plain = false, has_pre = false, has_post = false, has_scale = false;
+    fr_rec omega, pre, post, scale;
+};
+
+// The argument rules both entries share; no device is needed and nothing is launched or written before they hold.
+int frfft_check(amdmsm_ctx *ctx, const fr_vtable *f, const void *values, size_t n, const void *omega, const void *pre,
+                const void *post, const void *scale, int tile_log2, const amdmsm_opts *opts, const void *out, frfft_plan &plan,
+                frfft_params &pr) {
+    if (n & (n - 1)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "n = " + std::to_string(n) + " is not a power of two");
+    if (n > FR_FFT_MAX_N) return fail(ctx, AMDMSM_ERR_TOO_LARGE, "n = " + std::to_string(n) + ": at most 2^28 records");
+    if (frfft_make_plan(f, n, tile_log2, plan))
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "tile_log2 = " + std::to_string(tile_log2) + ": 0 or " + std::to_string(FR_TILE_MIN) +
+                                                 " .. " + std::to_string(FR_TILE_MAX));
+    if (n && !values) return fail(ctx, AMDMSM_ERR_BAD_ARG, "values: null pointer");
+    if (n && !out) return fail(ctx, AMDMSM_ERR_BAD_ARG, "output: null pointer");
+    if (n > 1 && !omega) return fail(ctx, AMDMSM_ERR_BAD_ARG, "omega: null pointer");
+    pr.plain = opts && opts->scalars_plain;
+    if (n > 1) {
+        pr.omega = fr_read(f, omega, pr.plain);
+        fr_rec x = pr.omega, minus_one;   // -1 as a Montgomery residue: r - R
+        uint64_t borrow = 0;
+        for (int j = 0; j < f->words; ++j) {
+            const uint64_t d = (uint64_t)f->modulus[j] - f->one[j] - borrow;
+            minus_one.v[j] = (uint32_t)d;
+            borrow = (d >> 63) & 1u;
+        }
+        for (int b = 0; b + 1 < plan.log_n; ++b) x = fr_mul(f, x, x);
+        if (!fr_same(f, x, minus_one))
+            return fail(ctx, AMDMSM_ERR_BAD_ARG, "omega is not a primitive n-th root of unity: omega^(n/2) != r - 1 (n = 2^" +
+                                                     std::to_string(plan.log_n) + ", 2-adicity of r - 1: " + std::to_string(f->two_adicity) + ")");
+    }
+    pr.has_pre = pre != nullptr && n > 1;
+    pr.has_post = post != nullptr && n > 1;
+    pr.has_scale = scale != nullptr;
+    if (pre) pr.pre = fr_read(f, pre, pr.plain);
+    if (post) pr.post = fr_read(f, post, pr.plain);
+    pr.scale = scale ? fr_read(f, scale, pr.plain) : fr_from_words(f, f->one);
+    return AMDMSM_OK;
+}
+
+// the n / 2 powers of omega, from the context's two most recent or built now; the caller records e->ev when it is done
+int frfft_twiddles(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, size_t n, const frfft_params &pr, fr_tw_entry *&e) {
+    fr_tw_entry *hit = nullptr, *lru = &ctx->fr_tw[0];
+    for (auto &t : ctx->fr_tw) {
+        if (t.curve == f->curve && t.n == n && memcmp(t.omega, pr.omega.v, (size_t)f->words * 4) == 0) hit = &t;
+        if (t.last_use < lru->last_use) lru = &t;
+    }
+    e = hit ? hit : lru;
+    e->last_use = ++ctx->fr_clock;
+    if (!e->ev) HIP_TRY(ctx, hipEventCreateWithFlags(&e->ev, hipEventDisableTiming));
+    // the build, or the last reader on another stream, comes first
+    if (e->curve >= 0) HIP_TRY(ctx, hipStreamWaitEvent(st, e->ev, 0));
+    if (hit) return AMDMSM_OK;
+    e->curve = -1;   // not a valid entry until the powers are enqueued
+    const int rc = ensure_buf(ctx, e->buf, n / 2 * (size_t)f->words * 4);
+    if (rc) return rc;
+    const std::vector<uint32_t> table = fr_pow_table(f, pr.omega, 0);
+    f->powers(st, table.data(), nullptr, 0, n / 2, (uint32_t *)e->buf.p);
+    HIP_TRY(ctx, hipGetLastError());
+    // behind the build at once: whatever becomes of this call, a later one on another stream waits for the powers
+    HIP_TRY(ctx, hipEventRecord(e->ev, st));
+    e->curve = f->curve;
+    e->n = n;
+    memcpy(e->omega, pr.omega.v, sizeof(e->omega));
+    return AMDMSM_OK;
+}
+
+// The transform on device-resident vectors, n >= 1; ws: frfft_plan's workspace.  Marks the phases of a timed call.
+int frfft_run(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, const frfft_plan &p, const frfft_params &pr,
+              const uint32_t *d_in, uint32_t *d_out, size_t n, char *ws) {
+    fr_tw_entry *tw = nullptr;
+    if (n > 1) {
+        const int rc = frfft_twiddles(ctx, f, st, n, pr, tw);
+        if (rc) return rc;
+    }
+    uint32_t *pre_col = (uint32_t *)(ws + p.off_pre_col), *pre_row = (uint32_t *)(ws + p.off_pre_row);
+    uint32_t *post_col = (uint32_t *)(ws + p.off_post_col), *post_row = (uint32_t *)(ws + p.off_post_row);
+    if (pr.has_pre) {   // pre^c, c < n >> t_first, and pre^((n >> t_first) k), k < 2^t_first
+        f->powers(st, fr_pow_table(f, pr.pre, 0).data(), nullptr, 0, n >> p.t_first, pre_col);
+        f->powers(st, fr_pow_table(f, pr.pre, p.log_n - p.t_first).data(), nullptr, 0, (size_t)1 << p.t_first, pre_row);
+    }
+    if (pr.has_post) {   // post^q, q < n >> t_last, and scale post^((n >> t_last) k), k < 2^t_last
+        f->powers(st, fr_pow_table(f, pr.post, 0).data(), nullptr, 0, n >> p.t_last, post_col);
+        f->powers(st, fr_pow_table(f, pr.post, p.log_n - p.t_last).data(), pr.scale.v, 0, (size_t)1 << p.t_last, post_row);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    fft_mark(ctx, st, 1);
+    // pass k of P reads what pass k - 1 wrote; the last one writes d_out, and no pass reads and writes one vector --
+    // except a lone pass, which is one workgroup that loads everything before it stores anything
+    uint32_t *w1 = (uint32_t *)ws, *w2 = (uint32_t *)(ws + p.off_w2);
+    const bool third = frfft_third(p, d_in == d_out);
+    const uint32_t *src = d_in;
+    int log_s = 0;
+    for (int k = 0; k < p.passes; ++k) {
+        const bool first = k == 0, last = k == p.passes - 1;
+        const int t = last ? p.t_last : p.tile;
+        uint32_t *dst = last ? d_out : ((p.passes - 1 - k) % 2 == 1 ? w1 : (third ? w2 : d_out));
+        fr_pass a = {};
+        a.in = src;
+        a.out = dst;
+        a.tw = tw ? (const uint32_t *)tw->buf.p : nullptr;
+        a.pre_col = first && pr.has_pre ? pre_col : nullptr;
+        a.pre_row = pre_row;
+        a.post_col = last && pr.has_post ? post_col : nullptr;
+        a.post_row = post_row;
+        a.log_n = p.log_n;
+        a.log_r = t;
+        a.log_s = log_s;
+        a.log_c = std::min(FR_LDS_LOG2 - t, p.log_n - t);
+        a.in_plain = first && pr.plain;
+        a.out_plain = last && pr.plain;
+        a.has_scale = last && pr.has_scale && !pr.has_post;
+        memcpy(a.scale, pr.scale.v, sizeof(a.scale));
+        f->pass(st, a);
+        src = dst;
+        log_s += t;
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    if (tw) HIP_TRY(ctx, hipEventRecord(tw->ev, st));
+    return AMDMSM_OK;
+}
+
+// device vectors are moved 16 bytes at a time, 8 for the 10-word fields (fp_load / fp_store)
+bool fr_misaligned(const fr_vtable *f, std::initializer_list<const void *> ptrs) {
+    const uintptr_t mask = f->words % 4 ? 7 : 15;
+    for (const void *p : ptrs)
+        if ((uintptr_t)p & mask) return true;
+    return false;
+}
+bool ranges_overlap(const void *a, const void *b, size_t bytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + bytes && y < x + bytes;
+}
+
+#define FR_ENTER(ctx)                                                 \
+    if (!ctx) return AMDMSM_ERR_BAD_ARG;                              \
+    std::lock_guard<std::recursive_mutex> lock_(ctx->mu);             \
+    dev_guard guard_(ctx->device)
+
+}   // namespace
+
+extern "C" {
+
+int amdmsm_plan_fr_fft(int curve, size_t n, int tile_log2, size_t out[6]) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return AMDMSM_ERR_UNSUPPORTED;
+    if (!out || (n & (n - 1))) return AMDMSM_ERR_BAD_ARG;
+    if (n > FR_FFT_MAX_N) return AMDMSM_ERR_TOO_LARGE;
+    frfft_plan p;
+    if (frfft_make_plan(f, n, tile_log2, p)) return AMDMSM_ERR_BAD_ARG;
+    out[0] = (size_t)p.tile;
+    out[1] = FR_TILE_MIN;
+    out[2] = FR_TILE_MAX;
+    out[3] = (size_t)p.passes;
+    out[4] = n / 2 * (size_t)p.log_n;
+    out[5] = p.ws_plain;
+    return AMDMSM_OK;
+}
+
+int amdmsm_fr_root_of_unity(int curve, int log2_n, void *r_plain_out) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return AMDMSM_ERR_UNSUPPORTED;
+    if (!r_plain_out || log2_n < 0 || log2_n > f->two_adicity) return AMDMSM_ERR_BAD_ARG;
+    fr_rec x = fr_from_words(f, f->root);
+    for (int b = f->two_adicity; b > log2_n; --b) x = fr_mul(f, x, x);
+    fr_rec one;
+    one.v[0] = 1;
+    x = fr_mul(f, x, one);   // out of Montgomery form
+    memcpy(r_plain_out, x.v, (size_t)f->words * 4);
+    return AMDMSM_OK;
+}
+
+int amdmsm_fr_fft_device(amdmsm_ctx *ctx, int curve, const void *d_values, size_t n, const void *omega, const void *pre,
+                         const void *post, const void *scale, int tile_log2, const amdmsm_opts *opts, void *d_out) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
+    CHECK_OPTS(ctx, opts);
+    frfft_plan p;
+    frfft_params pr;
+    int rc = frfft_check(ctx, f, d_values, n, omega, pre, post, scale, tile_log2, opts, d_out, p, pr);
+    if (rc) return rc;
+    if (n && fr_misaligned(f, {d_values, d_out}))
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_values / d_out: not aligned to " + std::to_string(f->words % 4 ? 8 : 16) + " bytes");
+    if (n && d_values != d_out && ranges_overlap(d_values, d_out, n * p.rec))
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_values and d_out overlap without being the same vector");
+    FR_ENTER(ctx);
+    if (!n) return AMDMSM_OK;
+    hipStream_t st = stream_of(ctx, opts);
+    ws_slot *sl = nullptr;
+    rc = fft_begin(ctx, st, frfft_ws_bytes(p, d_values == d_out), sl);
+    if (rc) return rc;
+    rc = frfft_run(ctx, f, st, p, pr, (const uint32_t *)d_values, (uint32_t *)d_out, n, (char *)sl->ws);
+    if (rc) return rc;
+    return fft_end(ctx, st, *sl, 1);
+}
+
+int amdmsm_fr_fft(amdmsm_ctx *ctx, int curve, const void *values, size_t n, const void *omega, const void *pre, const void *post,
+                  const void *scale, int tile_log2, const amdmsm_opts *opts, void *out) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
+    CHECK_OPTS(ctx, opts);
+    frfft_plan p;
+    frfft_params pr;
+    int rc = frfft_check(ctx, f, values, n, omega, pre, post, scale, tile_log2, opts, out, p, pr);
+    if (rc) return rc;
+    FR_ENTER(ctx);
+    if (!n) return AMDMSM_OK;
+    hipStream_t st = ctx->stream;
+    ws_slot *sl = nullptr;
+    // the uploaded vector in front of the device entry's workspace; the transform runs in place on it
+    rc = fft_begin(ctx, st, p.vec + frfft_ws_bytes(p, true), sl);
+    if (rc) return rc;
+    uint32_t *d_vec = (uint32_t *)sl->ws;
+    HIP_TRY(ctx, hipMemcpyAsync(d_vec, values, n * p.rec, hipMemcpyHostToDevice, st));
+    rc = frfft_run(ctx, f, st, p, pr, d_vec, d_vec, n, (char *)sl->ws + p.vec);
+    if (rc) {
+        (void)hipDeviceSynchronize();   // nothing of this call may still read the caller's vector
+        return rc;
+    }
+    fft_mark(ctx, st, 2);
+    HIP_TRY(ctx, hipMemcpyAsync(out, d_vec, n * p.rec, hipMemcpyDeviceToHost, st));
+    rc = fft_end(ctx, st, *sl, 2);
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return rc;
+}
+
+int amdmsm_fr_powers_device(amdmsm_ctx *ctx, int curve, const void *base, size_t n, const amdmsm_opts *opts, void *d_out) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
+    CHECK_OPTS(ctx, opts);
+    if (n && (!base || !d_out)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null pointer");
+    if (n > ((size_t)1 << 32)) return fail(ctx, AMDMSM_ERR_TOO_LARGE, "n = " + std::to_string(n) + ": at most 2^32 records");
+    if (n && fr_misaligned(f, {d_out})) return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_out: misaligned");
+    FR_ENTER(ctx);
+    if (!n) return AMDMSM_OK;
+    const bool plain = opts && opts->scalars_plain;
+    f->powers(stream_of(ctx, opts), fr_pow_table(f, fr_read(f, base, plain), 0).data(), nullptr, plain ? 1 : 0, n, (uint32_t *)d_out);
+    HIP_TRY(ctx, hipGetLastError());
+    return AMDMSM_OK;
+}
+
+int amdmsm_fr_muladd_device(amdmsm_ctx *ctx, int curve, size_t n, const void *d_a, const void *d_b, const void *d_c,
+                            const void *k, const amdmsm_opts *opts, void *d_out) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
+    CHECK_OPTS(ctx, opts);
+    if (n && (!d_a || !d_b || !d_out)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null pointer");
+    if (n && fr_misaligned(f, {d_a, d_b, d_c, d_out})) return fail(ctx, AMDMSM_ERR_BAD_ARG, "a device vector is misaligned");
+    FR_ENTER(ctx);
+    if (!n) return AMDMSM_OK;
+    const bool plain = opts && opts->scalars_plain;
+    fr_rec kk;
+    if (k) kk = fr_read(f, k, plain);
+    f->muladd(stream_of(ctx, opts), n, (const uint32_t *)d_a, (const uint32_t *)d_b, (const uint32_t *)d_c, k ? kk.v : nullptr,
+              plain ? 1 : 0, (uint32_t *)d_out);
+    HIP_TRY(ctx, hipGetLastError());
     return AMDMSM_OK;
 }
 

@@ -1,0 +1,50 @@
+// Host-visible interface of one scalar-field translation unit (fr_ntt.hip, compiled once per curve with
+// -DAMDMSM_FR=<curve>_fr): the field's constants for the host-side parameter arithmetic of engine.cpp and launchers of
+// the three kernels.  Every record that crosses this interface on the host side is a Montgomery residue below r.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace amdmsm {
+
+constexpr int FR_MAX_WORDS = 12;
+constexpr int FR_LDS_LOG2 = 10;        // records of one LDS tile (log2), every field: 32 / 40 / 48 KiB
+constexpr int FR_TILE_MIN = 4, FR_TILE_MAX = 8, FR_TILE_DEFAULT = 8;   // butterfly stages per global pass
+constexpr int FR_POW_TABLE = 17;       // base^(2^b), b = 0 .. 16: what k_fr_powers is given
+
+// one global pass of the transform (k_fr_fft_pass): log_r in-LDS stages on tiles of 2^log_c neighbouring columns
+struct fr_pass {
+    const uint32_t* in;
+    uint32_t* out;
+    const uint32_t* tw;         // n / 2 powers of omega, Montgomery
+    const uint32_t* pre_col;    // first pass, pre given: pre^c, c < n >> log_r;  else null
+    const uint32_t* pre_row;    //                        pre^((n >> log_r) k), k < 2^log_r
+    const uint32_t* post_col;   // last pass, post given: post^q, q < 2^log_s;  else null
+    const uint32_t* post_row;   //                        scale * post^(k << log_s), k < 2^log_r
+    int log_n, log_r, log_s, log_c;
+    int in_plain, out_plain;    // conversion at the first load / the last store
+    int has_scale;              // last pass, scale given and post not: every result times scale
+    uint32_t scale[FR_MAX_WORDS];
+};
+
+struct fr_vtable {
+    int curve, words, two_adicity;
+    uint32_t inv;                                  // -r^-1 mod 2^32
+    const uint32_t *modulus, *one, *r2, *root;     // r, R mod r, R^2 mod r, libff's Fr::root_of_unity (Montgomery)
+    // d_out[i] = first * base^i, i < n.  table: FR_POW_TABLE host records base^(2^b); first: a host record or null (1)
+    void (*powers)(hipStream_t, const uint32_t* table, const uint32_t* first, int out_plain, size_t n, uint32_t* d_out);
+    void (*pass)(hipStream_t, const fr_pass&);
+    // d_out[i] = (a_i * b_i - c_i) * k; d_c, k: null for 0 and 1.  k: a host record
+    void (*muladd)(hipStream_t, size_t n, const uint32_t* d_a, const uint32_t* d_b, const uint32_t* d_c, const uint32_t* k,
+                   int plain, uint32_t* d_out);
+};
+
+const fr_vtable* frvt_alt_bn128() __attribute__((weak));
+const fr_vtable* frvt_bls12_377() __attribute__((weak));
+const fr_vtable* frvt_bw6_761() __attribute__((weak));
+const fr_vtable* frvt_bls12_381() __attribute__((weak));
+const fr_vtable* frvt_mnt4() __attribute__((weak));
+const fr_vtable* frvt_mnt6() __attribute__((weak));
+
+}  // namespace amdmsm

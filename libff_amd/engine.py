@@ -66,6 +66,8 @@ EXPORTED_SYMBOLS = [
     "amdmsm_multi_exp_segments", "amdmsm_msm_device_segments", "amdmsm_set_segments_chunk_terms",
     "amdmsm_fold_vec", "amdmsm_fold_vec_device", "amdmsm_plan_fold",
     "amdmsm_group_fft", "amdmsm_group_fft_device", "amdmsm_plan_group_fft", "amdmsm_fr_modulus",
+    "amdmsm_fr_fft", "amdmsm_fr_fft_device", "amdmsm_plan_fr_fft", "amdmsm_fr_root_of_unity", "amdmsm_fr_powers_device",
+    "amdmsm_fr_muladd_device",
 ]
 SEG_SHARED_BASES = 1            # include/amdmsm.h AMDMSM_SEG_SHARED_BASES
 SEG_LONG_NEVER = 2 ** 64 - 1    # long_from = SIZE_MAX: no segment takes the single-MSM route
@@ -266,6 +268,38 @@ def fft_twiddles(curve, n, inverse=False):
         buf += x.to_bytes(8 * limbs, "little")
         x = x * w % r
     return np.frombuffer(bytes(buf), dtype="<u8").astype(np.uint64).reshape(n // 2, limbs)
+
+
+def plan_fr_fft(curve, n, tile_log2=0):
+    """What ``Engine.fr_fft`` runs for ``n`` scalars (``amdmsm_plan_fr_fft``, read-only): butterfly stages per global pass,
+    the smallest and largest such tile the unit supports, global passes, butterflies and workspace bytes."""
+    out = (ctypes.c_size_t * 6)()
+    rc = load_library().amdmsm_plan_fr_fft(curve, ctypes.c_size_t(n), int(tile_log2), out)
+    if rc:
+        raise AmdMsmError(f"amdmsm_plan_fr_fft: {rc}")
+    return {"tile_log2": out[0], "tile_min": out[1], "tile_max": out[2], "passes": out[3], "butterflies": out[4],
+            "workspace_bytes": out[5]}
+
+
+def fr_root_of_unity(curve, n):
+    """libff's ``get_root_of_unity<Fr>(n)`` (``amdmsm_fr_root_of_unity``), as an int: what ``basic_radix2_domain`` of size
+    ``n`` uses.  ValueError where n is no power of two or exceeds the 2-part of r - 1."""
+    n = int(n)
+    if n < 1 or n & (n - 1):
+        raise ValueError(f"n = {n} is not a power of two")
+    w = (ctypes.c_uint8 * sizes(curve, G1)["fr_bytes"])()
+    rc = load_library().amdmsm_fr_root_of_unity(curve, n.bit_length() - 1, w)
+    if rc:
+        raise ValueError(f"n = {n}: no n-th root of unity in Fr of {CURVE_NAMES.get(curve, curve)} ({rc})")
+    return int.from_bytes(bytes(w), "little")
+
+
+def _fr_record(x, limbs, r, plain):
+    """the int ``x`` as one Fr record: plain, or libff's Montgomery residue with R = 2^(64 limbs)"""
+    x = int(x) % r
+    if not plain:
+        x = x * (1 << (64 * limbs)) % r
+    return np.frombuffer(x.to_bytes(8 * limbs, "little"), dtype="<u8").astype(np.uint64)
 
 
 def endomorphism_info(curve, group):
@@ -812,6 +846,47 @@ class Engine:
         self._check(rc, "amdmsm_group_fft")
         return out
 
+    def _fr_params(self, curve, n, omega, inverse, coset, plain, given=(None, None, None)):
+        """(omega, pre, post, scale) records of a transform of ``n`` scalars; the inverses are Python's.  ``given``: the
+        caller's own (pre, post, scale) of the general form, each taking the place of the derived one"""
+        r = fr_modulus(curve, G1)
+        limbs = sizes(curve, G1)["fr_bytes"] // 8
+        w = (fr_root_of_unity(curve, n) if omega is None else int(omega)) if n > 1 else None
+        pre = post = scale = None
+        if inverse:
+            w = None if w is None else pow(w, -1, r)
+            scale = pow(n, -1, r) if n else None
+            post = None if coset is None else pow(int(coset), -1, r)
+        elif coset is not None:
+            pre = int(coset)
+        pre, post, scale = [d if g is None else int(g) for d, g in zip((pre, post, scale), given)]
+        return [None if x is None else _fr_record(x, limbs, r, plain) for x in (w, pre, post, scale)]
+
+    def fr_fft(self, curve, values, omega=None, inverse=False, coset=None, plain=False, tile_log2=0, out=None, *,
+               pre=None, post=None, scale=None):
+        """Radix-2 FFT over a vector of Fr scalars (``amdmsm_fr_fft``): ``out[j] = sum_i values[i] w^(i j)``, n a power
+        of two, natural order in and out.  ``values``: (n, fr_limbs) uint64 Montgomery residues, with ``plain`` plain
+        integers.  ``omega`` (an int): a primitive n-th root of unity, None = ``fr_root_of_unity(curve, n)``, libff's.
+        ``coset`` (an int g): the coset FFT -- values[i] times g^i first.  ``inverse``: w^-1 and the scale n^-1, with
+        ``coset`` also g^-j on the way out: the inverse of the two above.  ``tile_log2``: stages per global pass, 0 =
+        default (``plan_fr_fft`` tells).  ``pre``, ``post``, ``scale`` (ints): the general form
+        ``out[j] = post^j scale sum_i pre^i values[i] w^(i j)``, each in place of what the flags derive."""
+        limbs = sizes(curve, G1)["fr_bytes"] // 8
+        values = np.ascontiguousarray(values, dtype=np.uint64)
+        n = int(values.shape[0]) if values.ndim == 2 else 0
+        if n:
+            assert values.shape == (n, limbs), "values must be (n, fr_limbs) uint64"
+        if out is None:
+            out = np.zeros((n, limbs), dtype=np.uint64)
+        assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape == (n, limbs)
+        w, pre, post, scale = self._fr_params(curve, n, omega, inverse, coset, plain, (pre, post, scale))
+        o = self._opts(scalars_plain=plain)
+        ptr = lambda a: None if a is None else _np_ptr(a)
+        rc = self.lib.amdmsm_fr_fft(self.h, curve, _np_ptr(values) if n else None, ctypes.c_size_t(n), ptr(w), ptr(pre),
+                                    ptr(post), ptr(scale), int(tile_log2), ctypes.byref(o), _np_ptr(out) if n else None)
+        self._check(rc, "amdmsm_fr_fft")
+        return out
+
     def batch_exp_timings(self):
         """device times (ms) of the last batch_exp: inputs H2D, window table (0 = reused), exponentiations, results D2H"""
         ms = (ctypes.c_float * 4)()
@@ -953,6 +1028,37 @@ class Engine:
                                                      ctypes.c_size_t(n), None if d_twiddles is None else _vp(d_twiddles),
                                                      None if d_out_xyz is None else _vp(d_out_xyz),
                                                      ctypes.c_size_t(chunk_points), ctypes.byref(o)), "amdmsm_group_fft_device")
+
+    def fr_fft_device(self, curve, d_values, n, d_out, omega=None, inverse=False, coset=None, plain=False, tile_log2=0,
+                      stream=None, *, pre=None, post=None, scale=None):
+        """``fr_fft`` on ``n`` device-resident records; ``d_out`` may be ``d_values`` (in place); enqueued on ``stream``,
+        not synchronised."""
+        w, pre, post, scale = self._fr_params(curve, n, omega, inverse, coset, plain, (pre, post, scale))
+        o = self._opts(scalars_plain=plain, stream=stream)
+        ptr = lambda a: None if a is None else _np_ptr(a)
+        self._check(self.lib.amdmsm_fr_fft_device(self.h, curve, None if d_values is None else _vp(d_values),
+                                                  ctypes.c_size_t(n), ptr(w), ptr(pre), ptr(post), ptr(scale), int(tile_log2),
+                                                  ctypes.byref(o), None if d_out is None else _vp(d_out)),
+                    "amdmsm_fr_fft_device")
+
+    def fr_powers_device(self, curve, base, n, d_out, plain=False, stream=None):
+        """``d_out[i] = base^i`` for i < n (``amdmsm_fr_powers_device``; ``base`` an int): twiddles for
+        ``group_fft_device``, coset powers for ``scalar_mul_vec_device``; enqueued on ``stream``, not synchronised."""
+        limbs = sizes(curve, G1)["fr_bytes"] // 8
+        b = _fr_record(base, limbs, fr_modulus(curve, G1), plain)
+        o = self._opts(scalars_plain=plain, stream=stream)
+        self._check(self.lib.amdmsm_fr_powers_device(self.h, curve, _np_ptr(b), ctypes.c_size_t(n), ctypes.byref(o),
+                                                     None if d_out is None else _vp(d_out)), "amdmsm_fr_powers_device")
+
+    def fr_muladd_device(self, curve, n, d_a, d_b, d_out, d_c=None, k=None, plain=False, stream=None):
+        """``d_out[i] = (a_i * b_i - c_i) * k`` (``amdmsm_fr_muladd_device``; ``d_c`` None = 0, ``k`` an int, None = 1);
+        ``d_out`` may be any input; enqueued on ``stream``, not synchronised."""
+        limbs = sizes(curve, G1)["fr_bytes"] // 8
+        kk = None if k is None else _fr_record(k, limbs, fr_modulus(curve, G1), plain)
+        o = self._opts(scalars_plain=plain, stream=stream)
+        self._check(self.lib.amdmsm_fr_muladd_device(self.h, curve, ctypes.c_size_t(n), _vp(d_a), _vp(d_b),
+                                                     None if d_c is None else _vp(d_c), None if kk is None else _np_ptr(kk),
+                                                     ctypes.byref(o), _vp(d_out)), "amdmsm_fr_muladd_device")
 
     def msm_device_segments(self, curve, group, d_bases_affine, n_bases, d_scalars, n_terms, offsets, d_out, *,
                             shared_bases=False, long_from=0, out_form=OUT_LIBFF, scalars_plain=False, chunk_terms=0,

@@ -19,6 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 CURVES = {
     "alt_bn128": dict(
+        fr_gen=5,   # Fr::multiplicative_generator
         id=0,
         r=0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001,
         q=0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47,
@@ -36,6 +37,7 @@ CURVES = {
         ),
     ),
     "bls12_377": dict(
+        fr_gen=22,   # Fr::multiplicative_generator
         id=1,
         r=0x12AB655E9A2CA55660B44D1E5C37B00159AA76FED00000010A11800000000001,
         q=0x1AE3A4617C510EAC63B05C06CA1493B1A22D9F300F5138F1EF3622FBA094800170B5D44300000008508C00000000001,
@@ -63,6 +65,7 @@ CURVES = {
         ),
     ),
     "bw6_761": dict(
+        fr_gen=15,   # Fr::multiplicative_generator
         id=2,
         r=0x1AE3A4617C510EAC63B05C06CA1493B1A22D9F300F5138F1EF3622FBA094800170B5D44300000008508C00000000001,
         q=0x122E824FB83CE0AD187C94004FAFF3EB926186A81D14688528275EF8087BE41707BA638E584E91903CEBAFF25B423048689C8ED12F9FD9071DCD3DC73EBFF2E98A116C25667A8F8160CF8AEEAF0A437E6913E6870000082F49D00000000008B,
@@ -82,6 +85,7 @@ CURVES = {
         ),
     ),
     "bls12_381": dict(
+        fr_gen=7,   # Fr::multiplicative_generator
         id=3,
         r=0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001,
         q=0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB,
@@ -112,7 +116,7 @@ MNT46_A = int("475922286169261325753349249653048451545124878552" "82351555326773
 MNT46_B = int("475922286169261325753349249653048451545124879242" "694725395555128576210262817955800483758081")
 MNT_CURVES = {
     "mnt4": dict(
-        id=4, r=MNT46_A, q=MNT46_B, coords="projective",
+        id=4, fr_gen=10, r=MNT46_A, q=MNT46_B, coords="projective",
         g1=dict(deg=1, a=2,
                 x=[int("60760244141852568949126569781626075788424196370144486719385562" "369396875346601926534016838")],
                 y=[int("36373285070258297826390277081514578445974772235707184397110767" "4179038674942891694705904306")],
@@ -128,7 +132,7 @@ MNT_CURVES = {
                    int("4246214795988938826723931903374206805975846958923171976461" "13820787463109735345923009077489")]),
     ),
     "mnt6": dict(
-        id=5, r=MNT46_B, q=MNT46_A, coords="projective",
+        id=5, fr_gen=17, r=MNT46_B, q=MNT46_A, coords="projective",
         g1=dict(deg=1, a=11,
                 x=[int("33668575288308222810928984635393710418569820937140417834296883" "8739115829740084426881123453")],
                 y=[int("40259629013978098970933270771656892077762203207376274986234237" "4583908837063963736098549800")],
@@ -359,7 +363,7 @@ def emit_device_header():
     w("")
     done_fields = {}
 
-    def emit_field(name, p):
+    def emit_field(name, p, gen=None):
         if name in done_fields:
             return
         f = field(p)
@@ -385,11 +389,19 @@ def emit_device_header():
           "// (p+1)/4 if SQRT_S == 1, else (t-1)/2")
         w(f"    static constexpr uint32_t NQR_TO_T[{n}] = {c_arr(limbs(nqr_t, n, 32), '0x%08xu')};   "
           "// (non-residue)^t, Montgomery form (SQRT_S > 1)")
+        if gen is not None:
+            # Fr::root_of_unity = multiplicative_generator^t, a primitive 2^s-th root of unity (get_root_of_unity squares
+            # it down to the domain size); equal to NQR_TO_T only where the generator is the non-residue chosen above
+            assert pow(gen, (p - 1) // 2, p) == p - 1 and sq_s > 1
+            root = pow(gen, t, p)
+            assert pow(root, 1 << (sq_s - 1), p) == p - 1
+            w(f"    static constexpr uint32_t ROOT_OF_UNITY[{n}] = {c_arr(limbs(root * f['R'] % p, n, 32), '0x%08xu')};   "
+              f"// {gen}^t, Montgomery form: Fr::root_of_unity")
         w("};")
         w("")
 
     for cname, c in {**CURVES, **MNT_CURVES}.items():
-        emit_field(f"{cname}_fr", c["r"])
+        emit_field(f"{cname}_fr", c["r"], c["fr_gen"])
         emit_field(f"{cname}_fq", c["q"])
     glv = {}
     for cname, c in CURVES.items():

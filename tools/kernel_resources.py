@@ -3,6 +3,7 @@
 hipcc's -Rpass-analysis=kernel-resource-usage remarks (device-only compile, nothing is linked).
 
   python tools/kernel_resources.py alt_bn128_g1 [k_accumulate ...]
+  python tools/kernel_resources.py fr_alt_bn128 [k_fr_fft_pass ...]     a scalar-field unit (fr_ntt.hip)
 """
 import os
 import re
@@ -17,9 +18,14 @@ from libff_amd import build as b  # noqa: E402
 def main():
     group = sys.argv[1]
     want = sys.argv[2:]
-    cmd = [b.hipcc(), *b.COMMON, "--offload-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
-           os.path.join(b.CSRC, "msm_group.hip"), f"-DAMDMSM_GROUP={group}", f"-DAMDMSM_VT=vt_{group}",
-           *b.GROUP_FLAGS.get(group, []), "-o", "/dev/null"]
+    if group.startswith("fr_") and group[3:] in b.FR_UNITS:
+        c = group[3:]
+        unit = [os.path.join(b.CSRC, "fr_ntt.hip"), f"-DAMDMSM_FR={c}_fr", f"-DAMDMSM_FR_VT=frvt_{c}",
+                f"-DAMDMSM_FR_CURVE={b.FR_UNITS[c]}"]
+    else:
+        unit = [os.path.join(b.CSRC, "msm_group.hip"), f"-DAMDMSM_GROUP={group}", f"-DAMDMSM_VT=vt_{group}",
+                *b.GROUP_FLAGS.get(group, [])]
+    cmd = [b.hipcc(), *b.COMMON, "--offload-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", *unit, "-o", "/dev/null"]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode:
         sys.exit(r.stderr[-3000:])
