@@ -327,6 +327,59 @@ int amdmsm_fr_powers_device(amdmsm_ctx *ctx, int curve, const void *base, size_t
 int amdmsm_fr_muladd_device(amdmsm_ctx *ctx, int curve, size_t n, const void *d_a, const void *d_b, const void *d_c,
                             const void *k, const amdmsm_opts *opts, void *d_out);
 
+/* Sparse matrix times Fr vector -- the rows <A_i, z>, <B_i, z>, <C_i, z> of a constraint system on a resident
+ * assignment, the vectors the transforms above start from -- and any other sparse linear map over Fr:
+ *     out[i] = sum over offsets[i] <= k < offsets[i + 1] of coeffs[k] * x[cols[k]]  (mod r),   i < n_rows
+ *     out[i] = 0,                                                                              n_rows <= i < n_out
+ * The matrix is given once, in CSR form, and kept in HBM in a form of the library's own; an apply
+ * reads the vector and writes canonical records, bit for bit the sum taken with integers.
+ *   offsets   n_rows + 1 values, offsets[0] = 0, not decreasing; offsets[n_rows] = nnz <= 2^31
+ *   cols      nnz columns below n_cols, in any order within a row; a column may repeat, its terms add
+ *   coeffs    nnz Fr records below r: Montgomery residues, or with coeffs_plain != 0 plain integers.  A zero
+ *             coefficient contributes nothing (it is dropped at the load)
+ *   n_rows, n_cols  at most 2^28 each; 0 rows and 0 entries are valid
+ * amdmsm_fr_matrix_load validates the arrays, rearranges them on the host, uploads the result and returns a handle that
+ * belongs to the context; it synchronises.  AMDMSM_ERR_UNSUPPORTED for an unknown curve (looked at before the context);
+ * AMDMSM_ERR_BAD_ARG, with amdmsm_last_error naming the row or entry, before anything is allocated or uploaded, for
+ * offsets[0] != 0, a decreasing offset, a column >= n_cols, a coefficient >= r, a null array with work to do;
+ * AMDMSM_ERR_TOO_LARGE above the limits.  AMDMSM_FR_MATRIX_NAIVE=1 in the environment of the load keeps the CSR arrays
+ * as they are and has the applies of that handle run one lane per row, a product and an addition per entry: the
+ * second implementation the tests compare with, and the baseline of profiles/fr_matrix.txt.
+ * amdmsm_fr_matrix_apply_device: d_x (n_x >= n_cols records) and d_out (n_out >= n_rows records) in HBM, both in the
+ * form opts->scalars_plain says, aligned as the vectors of amdmsm_fr_fft_device and not overlapping.  Records n_rows ..
+ * n_out - 1 are written as zero -- the output is the input of a transform of size n_out as it stands -- and nothing at
+ * or beyond n_out is touched.  Enqueued on opts->stream (or the context's), not synchronised; one handle may be applied
+ * on several streams.  AMDMSM_ERR_BAD_ARG, with a message, before anything is launched or written: a handle of another
+ * context or a freed one, n_x < n_cols, n_out < n_rows, a null vector with work to do, a misaligned or overlapping
+ * vector, a wrong opts->struct_size; AMDMSM_ERR_TOO_LARGE for n_x or n_out above 2^28.  A record of x that is not below
+ * r gives an unspecified value in the rows that read it and nothing else: every address comes from the validated
+ * handle, none from the vector.
+ * amdmsm_fr_matrix_apply: the same with x and out in host memory (no alignment rule); uploads, applies, downloads and
+ * synchronises.
+ * amdmsm_fr_matrix_free waits for the applies that still use the handle and releases it; handles still alive are
+ * released with the context.
+ * With timing enabled (amdmsm_get_timings): [0] the upload (host entry), [1] the kernels, [2] the download (host
+ * entry), [AMDMSM_PH_TOTAL] the call. */
+int amdmsm_fr_matrix_load(amdmsm_ctx *ctx, int curve, size_t n_rows, size_t n_cols, const uint64_t *offsets,
+                          const uint32_t *cols, const void *coeffs, int coeffs_plain, uint64_t *mat);
+int amdmsm_fr_matrix_apply_device(amdmsm_ctx *ctx, uint64_t mat, const void *d_x, size_t n_x, void *d_out, size_t n_out,
+                                  const amdmsm_opts *opts);
+int amdmsm_fr_matrix_apply(amdmsm_ctx *ctx, uint64_t mat, const void *x, size_t n_x, void *out, size_t n_out,
+                           const amdmsm_opts *opts);
+int amdmsm_fr_matrix_free(amdmsm_ctx *ctx, uint64_t mat);
+/* What amdmsm_fr_matrix_load would build, read-only and without a context; it validates exactly what the load does,
+ * with the same codes (the message is not kept).  Rows are classed by the number of their non-zero entries:
+ *   out[0]  nnz as given            out[1 .. 4]  entries with a general coefficient / 1 / r - 1 / 0 (dropped)
+ *   out[5 .. 7]  rows served one to a lane (shorter than out[8]) / by one wave / by several waves (longer than out[9])
+ *   out[8]  the shortest row that takes a wave    out[9]  the longest row one wave takes
+ *   out[10] the longest row         out[11] device bytes of the resident form
+ *   out[12] launches of one apply   out[13] general products per Montgomery reduction, the field's chain length
+ *   out[14] wave jobs of one apply  out[15] partial sums an apply keeps in its workspace
+ * AMDMSM_FR_MATRIX_WAVE_ROW / AMDMSM_FR_MATRIX_SPLIT_ROW in the environment replace out[8] / out[9] (experiments). */
+#define AMDMSM_FR_MATRIX_PLAN_WORDS 16
+int amdmsm_plan_fr_matrix(int curve, size_t n_rows, size_t n_cols, const uint64_t *offsets, const uint32_t *cols,
+                          const void *coeffs, int coeffs_plain, size_t out[AMDMSM_FR_MATRIX_PLAN_WORDS]);
+
 /* Segmented MSM: m sums in one call, out[j] = sum of scalars[i] * base(i) over offsets[j] <= i < offsets[j + 1] -- the
  * shape of k proofs verified as a batch (sum of input_i * IC_i per proof), of row or column commitments, of the cross
  * terms of an inner-product argument.  A single MSM per segment would pay the fixed cost of its launch chain m times;

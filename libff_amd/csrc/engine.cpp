@@ -14,6 +14,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -22,6 +23,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 using namespace amdmsm;
@@ -102,6 +104,20 @@ struct fr_tw_entry {
     uint64_t last_use = 0;
 };
 
+// A sparse matrix over Fr kept in HBM (amdmsm_fr_matrix_load): the resident form of fr_matrix_layout.h, or with
+// AMDMSM_FR_MATRIX_NAIVE=1 the caller's CSR arrays.  Owned by the context; known to callers by its id.
+struct fr_matrix {
+    uint64_t id = 0;
+    int curve = 0;
+    size_t n_rows = 0, n_cols = 0, kept = 0;     // kept: entries an apply reads
+    bool naive = false;
+    void *words = nullptr, *coef = nullptr, *desc = nullptr, *lane_rows = nullptr, *comb = nullptr;   // resident form
+    void *offsets = nullptr, *cols = nullptr;                                                         // naive: with coef
+    uint32_t n_desc = 0, n_comb = 0, n_partials = 0;
+    // behind the last apply on every stream that has used the handle: what amdmsm_fr_matrix_free waits for
+    std::vector<std::pair<hipStream_t, hipEvent_t>> users;
+};
+
 struct amdmsm_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -148,6 +164,7 @@ struct amdmsm_ctx {
     float aux_ms[4] = {};
     fr_tw_entry fr_tw[2];                         // a prover alternates omega and omega^-1 over one domain
     uint64_t fr_clock = 0;
+    std::vector<fr_matrix *> fr_mats;
     std::string err;
     std::recursive_mutex mu;                      // one call at a time per context (entries nest)
 };
@@ -1178,6 +1195,12 @@ void amdmsm_ctx_destroy(amdmsm_ctx *ctx) {
         for (auto &t : ctx->fr_tw) {
             if (t.buf.p) (void)hipFree(t.buf.p);
             if (t.ev) (void)hipEventDestroy(t.ev);
+        }
+        for (fr_matrix *m : ctx->fr_mats) {
+            for (void *p : {m->words, m->coef, m->desc, m->lane_rows, m->comb, m->offsets, m->cols})
+                if (p) (void)hipFree(p);
+            for (auto &u : m->users) (void)hipEventDestroy(u.second);
+            delete m;
         }
         for (int b = 0; b < stream_state::NB; ++b) {
             if (ctx->ss.h_stage[b]) (void)hipHostFree(ctx->ss.h_stage[b]);
@@ -4107,6 +4130,298 @@ int amdmsm_fr_muladd_device(amdmsm_ctx *ctx, int curve, size_t n, const void *d_
               plain ? 1 : 0, (uint32_t *)d_out);
     HIP_TRY(ctx, hipGetLastError());
     return AMDMSM_OK;
+}
+
+}  // extern "C"
+
+// ---- sparse matrix times Fr vector: out[i] = sum_k coeffs[k] x[cols[k]] over the row's entries --------------------------
+namespace {
+
+uint32_t frm_env(const char *name) {
+    const char *e = getenv(name);
+    return e ? (uint32_t)strtoul(e, nullptr, 10) : 0u;
+}
+bool frm_naive_env() {
+    const char *e = getenv("AMDMSM_FR_MATRIX_NAIVE");
+    return e && *e && strcmp(e, "0") != 0;
+}
+
+bool fr_below_modulus(const fr_vtable *f, const uint32_t *w) {
+    for (int j = f->words - 1; j >= 0; --j)
+        if (w[j] != f->modulus[j]) return w[j] < f->modulus[j];
+    return false;
+}
+
+// What plan and load share: the argument rules and the layout.  Nothing is allocated on the device before it returns 0.
+int frm_prepare(amdmsm_ctx *ctx, const fr_vtable *f, size_t n_rows, size_t n_cols, const uint64_t *offsets, const uint32_t *cols,
+                const void *coeffs, int coeffs_plain, frm_layout &L) {
+    std::string err;
+    const int bad = frm_validate(n_rows, n_cols, offsets, cols, coeffs != nullptr, err);
+    if (bad) return fail(ctx, bad == 2 ? AMDMSM_ERR_TOO_LARGE : AMDMSM_ERR_BAD_ARG, err);
+    // 1 and r - 1 in the form the coefficients come in
+    const int N = f->words;
+    fr_rec one, minus_one;
+    if (coeffs_plain) one.v[0] = 1;
+    else one = fr_from_words(f, f->one);
+    uint64_t borrow = 0;
+    for (int j = 0; j < N; ++j) {
+        const uint64_t d = (uint64_t)f->modulus[j] - one.v[j] - borrow;
+        minus_one.v[j] = (uint32_t)d;
+        borrow = (d >> 63) & 1u;
+    }
+    const fr_rec zero;
+    const size_t rec = (size_t)N * 4;
+    uint64_t bad_entry = 0;
+    const auto cls_of = [&](uint64_t k) -> uint32_t {
+        uint32_t w[FR_MAX_WORDS];
+        memcpy(w, (const char *)coeffs + k * rec, rec);   // the caller's array needs no alignment
+        if (!fr_below_modulus(f, w)) return FRM_BAD;
+        if (!memcmp(w, one.v, rec)) return FRM_PLUS;
+        if (!memcmp(w, minus_one.v, rec)) return FRM_MINUS;
+        if (!memcmp(w, zero.v, rec)) return FRM_ZERO;
+        return FRM_GEN;
+    };
+    if (!frm_build(n_rows, offsets, cols, cls_of, frm_env("AMDMSM_FR_MATRIX_WAVE_ROW"), frm_env("AMDMSM_FR_MATRIX_SPLIT_ROW"), L,
+                   bad_entry))
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "entry " + std::to_string(bad_entry) + ": coefficient >= r");
+    return AMDMSM_OK;
+}
+
+size_t frm_device_bytes(const fr_vtable *f, const frm_layout &L, size_t n_rows, bool naive) {
+    const size_t rec = (size_t)f->words * 4;
+    if (naive) return (n_rows + 1) * 8 + L.nnz * 4 + L.nnz * rec;
+    return L.words.size() * 4 + L.gen_src.size() * rec + L.desc.size() * sizeof(frm_desc) + L.lane_rows.size() * 4 +
+           L.comb.size() * sizeof(frm_comb);
+}
+
+std::atomic<uint64_t> g_fr_matrix_id{1};   // ids are never reused, in any context: a stale or foreign handle finds nothing
+
+fr_matrix *frm_find(amdmsm_ctx *ctx, uint64_t id) {
+    for (fr_matrix *m : ctx->fr_mats)
+        if (m->id == id) return m;
+    return nullptr;
+}
+
+int frm_upload(amdmsm_ctx *ctx, void *&d, const void *h, size_t bytes) {
+    if (!bytes) return AMDMSM_OK;
+    HIP_TRY(ctx, hipMalloc(&d, bytes));
+    HIP_TRY(ctx, hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));
+    return AMDMSM_OK;
+}
+
+void frm_release(fr_matrix *m) {
+    for (void *p : {m->words, m->coef, m->desc, m->lane_rows, m->comb, m->offsets, m->cols})
+        if (p) (void)hipFree(p);
+    for (auto &u : m->users) (void)hipEventDestroy(u.second);
+    delete m;
+}
+
+// The argument rules of both apply entries, the handle found; device: the vectors are HBM addresses
+int frm_check_apply(amdmsm_ctx *ctx, uint64_t mat, const void *x, size_t n_x, const void *out, size_t n_out, bool device,
+                    fr_matrix *&m, const fr_vtable *&f) {
+    m = frm_find(ctx, mat);
+    if (!m) return fail(ctx, AMDMSM_ERR_BAD_ARG, "matrix handle " + std::to_string(mat) + ": not a live handle of this context");
+    f = find_frvt(m->curve);
+    if (n_x < m->n_cols)
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "n_x = " + std::to_string(n_x) + " < n_cols = " + std::to_string(m->n_cols));
+    if (n_out < m->n_rows)
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "n_out = " + std::to_string(n_out) + " < n_rows = " + std::to_string(m->n_rows));
+    if (n_x > FRM_MAX_DIM || n_out > FRM_MAX_DIM)
+        return fail(ctx, AMDMSM_ERR_TOO_LARGE, "n_x / n_out: at most 2^28 records");
+    if (n_out && !out) return fail(ctx, AMDMSM_ERR_BAD_ARG, "output: null pointer");
+    if (m->kept && !x) return fail(ctx, AMDMSM_ERR_BAD_ARG, "x: null pointer");
+    if (device) {
+        if (fr_misaligned(f, {x, out}))
+            return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_x / d_out: not aligned to " + std::to_string(f->words % 4 ? 8 : 16) + " bytes");
+        const size_t rec = (size_t)f->words * 4;
+        const uintptr_t a = (uintptr_t)x, b = (uintptr_t)out;
+        if (x && out && n_x && n_out && a < b + n_out * rec && b < a + n_x * rec)
+            return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_x and d_out overlap");
+    }
+    return AMDMSM_OK;
+}
+
+// the kernels of one apply on device vectors; partial: room for n_partials records
+int frm_run(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, fr_matrix *m, const uint32_t *d_x, uint32_t *d_out, size_t n_out,
+            uint32_t *partial) {
+    if (m->naive) {
+        f->matrix_naive(st, m->n_rows, n_out, (const uint64_t *)m->offsets, (const uint32_t *)m->cols, (const uint32_t *)m->coef, d_x,
+                        d_out);
+    } else {
+        frm_args a = {};
+        a.words = (const uint32_t *)m->words;
+        a.coef = (const uint32_t *)m->coef;
+        a.desc = (const frm_desc *)m->desc;
+        a.lane_rows = (const uint32_t *)m->lane_rows;
+        a.comb = (const frm_comb *)m->comb;
+        a.x = d_x;
+        a.out = d_out;
+        a.partial = partial;
+        a.n_desc = m->n_desc;
+        a.n_comb = m->n_comb;
+        a.n_rows = m->n_rows;
+        a.n_out = n_out;
+        f->matrix_apply(st, a);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    // behind this user of the handle
+    hipEvent_t *ev = nullptr;
+    for (auto &u : m->users)
+        if (u.first == st) ev = &u.second;
+    if (!ev) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        m->users.emplace_back(st, e);
+        ev = &m->users.back().second;
+    }
+    HIP_TRY(ctx, hipEventRecord(*ev, st));
+    return AMDMSM_OK;
+}
+
+}   // namespace
+
+extern "C" {
+
+int amdmsm_plan_fr_matrix(int curve, size_t n_rows, size_t n_cols, const uint64_t *offsets, const uint32_t *cols, const void *coeffs,
+                          int coeffs_plain, size_t out[AMDMSM_FR_MATRIX_PLAN_WORDS]) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return AMDMSM_ERR_UNSUPPORTED;
+    if (!out) return AMDMSM_ERR_BAD_ARG;
+    frm_layout L;
+    const int rc = frm_prepare(nullptr, f, n_rows, n_cols, offsets, cols, coeffs, coeffs_plain, L);
+    if (rc) return rc;
+    const bool naive = frm_naive_env();
+    out[0] = L.nnz;
+    out[1] = L.cnt[FRM_GEN];
+    out[2] = L.cnt[FRM_PLUS];
+    out[3] = L.cnt[FRM_MINUS];
+    out[4] = L.cnt[FRM_ZERO];
+    out[5] = L.rows_lane;
+    out[6] = L.rows_wave;
+    out[7] = L.rows_split;
+    out[8] = L.t_wave;
+    out[9] = L.t_split;
+    out[10] = L.longest;
+    out[11] = frm_device_bytes(f, L, n_rows, naive);
+    out[12] = naive ? 1 : 1 + (L.comb.empty() ? 0 : 1);
+    out[13] = f->matrix_chunk;
+    out[14] = L.desc.size();
+    out[15] = L.n_partials;
+    return AMDMSM_OK;
+}
+
+int amdmsm_fr_matrix_load(amdmsm_ctx *ctx, int curve, size_t n_rows, size_t n_cols, const uint64_t *offsets, const uint32_t *cols,
+                          const void *coeffs, int coeffs_plain, uint64_t *mat) {
+    if (mat) *mat = 0;   // no handle is ever 0
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
+    if (!mat) return fail(ctx, AMDMSM_ERR_BAD_ARG, "mat: null pointer");
+    frm_layout L;
+    int rc = frm_prepare(ctx, f, n_rows, n_cols, offsets, cols, coeffs, coeffs_plain, L);
+    if (rc) return rc;
+    FR_ENTER(ctx);
+    const size_t rec = (size_t)f->words * 4, N = (size_t)f->words;
+    const fr_rec r2 = fr_from_words(f, f->r2);
+    const auto mont = [&](uint64_t k, uint32_t *dst) {   // the caller's coefficient k as a Montgomery residue
+        fr_rec c;
+        memcpy(c.v, (const char *)coeffs + k * rec, rec);
+        if (coeffs_plain) c = fr_mul(f, c, r2);
+        memcpy(dst, c.v, rec);
+    };
+    fr_matrix *m = new fr_matrix();
+    m->curve = curve;
+    m->n_rows = n_rows;
+    m->n_cols = n_cols;
+    m->naive = frm_naive_env();
+    std::vector<uint32_t> coef;
+    if (m->naive) {
+        m->kept = L.nnz;
+        coef.resize(L.nnz * N);
+        for (uint64_t k = 0; k < L.nnz; ++k) mont(k, &coef[k * N]);
+        const uint64_t none[1] = {0};
+        rc = frm_upload(ctx, m->offsets, n_rows ? offsets : none, (n_rows + 1) * 8);
+        if (!rc) rc = frm_upload(ctx, m->cols, cols, L.nnz * 4);
+    } else {
+        m->kept = L.nnz - L.cnt[FRM_ZERO];
+        coef.resize(L.gen_src.size() * N);
+        for (size_t g = 0; g < L.gen_src.size(); ++g) mont(L.gen_src[g], &coef[g * N]);
+        m->n_desc = (uint32_t)L.desc.size();
+        m->n_comb = (uint32_t)L.comb.size();
+        m->n_partials = L.n_partials;
+        rc = frm_upload(ctx, m->words, L.words.data(), L.words.size() * 4);
+        if (!rc) rc = frm_upload(ctx, m->desc, L.desc.data(), L.desc.size() * sizeof(frm_desc));
+        if (!rc) rc = frm_upload(ctx, m->lane_rows, L.lane_rows.data(), L.lane_rows.size() * 4);
+        if (!rc) rc = frm_upload(ctx, m->comb, L.comb.data(), L.comb.size() * sizeof(frm_comb));
+    }
+    if (!rc) rc = frm_upload(ctx, m->coef, coef.data(), coef.size() * 4);
+    if (rc) {
+        frm_release(m);
+        return rc;
+    }
+    m->id = g_fr_matrix_id.fetch_add(1);
+    ctx->fr_mats.push_back(m);
+    *mat = m->id;
+    return AMDMSM_OK;
+}
+
+int amdmsm_fr_matrix_free(amdmsm_ctx *ctx, uint64_t mat) {
+    FR_ENTER(ctx);
+    fr_matrix *m = frm_find(ctx, mat);
+    if (!m) return fail(ctx, AMDMSM_ERR_BAD_ARG, "matrix handle " + std::to_string(mat) + ": not a live handle of this context");
+    for (auto &u : m->users) (void)hipEventSynchronize(u.second);   // the applies that still read the arrays
+    ctx->fr_mats.erase(std::find(ctx->fr_mats.begin(), ctx->fr_mats.end(), m));
+    frm_release(m);
+    return AMDMSM_OK;
+}
+
+int amdmsm_fr_matrix_apply_device(amdmsm_ctx *ctx, uint64_t mat, const void *d_x, size_t n_x, void *d_out, size_t n_out,
+                                  const amdmsm_opts *opts) {
+    CHECK_OPTS(ctx, opts);
+    FR_ENTER(ctx);
+    fr_matrix *m = nullptr;
+    const fr_vtable *f = nullptr;
+    int rc = frm_check_apply(ctx, mat, d_x, n_x, d_out, n_out, true, m, f);
+    if (rc) return rc;
+    if (!n_out) return AMDMSM_OK;
+    hipStream_t st = stream_of(ctx, opts);
+    ws_slot *sl = nullptr;
+    rc = fft_begin(ctx, st, align_up(((size_t)m->n_partials + 1) * f->words * 4, 256), sl);
+    if (rc) return rc;
+    fft_mark(ctx, st, 1);
+    rc = frm_run(ctx, f, st, m, (const uint32_t *)d_x, (uint32_t *)d_out, n_out, (uint32_t *)sl->ws);
+    if (rc) return rc;
+    return fft_end(ctx, st, *sl, 1);
+}
+
+int amdmsm_fr_matrix_apply(amdmsm_ctx *ctx, uint64_t mat, const void *x, size_t n_x, void *out, size_t n_out,
+                           const amdmsm_opts *opts) {
+    CHECK_OPTS(ctx, opts);
+    FR_ENTER(ctx);
+    fr_matrix *m = nullptr;
+    const fr_vtable *f = nullptr;
+    int rc = frm_check_apply(ctx, mat, x, n_x, out, n_out, false, m, f);
+    if (rc) return rc;
+    if (!n_out) return AMDMSM_OK;
+    hipStream_t st = ctx->stream;
+    const size_t rec = (size_t)f->words * 4;
+    // the uploaded vector, the result and the partial sums, in that order
+    const size_t x_bytes = align_up((n_x ? n_x : 1) * rec, 256), out_bytes = align_up(n_out * rec, 256);
+    ws_slot *sl = nullptr;
+    rc = fft_begin(ctx, st, x_bytes + out_bytes + align_up(((size_t)m->n_partials + 1) * rec, 256), sl);
+    if (rc) return rc;
+    uint32_t *d_x = (uint32_t *)sl->ws, *d_out = (uint32_t *)((char *)sl->ws + x_bytes);
+    if (n_x && x) HIP_TRY(ctx, hipMemcpyAsync(d_x, x, n_x * rec, hipMemcpyHostToDevice, st));
+    fft_mark(ctx, st, 1);
+    rc = frm_run(ctx, f, st, m, d_x, d_out, n_out, (uint32_t *)((char *)sl->ws + x_bytes + out_bytes));
+    if (rc) {
+        (void)hipDeviceSynchronize();   // nothing of this call may still read the caller's vector
+        return rc;
+    }
+    fft_mark(ctx, st, 2);
+    HIP_TRY(ctx, hipMemcpyAsync(out, d_out, n_out * rec, hipMemcpyDeviceToHost, st));
+    rc = fft_end(ctx, st, *sl, 2);
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return rc;
 }
 
 }  // extern "C"

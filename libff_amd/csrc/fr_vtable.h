@@ -1,10 +1,12 @@
 // Host-visible interface of one scalar-field translation unit (fr_ntt.hip, compiled once per curve with
 // -DAMDMSM_FR=<curve>_fr): the field's constants for the host-side parameter arithmetic of engine.cpp and launchers of
-// the three kernels.  Every record that crosses this interface on the host side is a Montgomery residue below r.
+// the kernels.  Every record that crosses this interface on the host side is a Montgomery residue below r.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include "fr_matrix_layout.h"
 
 namespace amdmsm {
 
@@ -28,6 +30,20 @@ struct fr_pass {
     uint32_t scale[FR_MAX_WORDS];
 };
 
+// one apply of a resident sparse matrix (k_frm_apply, k_frm_combine; fr_matrix_layout.h has the arrays' meaning)
+struct frm_args {
+    const uint32_t* words;
+    const uint32_t* coef;        // the general coefficients in word order, Montgomery
+    const frm_desc* desc;
+    const uint32_t* lane_rows;
+    const frm_comb* comb;
+    const uint32_t* x;
+    uint32_t* out;
+    uint32_t* partial;           // n_partials records of workspace
+    uint32_t n_desc, n_comb;
+    size_t n_rows, n_out;        // out[n_rows .. n_out - 1] = 0
+};
+
 struct fr_vtable {
     int curve, words, two_adicity;
     uint32_t inv;                                  // -r^-1 mod 2^32
@@ -38,6 +54,12 @@ struct fr_vtable {
     // d_out[i] = (a_i * b_i - c_i) * k; d_c, k: null for 0 and 1.  k: a host record
     void (*muladd)(hipStream_t, size_t n, const uint32_t* d_a, const uint32_t* d_b, const uint32_t* d_c, const uint32_t* k,
                    int plain, uint32_t* d_out);
+    // sparse matrix times vector: general products summed unreduced, matrix_chunk of them to one Montgomery reduction
+    uint32_t matrix_chunk;
+    void (*matrix_apply)(hipStream_t, const frm_args&);
+    // the same from the caller's CSR (coefficients Montgomery), one lane per row: AMDMSM_FR_MATRIX_NAIVE=1
+    void (*matrix_naive)(hipStream_t, size_t n_rows, size_t n_out, const uint64_t* d_offsets, const uint32_t* d_cols,
+                         const uint32_t* d_coef, const uint32_t* d_x, uint32_t* d_out);
 };
 
 const fr_vtable* frvt_alt_bn128() __attribute__((weak));

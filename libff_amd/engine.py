@@ -68,6 +68,8 @@ EXPORTED_SYMBOLS = [
     "amdmsm_group_fft", "amdmsm_group_fft_device", "amdmsm_plan_group_fft", "amdmsm_fr_modulus",
     "amdmsm_fr_fft", "amdmsm_fr_fft_device", "amdmsm_plan_fr_fft", "amdmsm_fr_root_of_unity", "amdmsm_fr_powers_device",
     "amdmsm_fr_muladd_device",
+    "amdmsm_plan_fr_matrix", "amdmsm_fr_matrix_load", "amdmsm_fr_matrix_apply", "amdmsm_fr_matrix_apply_device",
+    "amdmsm_fr_matrix_free",
 ]
 SEG_SHARED_BASES = 1            # include/amdmsm.h AMDMSM_SEG_SHARED_BASES
 SEG_LONG_NEVER = 2 ** 64 - 1    # long_from = SIZE_MAX: no segment takes the single-MSM route
@@ -292,6 +294,57 @@ def fr_root_of_unity(curve, n):
     if rc:
         raise ValueError(f"n = {n}: no n-th root of unity in Fr of {CURVE_NAMES.get(curve, curve)} ({rc})")
     return int.from_bytes(bytes(w), "little")
+
+
+FR_MATRIX_PLAN_WORDS = 16   # include/amdmsm.h AMDMSM_FR_MATRIX_PLAN_WORDS
+
+
+def _csr_arrays(curve, offsets, cols, coeffs):
+    """the CSR arrays as the C entries take them: uint64 offsets, uint32 columns, (nnz, fr_limbs) uint64 records"""
+    limbs = sizes(curve, G1)["fr_bytes"] // 8
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    cols = np.ascontiguousarray(cols, dtype=np.uint32)
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64).reshape(-1, limbs)
+    assert offsets.ndim == 1 and cols.ndim == 1 and cols.shape[0] == coeffs.shape[0], "cols and coeffs: one per entry"
+    assert offsets.shape[0] == 0 or int(offsets[-1]) <= cols.shape[0], "offsets reach beyond the entries given"
+    ptr = lambda a: _np_ptr(a) if a.size else None
+    return offsets, cols, coeffs, max(0, offsets.shape[0] - 1), ptr
+
+
+def plan_fr_matrix(curve, offsets, cols, coeffs, n_cols, plain=False):
+    """What ``Engine.fr_matrix_load`` would build from a CSR matrix (``amdmsm_plan_fr_matrix``, read-only, no device):
+    entries per coefficient class, rows per length class with the thresholds between them, the longest row, device
+    bytes, launches of one apply and the field's chain length.  Validates exactly what the load validates and raises
+    ``AmdMsmError`` with the code."""
+    offsets, cols, coeffs, n_rows, ptr = _csr_arrays(curve, offsets, cols, coeffs)
+    out = (ctypes.c_size_t * FR_MATRIX_PLAN_WORDS)()
+    rc = load_library().amdmsm_plan_fr_matrix(curve, ctypes.c_size_t(n_rows), ctypes.c_size_t(n_cols), ptr(offsets), ptr(cols),
+                                              ptr(coeffs), int(plain), out)
+    if rc:
+        raise AmdMsmError(f"amdmsm_plan_fr_matrix: {rc}")
+    return {"nnz": out[0], "general": out[1], "plus_one": out[2], "minus_one": out[3], "zero": out[4],
+            "rows_lane": out[5], "rows_wave": out[6], "rows_split": out[7], "wave_row": out[8], "split_row": out[9],
+            "longest_row": out[10], "device_bytes": out[11], "launches": out[12], "chunk": out[13], "wave_jobs": out[14],
+            "partials": out[15]}
+
+
+class FrMatrix:
+    """A sparse matrix over Fr resident on the device (``Engine.fr_matrix_load``); ``free()`` or a ``with`` block
+    releases it, the engine's ``close()`` whatever is left."""
+
+    def __init__(self, engine, handle, curve, n_rows, n_cols):
+        self.engine, self.handle, self.curve, self.n_rows, self.n_cols = engine, handle, curve, n_rows, n_cols
+
+    def free(self):
+        if self.handle:
+            h, self.handle = self.handle, 0
+            self.engine._check(self.engine.lib.amdmsm_fr_matrix_free(self.engine.h, ctypes.c_uint64(h)), "amdmsm_fr_matrix_free")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
 
 
 def _fr_record(x, limbs, r, plain):
@@ -886,6 +939,41 @@ class Engine:
                                     ptr(post), ptr(scale), int(tile_log2), ctypes.byref(o), _np_ptr(out) if n else None)
         self._check(rc, "amdmsm_fr_fft")
         return out
+
+    def fr_matrix_load(self, curve, offsets, cols, coeffs, n_cols, plain=False):
+        """Keep a CSR matrix over Fr on the device (``amdmsm_fr_matrix_load``): ``offsets`` (n_rows + 1), ``cols`` (nnz),
+        ``coeffs`` (nnz, fr_limbs) uint64 records -- Montgomery residues, with ``plain`` plain integers.  Returns an
+        ``FrMatrix``."""
+        offsets, cols, coeffs, n_rows, ptr = _csr_arrays(curve, offsets, cols, coeffs)
+        h = ctypes.c_uint64(0)
+        rc = self.lib.amdmsm_fr_matrix_load(self.h, curve, ctypes.c_size_t(n_rows), ctypes.c_size_t(n_cols), ptr(offsets),
+                                            ptr(cols), ptr(coeffs), int(plain), ctypes.byref(h))
+        self._check(rc, "amdmsm_fr_matrix_load")
+        return FrMatrix(self, h.value, curve, n_rows, int(n_cols))
+
+    def fr_matrix_apply(self, mat, x, n_out=None, plain=False):
+        """``out[i] = sum_k coeffs[k] x[cols[k]]`` over row i (``amdmsm_fr_matrix_apply``): ``x`` (n_x >= n_cols, fr_limbs)
+        uint64 records in the form ``plain`` says, the result -- ``n_out`` records, the rows and zeros behind them --
+        in the same form."""
+        limbs = sizes(mat.curve, G1)["fr_bytes"] // 8
+        x = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, limbs)
+        n_out = mat.n_rows if n_out is None else int(n_out)
+        out = np.zeros((n_out, limbs), dtype=np.uint64)
+        o = self._opts(scalars_plain=plain)
+        rc = self.lib.amdmsm_fr_matrix_apply(self.h, ctypes.c_uint64(mat.handle), _np_ptr(x) if x.size else None,
+                                             ctypes.c_size_t(x.shape[0]), _np_ptr(out) if n_out else None,
+                                             ctypes.c_size_t(n_out), ctypes.byref(o))
+        self._check(rc, "amdmsm_fr_matrix_apply")
+        return out
+
+    def fr_matrix_apply_device(self, mat, d_x, n_x, d_out, n_out, plain=False, stream=None):
+        """``fr_matrix_apply`` on device-resident vectors (``amdmsm_fr_matrix_apply_device``): enqueued on ``stream``, not
+        synchronised; records n_rows .. n_out - 1 of ``d_out`` are written as zero."""
+        o = self._opts(scalars_plain=plain, stream=stream)
+        self._check(self.lib.amdmsm_fr_matrix_apply_device(self.h, ctypes.c_uint64(mat.handle),
+                                                           None if d_x is None else _vp(d_x), ctypes.c_size_t(n_x),
+                                                           None if d_out is None else _vp(d_out), ctypes.c_size_t(n_out),
+                                                           ctypes.byref(o)), "amdmsm_fr_matrix_apply_device")
 
     def batch_exp_timings(self):
         """device times (ms) of the last batch_exp: inputs H2D, window table (0 = reused), exponentiations, results D2H"""

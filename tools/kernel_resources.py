@@ -36,9 +36,8 @@ def main():
         if m:
             name = m.group(1)
             d = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
-            cur = re.sub(r"\(.*", "", d.split("::")[-1]) + ("" if "<" not in d else "")
-            if "<" in d.split("(")[0]:
-                cur = d.split("(")[0].split("::")[-1]
+            # the name in front of the parameter list: a parameter may be of a namespaced type itself
+            cur = d.replace("(anonymous namespace)::", "").split("(")[0].split("::")[-1]
             rows[cur] = {}
             continue
         m = re.search(r"remark: .*?\s{2,}(\S[^:]*): (\S+)", line)
