@@ -288,8 +288,8 @@ int amdmsm_fr_modulus(int curve, int group, void *r_plain);
  *   omega        a primitive n-th root of unity, one record in host memory (amdmsm_fr_root_of_unity gives libff's); may
  *                be NULL when n <= 1.  Checked on the host: omega^(n/2) must be r - 1
  *   pre, post, scale   one record each in host memory, NULL = 1.  All NULL: libfqfft's FFT.  pre = g: the coset FFT by
- *                g.  omega^-1 and scale = n^-1: the inverse FFT; with post = g^-1 as well: the inverse coset FFT.  The
- *                library has no Fr inversion: the caller supplies the inverses
+ *                g.  omega^-1 and scale = n^-1: the inverse FFT; with post = g^-1 as well: the inverse coset FFT.
+ *                amdmsm_fr_inverse gives the inverses
  *   tile_log2    butterfly stages of one global pass, 0 = the default; amdmsm_plan_fr_fft reports the range
  * A transform is ceil(log2 n / tile) passes; a pass reads every record once and writes it once, pre^i is applied as the
  * first pass loads and post^j * scale as the last pass stores.  Workspace, from the context's slots: one vector of n
@@ -326,6 +326,67 @@ int amdmsm_fr_powers_device(amdmsm_ctx *ctx, int curve, const void *base, size_t
    (one record in host memory) may be NULL: 0 and 1.  d_out may be any of the inputs.  Enqueued, not synchronised */
 int amdmsm_fr_muladd_device(amdmsm_ctx *ctx, int curve, size_t n, const void *d_a, const void *d_b, const void *d_c,
                             const void *k, const amdmsm_opts *opts, void *d_out);
+
+/* Scans and batch inversion over a vector of Fr records -- the operations that carry a value from one record to the
+ * next: prefix products (the z vector of a grand product), prefix sums, Horner evaluation and synthetic division by
+ * X - z in front of an opening, Lagrange coefficients.  Records as for amdmsm_fr_fft: Montgomery residues below r, or
+ * with opts->scalars_plain plain integers below r, the vectors, a_const, init and the total alike; a record >= r gives
+ * unspecified values in the outputs that depend on it and never an access outside the outputs.
+ * Scan: the first-order recurrence over n <= 2^28 records
+ *     y_(-1) = init,  y_i = a_i * y_(i-1) + b_i,  i = 0 .. n - 1;        total = y_(n-1)
+ *     out[i] = y_i, or with AMDMSM_SCAN_EXCLUSIVE y_(i-1) (out[0] = init)
+ * and with AMDMSM_SCAN_REVERSE from the other end: y_n = init, y_i = a_i * y_(i+1) + b_i, i = n - 1 .. 0, total = y_0,
+ * out[i] = y_i or, exclusive, y_(i+1).
+ *   a        a vector (d_a / a), or one record in host memory for every i (a_const), or neither: every a_i is 1
+ *   b        a vector (d_b / b) or NULL: every b_i is 0
+ *   init     one record in host memory; NULL means 1 without b and 0 with it
+ *   total    one record (d_total in HBM / total in host memory), may be NULL.  n = 0 writes nothing but total = init
+ * d_a alone: prefix products.  d_b alone: prefix sums.  a_const = z, d_b = p, reverse, exclusive, init = 0: out[i] is
+ * coefficient i of (p(X) - p(z)) / (X - z), out[n - 1] = 0 and total = p(z).
+ * Batch inversion: out[i] = 1 / values[i], and 0 where values[i] is 0; the number of zero records goes to
+ * d_zero_count (a uint64 in HBM, aligned to 8 bytes) / zero_count (host memory), which may be NULL and need not be
+ * cleared.  One field inversion per call, whatever n.
+ *   tile_log2   records of one workgroup's tile (log2), 0 = the default; amdmsm_plan_fr_scan reports the range
+ * Device entries: enqueued on opts->stream (or the context's), not synchronised.  d_out may be exactly d_a, d_b or
+ * d_values (a tile loads all it needs before it stores); any other overlap is refused, as is a d_total or d_zero_count
+ * inside a vector.  Vectors and d_total aligned as the vectors of amdmsm_fr_fft_device.  The host entries (no alignment
+ * rule) upload, run, download and synchronise.
+ * Three launches in stream order and no kernel that waits for another workgroup: every tile's aggregate, one workgroup
+ * over the aggregates, every tile again.  AMDMSM_FR_SCAN_NAIVE=1 in the environment of a call has
+ * one lane walk the vector instead: the second implementation the tests compare with and the baseline of
+ * profiles/fr_scan.txt.
+ * Refused before anything is launched or written and before the context is looked at, amdmsm_last_error naming the
+ * argument: AMDMSM_ERR_UNSUPPORTED for an unknown curve; AMDMSM_ERR_TOO_LARGE for n > 2^28; AMDMSM_ERR_BAD_ARG for a
+ * wrong opts->struct_size, unknown flag bits, d_a and a_const both given, a and b both absent, a null or misaligned
+ * vector with n > 0, a partial overlap, a nonzero tile_log2 outside the plan's range, a_const or init not below r.
+ * With timing enabled (amdmsm_get_timings): [0] the upload (host entries), [1] the kernels, [2] the download (host
+ * entries), [AMDMSM_PH_TOTAL] the call. */
+#define AMDMSM_SCAN_REVERSE 1
+#define AMDMSM_SCAN_EXCLUSIVE 2
+int amdmsm_fr_scan_device(amdmsm_ctx *ctx, int curve, size_t n, const void *d_a, const void *a_const, const void *d_b,
+                          const void *init, int flags, int tile_log2, const amdmsm_opts *opts, void *d_out, void *d_total);
+int amdmsm_fr_scan(amdmsm_ctx *ctx, int curve, size_t n, const void *a, const void *a_const, const void *b, const void *init,
+                   int flags, int tile_log2, const amdmsm_opts *opts, void *out, void *total);
+int amdmsm_fr_batch_invert_device(amdmsm_ctx *ctx, int curve, size_t n, const void *d_values, int tile_log2,
+                                  const amdmsm_opts *opts, void *d_out, uint64_t *d_zero_count);
+int amdmsm_fr_batch_invert(amdmsm_ctx *ctx, int curve, size_t n, const void *values, const amdmsm_opts *opts, void *out,
+                           uint64_t *zero_count);
+/* What a scan or an inversion of n records runs, read-only and without a context.  kind_and_flags: what is given --
+ * AMDMSM_SCAN_KIND_A (a vector or a_const) and / or AMDMSM_SCAN_KIND_B, with the scan's flags, or AMDMSM_SCAN_KIND_INVERT
+ * alone.
+ *   out[0]  records of a tile      out[1]  records of a lane      out[2]  tiles the spine takes per step
+ *   out[3] / out[4]  smallest / largest tile_log2                 out[5]  launches
+ *   out[6]  workspace bytes        out[7]  field products per record, the block scans' share left out
+ * (AMDMSM_FR_SCAN_NAIVE=1: one launch; an inversion keeps n records of workspace).  AMDMSM_ERR_BAD_ARG for a kind that
+ * names nothing, unknown bits or a tile out of range, AMDMSM_ERR_TOO_LARGE above 2^28 */
+#define AMDMSM_SCAN_KIND_A 0x100
+#define AMDMSM_SCAN_KIND_B 0x200
+#define AMDMSM_SCAN_KIND_INVERT 0x400
+int amdmsm_plan_fr_scan(int curve, size_t n, int kind_and_flags, int tile_log2, size_t out[8]);
+/* out = 1 / x in Fr, one record in host memory each, Montgomery residues or with plain != 0 plain integers; one Fermat
+   power on the host, no context: n^-1, g^-1 and omega^-1 of an inverse transform.  AMDMSM_ERR_BAD_ARG for 0 and for a
+   value not below r */
+int amdmsm_fr_inverse(int curve, const void *x, int plain, void *out);
 
 /* Sparse matrix times Fr vector -- the rows <A_i, z>, <B_i, z>, <C_i, z> of a constraint system on a resident
  * assignment, the vectors the transforms above start from -- and any other sparse linear map over Fr:

@@ -4425,3 +4425,247 @@ int amdmsm_fr_matrix_apply(amdmsm_ctx *ctx, uint64_t mat, const void *x, size_t 
 }
 
 }  // extern "C"
+
+// ---- scans and batch inversion over Fr vectors: y_i = a_i y_(i-1) + b_i, out[i] = 1 / in[i] -------------------------------
+namespace {
+
+constexpr int FRS_KIND_MASK = AMDMSM_SCAN_KIND_A | AMDMSM_SCAN_KIND_B | AMDMSM_SCAN_KIND_INVERT;
+constexpr int FRS_FLAG_MASK = AMDMSM_SCAN_REVERSE | AMDMSM_SCAN_EXCLUSIVE;
+
+bool frs_naive_env() {
+    const char *e = getenv("AMDMSM_FR_SCAN_NAIVE");
+    return e && *e && strcmp(e, "0") != 0;
+}
+
+// x^(r - 2) for a Montgomery residue x: one Fermat power, r - 2 scanned from its top bit
+fr_rec fr_inv_host(const fr_vtable *f, const fr_rec &x) {
+    uint32_t e[FR_MAX_WORDS];
+    uint64_t borrow = 2;
+    for (int j = 0; j < f->words; ++j) {
+        const uint64_t d = (uint64_t)f->modulus[j] - borrow;
+        e[j] = (uint32_t)d;
+        borrow = (d >> 63) & 1u;
+    }
+    fr_rec acc = fr_from_words(f, f->one);
+    for (int i = f->words * 32 - 1; i >= 0; --i) {
+        acc = fr_mul(f, acc, acc);
+        if ((e[i >> 5] >> (i & 31)) & 1u) acc = fr_mul(f, acc, x);
+    }
+    return acc;
+}
+
+// what a call runs with: the layout, and the host records as Montgomery residues
+struct frs_call {
+    frs_layout L;
+    bool plain = false, naive = false, invert = false;
+    int has_a = 0, has_b = 0, flags = 0;
+    fr_rec a_const, init;
+    size_t rec = 0;
+};
+
+// The argument rules of the four entries; nothing is launched or written and the context is not looked at before they
+// hold.  device: the vectors are HBM addresses (alignment, overlap).  vec_a: d_a / d_values; total: d_total / d_zero_count
+int frs_check(amdmsm_ctx *ctx, const fr_vtable *f, size_t n, const void *vec_a, const void *a_const, const void *vec_b,
+              const void *init, int flags, int tile_log2, const amdmsm_opts *opts, const void *out, const void *total, bool invert,
+              bool device, frs_call &c) {
+    c.rec = (size_t)f->words * 4;
+    c.plain = opts && opts->scalars_plain;
+    c.naive = frs_naive_env();
+    c.invert = invert;
+    c.flags = flags;
+    if (n > FRS_MAX_N) return fail(ctx, AMDMSM_ERR_TOO_LARGE, "n = " + std::to_string(n) + ": at most 2^28 records");
+    if (flags & ~FRS_FLAG_MASK) return fail(ctx, AMDMSM_ERR_BAD_ARG, "flags = " + std::to_string(flags) + ": unknown bits");
+    const char *na = invert ? "values" : "a", *no = "out";
+    if (!invert) {
+        if (vec_a && a_const) return fail(ctx, AMDMSM_ERR_BAD_ARG, "a and a_const: both given");
+        if (!vec_a && !a_const && !vec_b) return fail(ctx, AMDMSM_ERR_BAD_ARG, "a and b: both absent");
+    }
+    c.has_a = vec_a ? 1 : (a_const ? 2 : 0);
+    c.has_b = vec_b ? 1 : 0;
+    if (n) {
+        if (invert && !vec_a) return fail(ctx, AMDMSM_ERR_BAD_ARG, std::string(na) + ": null pointer");
+        if (!out) return fail(ctx, AMDMSM_ERR_BAD_ARG, std::string(no) + ": null pointer");
+    }
+    if (device) {
+        const std::string to = std::to_string(f->words % 4 ? 8 : 16) + " bytes";
+        if (n && fr_misaligned(f, {vec_a})) return fail(ctx, AMDMSM_ERR_BAD_ARG, std::string("d_") + na + ": not aligned to " + to);
+        if (n && fr_misaligned(f, {vec_b})) return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_b: not aligned to " + to);
+        if (n && fr_misaligned(f, {out})) return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_out: not aligned to " + to);
+        if (invert ? ((uintptr_t)total & 7) != 0 : fr_misaligned(f, {total}))
+            return fail(ctx, AMDMSM_ERR_BAD_ARG, invert ? "d_zero_count: not aligned to 8 bytes" : "d_total: not aligned to " + to);
+        const size_t bytes = n * c.rec;
+        if (n && vec_a && vec_a != out && ranges_overlap(vec_a, out, bytes))
+            return fail(ctx, AMDMSM_ERR_BAD_ARG, std::string("d_") + na + " and d_out overlap without being the same vector");
+        if (n && vec_b && vec_b != out && ranges_overlap(vec_b, out, bytes))
+            return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_b and d_out overlap without being the same vector");
+        if (n && total) {
+            const size_t tb = invert ? 8 : c.rec;
+            const uintptr_t t = (uintptr_t)total;
+            for (const void *v : {vec_a, vec_b, out})
+                if (v && t < (uintptr_t)v + bytes && (uintptr_t)v < t + tb)
+                    return fail(ctx, AMDMSM_ERR_BAD_ARG, invert ? "d_zero_count lies inside a vector" : "d_total lies inside a vector");
+        }
+    }
+    if (!frs_make_layout(n, tile_log2, c.rec, invert, c.naive, c.L))
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "tile_log2 = " + std::to_string(tile_log2) + ": 0 or " + std::to_string(FRS_TILE_MIN) +
+                                                 " .. " + std::to_string(FRS_TILE_MAX));
+    if (a_const && !fr_below_modulus(f, (const uint32_t *)a_const)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "a_const: not below r");
+    if (init && !fr_below_modulus(f, (const uint32_t *)init)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "init: not below r");
+    if (a_const) c.a_const = fr_read(f, a_const, c.plain);
+    if (init) c.init = fr_read(f, init, c.plain);
+    else if (!c.has_b) c.init = fr_from_words(f, f->one);
+    return AMDMSM_OK;
+}
+
+// the launches of one call on device vectors; ws: the layout's workspace
+int frs_run(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, const frs_call &c, size_t n, const void *d_a, const void *d_b,
+            void *d_out, void *d_total, char *ws) {
+    frs_args a = {};
+    a.a = (const uint32_t *)d_a;
+    a.b = (const uint32_t *)d_b;
+    a.out = (uint32_t *)d_out;
+    if (c.invert) a.zero_count = (uint64_t *)d_total;
+    else a.total = (uint32_t *)d_total;
+    a.ws_a = (uint32_t *)(ws + c.L.off_a);
+    a.ws_b = (uint32_t *)(ws + c.L.off_b);
+    a.ws_in = (uint32_t *)(ws + c.L.off_in);
+    a.ws_cnt = (uint32_t *)(ws + c.L.off_cnt);
+    a.n = n;
+    a.tiles = (uint32_t)c.L.tiles;
+    a.tile_log2 = c.L.tile_log2;
+    a.has_a = c.invert ? 1 : c.has_a;
+    a.has_b = c.has_b;
+    a.reverse = (c.flags & AMDMSM_SCAN_REVERSE) ? 1 : 0;
+    a.exclusive = (c.flags & AMDMSM_SCAN_EXCLUSIVE) ? 1 : 0;
+    a.plain = c.plain ? 1 : 0;
+    a.invert = c.invert ? 1 : 0;
+    memcpy(a.a_const, c.a_const.v, sizeof(a.a_const));
+    memcpy(a.init, c.init.v, sizeof(a.init));
+    if (c.naive) f->scan_naive(st, a);
+    else f->scan(st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return AMDMSM_OK;
+}
+
+int frs_device_entry(amdmsm_ctx *ctx, int curve, size_t n, const void *d_a, const void *a_const, const void *d_b, const void *init,
+                     int flags, int tile_log2, const amdmsm_opts *opts, void *d_out, void *d_total, bool invert) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
+    CHECK_OPTS(ctx, opts);
+    frs_call c;
+    int rc = frs_check(ctx, f, n, d_a, a_const, d_b, init, flags, tile_log2, opts, d_out, d_total, invert, true, c);
+    if (rc) return rc;
+    FR_ENTER(ctx);
+    if (!n && !d_total) return AMDMSM_OK;
+    hipStream_t st = stream_of(ctx, opts);
+    ws_slot *sl = nullptr;
+    rc = fft_begin(ctx, st, c.L.ws_bytes, sl);
+    if (rc) return rc;
+    fft_mark(ctx, st, 1);
+    rc = frs_run(ctx, f, st, c, n, d_a, d_b, d_out, d_total, (char *)sl->ws);
+    if (rc) return rc;
+    return fft_end(ctx, st, *sl, 1);
+}
+
+int frs_host_entry(amdmsm_ctx *ctx, int curve, size_t n, const void *a, const void *a_const, const void *b, const void *init,
+                   int flags, int tile_log2, const amdmsm_opts *opts, void *out, void *total, bool invert) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
+    CHECK_OPTS(ctx, opts);
+    frs_call c;
+    int rc = frs_check(ctx, f, n, a, a_const, b, init, flags, tile_log2, opts, out, total, invert, false, c);
+    if (rc) return rc;
+    FR_ENTER(ctx);
+    if (!n && !total) return AMDMSM_OK;
+    hipStream_t st = ctx->stream;
+    // the uploaded vectors, the total (or the zero count) and the kernels' workspace, in that order; the result takes
+    // the place of the first vector
+    const size_t vec = align_up((n ? n : 1) * c.rec, 256);
+    ws_slot *sl = nullptr;
+    rc = fft_begin(ctx, st, 2 * vec + 256 + c.L.ws_bytes, sl);
+    if (rc) return rc;
+    char *base = (char *)sl->ws;
+    void *d_a = a ? base : nullptr, *d_b = b ? base + vec : nullptr, *d_out = a ? base : base + vec;
+    void *d_total = total ? base + 2 * vec : nullptr;
+    if (n && a) HIP_TRY(ctx, hipMemcpyAsync(d_a, a, n * c.rec, hipMemcpyHostToDevice, st));
+    if (n && b) HIP_TRY(ctx, hipMemcpyAsync(d_b, b, n * c.rec, hipMemcpyHostToDevice, st));
+    fft_mark(ctx, st, 1);
+    rc = frs_run(ctx, f, st, c, n, d_a, d_b, d_out, d_total, base + 2 * vec + 256);
+    if (rc) {
+        (void)hipDeviceSynchronize();   // nothing of this call may still read the caller's vectors
+        return rc;
+    }
+    fft_mark(ctx, st, 2);
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, n * c.rec, hipMemcpyDeviceToHost, st));
+    if (total) HIP_TRY(ctx, hipMemcpyAsync(total, d_total, invert ? 8 : c.rec, hipMemcpyDeviceToHost, st));
+    rc = fft_end(ctx, st, *sl, 2);
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return rc;
+}
+
+}   // namespace
+
+extern "C" {
+
+int amdmsm_fr_inverse(int curve, const void *x, int plain, void *out) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return AMDMSM_ERR_UNSUPPORTED;
+    if (!x || !out) return AMDMSM_ERR_BAD_ARG;
+    const fr_rec raw = fr_from_words(f, (const uint32_t *)x), zero;
+    if (!fr_below_modulus(f, raw.v) || fr_same(f, raw, zero)) return AMDMSM_ERR_BAD_ARG;
+    fr_rec r = fr_inv_host(f, fr_read(f, x, plain != 0));
+    if (plain) {   // out of Montgomery form
+        fr_rec one;
+        one.v[0] = 1;
+        r = fr_mul(f, r, one);
+    }
+    memcpy(out, r.v, (size_t)f->words * 4);
+    return AMDMSM_OK;
+}
+
+int amdmsm_plan_fr_scan(int curve, size_t n, int kind_and_flags, int tile_log2, size_t out[8]) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return AMDMSM_ERR_UNSUPPORTED;
+    if (!out || (kind_and_flags & ~(FRS_KIND_MASK | FRS_FLAG_MASK))) return AMDMSM_ERR_BAD_ARG;
+    const bool invert = (kind_and_flags & AMDMSM_SCAN_KIND_INVERT) != 0;
+    const bool ha = (kind_and_flags & AMDMSM_SCAN_KIND_A) != 0, hb = (kind_and_flags & AMDMSM_SCAN_KIND_B) != 0;
+    if (invert ? (ha || hb || (kind_and_flags & FRS_FLAG_MASK)) : (!ha && !hb)) return AMDMSM_ERR_BAD_ARG;
+    if (n > FRS_MAX_N) return AMDMSM_ERR_TOO_LARGE;
+    frs_layout L;
+    const bool naive = frs_naive_env();
+    if (!frs_make_layout(n, tile_log2, (size_t)f->words * 4, invert, naive, L)) return AMDMSM_ERR_BAD_ARG;
+    out[0] = L.tile;
+    out[1] = L.per_lane;
+    out[2] = L.spine_step;
+    out[3] = FRS_TILE_MIN;
+    out[4] = FRS_TILE_MAX;
+    out[5] = (size_t)L.launches;
+    out[6] = L.ws_bytes;
+    // reduce and apply both compose a tile's maps (a product for A, one more for B under a), apply then one per record;
+    // an inversion: the tile products, the running products in a lane and two per record in the back-sweep
+    const size_t fold = (ha ? 1 : 0) + (ha && hb ? 1 : 0);
+    out[7] = invert ? (naive ? 3 : 4) : (naive ? (ha ? 1 : 0) : 2 * fold + (ha ? 1 : 0));
+    return AMDMSM_OK;
+}
+
+int amdmsm_fr_scan_device(amdmsm_ctx *ctx, int curve, size_t n, const void *d_a, const void *a_const, const void *d_b,
+                          const void *init, int flags, int tile_log2, const amdmsm_opts *opts, void *d_out, void *d_total) {
+    return frs_device_entry(ctx, curve, n, d_a, a_const, d_b, init, flags, tile_log2, opts, d_out, d_total, false);
+}
+
+int amdmsm_fr_scan(amdmsm_ctx *ctx, int curve, size_t n, const void *a, const void *a_const, const void *b, const void *init,
+                   int flags, int tile_log2, const amdmsm_opts *opts, void *out, void *total) {
+    return frs_host_entry(ctx, curve, n, a, a_const, b, init, flags, tile_log2, opts, out, total, false);
+}
+
+int amdmsm_fr_batch_invert_device(amdmsm_ctx *ctx, int curve, size_t n, const void *d_values, int tile_log2, const amdmsm_opts *opts,
+                                  void *d_out, uint64_t *d_zero_count) {
+    return frs_device_entry(ctx, curve, n, d_values, nullptr, nullptr, nullptr, 0, tile_log2, opts, d_out, d_zero_count, true);
+}
+
+int amdmsm_fr_batch_invert(amdmsm_ctx *ctx, int curve, size_t n, const void *values, const amdmsm_opts *opts, void *out,
+                           uint64_t *zero_count) {
+    return frs_host_entry(ctx, curve, n, values, nullptr, nullptr, nullptr, 0, 0, opts, out, zero_count, true);
+}
+
+}  // extern "C"

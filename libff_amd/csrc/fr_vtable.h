@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "fr_matrix_layout.h"
+#include "fr_scan_layout.h"
 
 namespace amdmsm {
 
@@ -44,6 +45,23 @@ struct frm_args {
     size_t n_rows, n_out;        // out[n_rows .. n_out - 1] = 0
 };
 
+// one scan or batch inversion (k_frs_reduce, k_frs_spine, k_frs_apply and their inversion forms; fr_scan_layout.h has the
+// tiles and the workspace).  Positions, not records: position p is record frs_record(n, reverse, p)
+struct frs_args {
+    const uint32_t* a;           // has_a == 1: the vector; an inversion: the values
+    const uint32_t* b;
+    uint32_t* out;
+    uint32_t* total;             // one record or null
+    uint64_t* zero_count;        // an inversion: the number of zero records, or null
+    uint32_t *ws_a, *ws_b, *ws_in, *ws_cnt;   // workspace; the naive inversion: ws_a holds n running products
+    size_t n;
+    uint32_t tiles;
+    int tile_log2;
+    int has_a, has_b;            // has_a: 0 = every a_i is 1, 1 = a vector, 2 = a_const
+    int reverse, exclusive, plain, invert;
+    uint32_t a_const[FR_MAX_WORDS], init[FR_MAX_WORDS];   // Montgomery
+};
+
 struct fr_vtable {
     int curve, words, two_adicity;
     uint32_t inv;                                  // -r^-1 mod 2^32
@@ -60,6 +78,10 @@ struct fr_vtable {
     // the same from the caller's CSR (coefficients Montgomery), one lane per row: AMDMSM_FR_MATRIX_NAIVE=1
     void (*matrix_naive)(hipStream_t, size_t n_rows, size_t n_out, const uint64_t* d_offsets, const uint32_t* d_cols,
                          const uint32_t* d_coef, const uint32_t* d_x, uint32_t* d_out);
+    // y_i = a_i y_(i-1) + b_i over the positions, or out[i] = 1 / a[i]: reduce, spine, apply in stream order
+    void (*scan)(hipStream_t, const frs_args&);
+    // the same by one lane that walks the vector: AMDMSM_FR_SCAN_NAIVE=1
+    void (*scan_naive)(hipStream_t, const frs_args&);
 };
 
 const fr_vtable* frvt_alt_bn128() __attribute__((weak));

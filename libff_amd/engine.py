@@ -70,6 +70,8 @@ EXPORTED_SYMBOLS = [
     "amdmsm_fr_muladd_device",
     "amdmsm_plan_fr_matrix", "amdmsm_fr_matrix_load", "amdmsm_fr_matrix_apply", "amdmsm_fr_matrix_apply_device",
     "amdmsm_fr_matrix_free",
+    "amdmsm_fr_scan", "amdmsm_fr_scan_device", "amdmsm_fr_batch_invert", "amdmsm_fr_batch_invert_device", "amdmsm_plan_fr_scan",
+    "amdmsm_fr_inverse",
 ]
 SEG_SHARED_BASES = 1            # include/amdmsm.h AMDMSM_SEG_SHARED_BASES
 SEG_LONG_NEVER = 2 ** 64 - 1    # long_from = SIZE_MAX: no segment takes the single-MSM route
@@ -353,6 +355,48 @@ def _fr_record(x, limbs, r, plain):
     if not plain:
         x = x * (1 << (64 * limbs)) % r
     return np.frombuffer(x.to_bytes(8 * limbs, "little"), dtype="<u8").astype(np.uint64)
+
+
+# include/amdmsm.h AMDMSM_SCAN_*
+SCAN_REVERSE, SCAN_EXCLUSIVE = 1, 2
+SCAN_KIND_A, SCAN_KIND_B, SCAN_KIND_INVERT = 0x100, 0x200, 0x400
+
+
+def plan_fr_scan(curve, n, a=True, b=False, invert=False, reverse=False, exclusive=False, tile_log2=0):
+    """What ``Engine.fr_scan`` (``a`` / ``b``: which operands are given) or ``Engine.fr_batch_invert`` (``invert``) runs
+    for ``n`` records (``amdmsm_plan_fr_scan``, read-only, no device): records per tile and per lane, tiles per spine
+    step, the range of ``tile_log2``, launches, workspace bytes and field products per record."""
+    kind = SCAN_KIND_INVERT if invert else (SCAN_KIND_A if a else 0) | (SCAN_KIND_B if b else 0)
+    kind |= (SCAN_REVERSE if reverse else 0) | (SCAN_EXCLUSIVE if exclusive else 0)
+    out = (ctypes.c_size_t * 8)()
+    rc = load_library().amdmsm_plan_fr_scan(curve, ctypes.c_size_t(n), kind, int(tile_log2), out)
+    if rc:
+        raise AmdMsmError(f"amdmsm_plan_fr_scan: {rc}")
+    return {"tile": out[0], "per_lane": out[1], "spine_step": out[2], "tile_min": out[3], "tile_max": out[4],
+            "launches": out[5], "workspace_bytes": out[6], "products_per_record": out[7]}
+
+
+def fr_inverse(curve, x, plain=True):
+    """``1 / x`` in Fr of the curve (``amdmsm_fr_inverse``: one Fermat power on the host), ``x`` and the result ints --
+    with ``plain=False`` both are taken as Montgomery residues.  ValueError for 0 and for a value not below r."""
+    limbs = sizes(curve, G1)["fr_bytes"] // 8
+    x = int(x)
+    if x < 0 or x >> (64 * limbs):
+        raise ValueError("x does not fit an Fr record")
+    src = np.frombuffer(x.to_bytes(8 * limbs, "little"), dtype="<u8").astype(np.uint64)
+    out = np.zeros(limbs, dtype=np.uint64)
+    rc = load_library().amdmsm_fr_inverse(curve, _np_ptr(src), int(bool(plain)), _np_ptr(out))
+    if rc:
+        raise ValueError(f"amdmsm_fr_inverse: {rc} (x = 0 or x >= r)")
+    return int.from_bytes(out.tobytes(), "little")
+
+
+def _fr_host_record(x, limbs, r, plain):
+    """one host record of a scan: None, an int (reduced and put in the form ``plain`` says) or an array of fr_limbs
+    words taken as it stands"""
+    if x is None or isinstance(x, np.ndarray):
+        return x if x is None else np.ascontiguousarray(x, dtype=np.uint64).reshape(limbs)
+    return _fr_record(x, limbs, r, plain)
 
 
 def endomorphism_info(curve, group):
@@ -974,6 +1018,67 @@ class Engine:
                                                            None if d_x is None else _vp(d_x), ctypes.c_size_t(n_x),
                                                            None if d_out is None else _vp(d_out), ctypes.c_size_t(n_out),
                                                            ctypes.byref(o)), "amdmsm_fr_matrix_apply_device")
+
+    def _scan_flags(self, reverse, exclusive):
+        return (SCAN_REVERSE if reverse else 0) | (SCAN_EXCLUSIVE if exclusive else 0)
+
+    def fr_scan(self, curve, a=None, b=None, *, a_const=None, init=None, reverse=False, exclusive=False, plain=False,
+                tile_log2=0, flags=None):
+        """The recurrence ``y_i = a_i y_(i-1) + b_i`` over host arrays (``amdmsm_fr_scan``): ``a`` / ``b`` (n, fr_limbs)
+        uint64 records or None, ``a_const`` / ``init`` ints (or records as arrays).  ``reverse``: from the last record
+        down; ``exclusive``: ``out[i]`` is the value that enters record i.  Returns ``(out, total)``, total a record."""
+        limbs = sizes(curve, G1)["fr_bytes"] // 8
+        r = fr_modulus(curve, G1)
+        a = None if a is None else np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, limbs)
+        b = None if b is None else np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, limbs)
+        n = a.shape[0] if a is not None else (b.shape[0] if b is not None else 0)
+        assert a is None or b is None or a.shape == b.shape, "a and b: one record each per position"
+        out, total = np.zeros((n, limbs), dtype=np.uint64), np.zeros(limbs, dtype=np.uint64)
+        ac, ini = _fr_host_record(a_const, limbs, r, plain), _fr_host_record(init, limbs, r, plain)
+        o = self._opts(scalars_plain=plain)
+        ptr = lambda v: None if v is None else _np_ptr(v)
+        rc = self.lib.amdmsm_fr_scan(self.h, curve, ctypes.c_size_t(n), ptr(a), ptr(ac), ptr(b), ptr(ini),
+                                     self._scan_flags(reverse, exclusive) if flags is None else int(flags), int(tile_log2),
+                                     ctypes.byref(o), _np_ptr(out), _np_ptr(total))
+        self._check(rc, "amdmsm_fr_scan")
+        return out, total
+
+    def fr_scan_device(self, curve, n, d_out, d_a=None, d_b=None, *, a_const=None, init=None, d_total=None, reverse=False,
+                       exclusive=False, plain=False, tile_log2=0, stream=None, flags=None):
+        """``fr_scan`` on ``n`` device-resident records (``amdmsm_fr_scan_device``); ``d_out`` may be ``d_a`` or ``d_b``,
+        ``d_total`` (one record) may be None; enqueued on ``stream``, not synchronised."""
+        limbs = sizes(curve, G1)["fr_bytes"] // 8
+        r = fr_modulus(curve, G1)
+        ac, ini = _fr_host_record(a_const, limbs, r, plain), _fr_host_record(init, limbs, r, plain)
+        o = self._opts(scalars_plain=plain, stream=stream)
+        ptr = lambda v: None if v is None else _np_ptr(v)
+        dev = lambda v: None if v is None else _vp(v)
+        self._check(self.lib.amdmsm_fr_scan_device(self.h, curve, ctypes.c_size_t(n), dev(d_a), ptr(ac), dev(d_b), ptr(ini),
+                                                   self._scan_flags(reverse, exclusive) if flags is None else int(flags),
+                                                   int(tile_log2), ctypes.byref(o), dev(d_out), dev(d_total)),
+                    "amdmsm_fr_scan_device")
+
+    def fr_batch_invert(self, curve, values, plain=False):
+        """``out[i] = 1 / values[i]``, 0 where ``values[i]`` is 0 (``amdmsm_fr_batch_invert``): (n, fr_limbs) uint64
+        records in the form ``plain`` says.  Returns ``(out, zero_count)``."""
+        limbs = sizes(curve, G1)["fr_bytes"] // 8
+        values = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, limbs)
+        n = values.shape[0]
+        out, zeros = np.zeros((n, limbs), dtype=np.uint64), ctypes.c_uint64(0)
+        o = self._opts(scalars_plain=plain)
+        rc = self.lib.amdmsm_fr_batch_invert(self.h, curve, ctypes.c_size_t(n), _np_ptr(values) if n else None, ctypes.byref(o),
+                                             _np_ptr(out) if n else None, ctypes.byref(zeros))
+        self._check(rc, "amdmsm_fr_batch_invert")
+        return out, int(zeros.value)
+
+    def fr_batch_invert_device(self, curve, n, d_values, d_out, d_zero_count=None, plain=False, tile_log2=0, stream=None):
+        """``fr_batch_invert`` on ``n`` device-resident records (``amdmsm_fr_batch_invert_device``); ``d_out`` may be
+        ``d_values``; ``d_zero_count``: a uint64 in device memory or None; enqueued on ``stream``, not synchronised."""
+        o = self._opts(scalars_plain=plain, stream=stream)
+        dev = lambda v: None if v is None else _vp(v)
+        self._check(self.lib.amdmsm_fr_batch_invert_device(self.h, curve, ctypes.c_size_t(n), dev(d_values), int(tile_log2),
+                                                           ctypes.byref(o), dev(d_out), dev(d_zero_count)),
+                    "amdmsm_fr_batch_invert_device")
 
     def batch_exp_timings(self):
         """device times (ms) of the last batch_exp: inputs H2D, window table (0 = reused), exponentiations, results D2H"""
