@@ -140,6 +140,12 @@ int amdmsm_plan_ex(int curve, int group, size_t n, int window_bits, int endomorp
    one piece (longer bins go chunk by chunk), out[4] = entries above which a coarse bin is spread over the whole grid */
 int amdmsm_plan_sort(int curve, int group, size_t n, int window_bits, int endomorphism, size_t out[5]);
 
+/* read-only: the grid of that sort's first pass (the digit pass) over `items` work items -- scalars, or 16-byte vectors
+   of packed integers with block_min = 256 -- on a device that holds `workgroups` of its workgroups at once.  Workgroup g
+   walks blocks g, g + out[2], ... of out[0] consecutive items: out[0] = items per block, out[1] = blocks, out[2] =
+   workgroups launched.  block_min = 0: the workgroup size */
+int amdmsm_plan_sort_digit_grid(size_t items, unsigned block_min, unsigned workgroups, size_t out[3]);
+
 /* read-only: the top window of that plan, scalars_plain as in amdmsm_opts.  out[0] = tb, the bits its bucket index
    |digit| - 1 can have -- a bound that holds for every admitted input, never taken from the data: the split's constants,
    or the scalar field's bit length for Montgomery scalars, or the word length for plain ones without the split (k >= r

@@ -537,6 +537,18 @@ int ensure_ws(amdmsm_ctx *ctx, ws_slot &sl, size_t bytes) {
 }
 
 constexpr uint64_t TIMING_RING = 64;
+// The events of `ring`, aux_ev and fft_ev only measure time, so they are created with hipEventDisableSystemFence: a
+// plain event writes the caches back and invalidates them where it is recorded -- six times inside every timed call --
+// and the kernels behind it pay for that (2^20 points: 1.593 -> 1.578 ms per step, profiles/digit_pass_and_step_gaps.txt).
+// The flag is right for them because their only readers are hipEventElapsedTime calls behind an event or stream
+// synchronisation of the reader's own, and nothing on the host looks at memory on the strength of one of them.
+// ctx->ev keeps the default flags: amdmsm_mul_bench_device / amdmsm_madd_bench_device return behind a synchronisation on
+// the event itself, and their callers then read what the probe kernel wrote.  The events that order streams (done,
+// tail_done, acc_done, ov_*, bases_ready, host_done) keep theirs too.  AMDMSM_TIMING_NOFENCE=0: plain events (A/B runs).
+hipError_t timing_event(hipEvent_t *e) {
+    static const bool nofence = !(getenv("AMDMSM_TIMING_NOFENCE") && atoi(getenv("AMDMSM_TIMING_NOFENCE")) == 0);
+    return nofence ? hipEventCreateWithFlags(e, hipEventDisableSystemFence) : hipEventCreate(e);
+}
 void record(amdmsm_ctx *ctx, ws_slot &, int idx, hipStream_t st) {
     if (ctx->timing) (void)hipEventRecord(ctx->ring[ctx->ticket % TIMING_RING][idx], st);
 }
@@ -1129,14 +1141,14 @@ int amdmsm_ctx_create(int device, amdmsm_ctx **out) {
     }
     for (auto &set : ctx->ring) {
         for (auto &e : set) {
-            if (hipEventCreate(&e) != hipSuccess) {
+            if (timing_event(&e) != hipSuccess) {
                 delete ctx;
                 return AMDMSM_ERR_HIP;
             }
         }
     }
     for (auto &e : ctx->aux_ev) {
-        if (hipEventCreate(&e) != hipSuccess) {
+        if (timing_event(&e) != hipSuccess) {
             delete ctx;
             return AMDMSM_ERR_HIP;
         }
@@ -1279,6 +1291,16 @@ int amdmsm_plan_sort(int curve, int group, size_t n, int window_bits, int endomo
     out[2] = (size_t)g.fb;
     out[3] = g.chunk_cap;
     out[4] = g.big_thresh;
+    return AMDMSM_OK;
+}
+
+int amdmsm_plan_sort_digit_grid(size_t items, unsigned block_min, unsigned workgroups, size_t out[3]) {
+    if (!out || workgroups == 0) return AMDMSM_ERR_BAD_ARG;
+    // the launcher's own function (msm_group.hip sort_launch)
+    const digit_grid g = sort_digit_grid(items, block_min, workgroups);
+    out[0] = g.block;
+    out[1] = g.blocks;
+    out[2] = g.grid;
     return AMDMSM_OK;
 }
 
@@ -3321,7 +3343,7 @@ void fft_mark(amdmsm_ctx *ctx, hipStream_t st, int phase, bool last = false) {
     if (ctx->fft_marks >= FFT_MAX_MARKS && !last) return;   // the time stays with the phase of the mark before
     if (ctx->fft_marks == ctx->fft_ev.size()) {
         hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) return;
+        if (timing_event(&e) != hipSuccess) return;
         ctx->fft_ev.push_back(e);
         ctx->fft_phase.push_back(0);
     }

@@ -56,6 +56,36 @@ inline sort_geom sort_geometry(size_t n, int c, int W) {
     return g;
 }
 
+// Grid of the digit pass (k_sort_digits and its siblings).  The work items -- scalars, or 16-byte vectors of packed
+// integers -- are cut into blocks of `block` consecutive items, thread t of a workgroup takes item block_index * block + t,
+// and workgroup g of `grid` walks blocks g, g + grid, g + 2 grid, ...  It keeps ONE histogram in LDS over all of them and
+// merges it into the global counters once, so a call costs grid * (counters per workgroup) global atomics whatever its
+// length; wgs_max = the workgroups the device holds at once (or AMDMSM_SORT_DIGIT_WGS), so no workgroup waits for a CU.
+// block is the workgroup size SORT_DIGIT_TPB; only where the items do not fill wgs_max such blocks is it halved, down to
+// block_min (packed integers: a few thousand items are a large input).
+constexpr uint32_t SORT_DIGIT_TPB = 1024;   // threads of a digit-pass workgroup (msm_group.hip SORT_TPB is this value)
+struct digit_grid {
+    uint32_t block;   // items per block, a power of two <= SORT_DIGIT_TPB
+    size_t blocks;    // ceil(items / block)
+    uint32_t grid;    // workgroups launched: min(blocks, wgs_max), 0 for no items
+};
+// wgs_max = 0: the resident count is not known (a failed query).  Then the grid is the one the pass had before it walked
+// blocks -- 1024 workgroups, from 8192 blocks up one workgroup per 8 blocks -- which is right on any device.
+inline digit_grid sort_digit_grid(size_t items, uint32_t block_min, uint32_t wgs_max) {
+    digit_grid g;
+    const uint32_t tpb = SORT_DIGIT_TPB;
+    if (wgs_max < 1) {
+        const size_t b = (items + tpb - 1) / tpb;
+        wgs_max = (uint32_t)(b / 8 > 1024 ? (b + 7) / 8 : 1024);
+    }
+    if (block_min < 1 || block_min > tpb) block_min = tpb;
+    g.block = tpb;
+    while (g.block > block_min && (items + g.block - 1) / g.block < wgs_max) g.block >>= 1;
+    g.blocks = (items + g.block - 1) / g.block;
+    g.grid = (uint32_t)(g.blocks < wgs_max ? g.blocks : wgs_max);
+    return g;
+}
+
 // The top window is short: its bucket index |digit| - 1 stays below 2^tb, a property of the plan and not of the data.
 // bound_log2_x1000 > 0 (endomorphism split): every half scalar is at most 2^(bound_log2_x1000 / 1000), so its top
 // window holds at most floor(2^e), e = bound - c (W - 1) bits, before the recoding carry of 1 -- an index of at most

@@ -572,7 +572,7 @@ __global__ void __launch_bounds__(SCAN_TPB) k_scan(uint32_t* __restrict__ counts
 //   k_sort_fine     workgroup (bin, w): LDS histogram of the bin by the low FB bits -> ends[],
 //                   then chunk-wise LDS counting sort -> lists[w] (runs per fine bucket)
 // bucket index = |digit| - 1 = (coarse << FB) | fine, HB = min(10, c-1), FB = c-1-HB.
-constexpr int SORT_TPB = 1024;
+constexpr int SORT_TPB = (int)SORT_DIGIT_TPB;   // 1024 (group_vtable.h, beside the digit pass's grid rule)
 #ifndef AMDMSM_SORT_TILE
 #define AMDMSM_SORT_TILE 16384
 #endif
@@ -633,7 +633,7 @@ AMDMSM_DEV uint32_t block_exclusive_scan(const uint32_t* cnt, uint32_t* out, uin
 }
 
 __global__ void __launch_bounds__(SORT_TPB) k_sort_digits(const uint32_t* __restrict__ scalars, size_t n, int mont, int c,
-                                                          int W, int hb, uint32_t per_block, int32_t* __restrict__ digits,
+                                                          int W, int hb, int32_t* __restrict__ digits,
                                                           size_t stride, uint32_t* __restrict__ coarse_counts, int mode,
                                                           int dtop) {
     // mode 1 (flat): the W digits of scalar i are entries i*W .. i*W+W-1 of ONE list (they index a
@@ -647,9 +647,10 @@ __global__ void __launch_bounds__(SORT_TPB) k_sort_digits(const uint32_t* __rest
     const uint32_t nctr = flat ? nbin : (uint32_t)W * nbin;
     for (uint32_t j = threadIdx.x; j < nctr; j += SORT_TPB) smem[j] = 0;
     __syncthreads();
-    const size_t base = (size_t)blockIdx.x * per_block;
-    for (uint32_t k = threadIdx.x; k < per_block; k += SORT_TPB) {
-        const size_t i = base + k;
+    // blocks blockIdx.x, blockIdx.x + gridDim.x, ... of SORT_TPB scalars (group_vtable.h sort_digit_grid), one histogram
+    const size_t nblocks = (n + SORT_TPB - 1) / SORT_TPB;
+    for (size_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
+        const size_t i = blk * SORT_TPB + threadIdx.x;
         if (i >= n) break;
         uint32_t s[FRW];
         load_scalar(s, scalars, i, mont);
@@ -702,7 +703,7 @@ AMDMSM_DEV void load_scalar_sel(uint32_t (&s)[FRW], const uint32_t* shared, cons
 // k_sort_digits with the selecting load.  A kernel of its own, body and all: sharing the body with k_sort_digits through
 // a template changed that kernel's register allocation, and the code of the existing call paths is to stay as it is.
 __global__ void __launch_bounds__(SORT_TPB) k_sort_digits_sel(const uint32_t* __restrict__ shared, size_t n, int mont, int c,
-                                                              int W, int hb, uint32_t per_block, int32_t* __restrict__ digits,
+                                                              int W, int hb, int32_t* __restrict__ digits,
                                                               size_t stride, uint32_t* __restrict__ coarse_counts, int mode,
                                                               const uint32_t* __restrict__ index, size_t offset,
                                                               size_t shared_n, uint32_t* __restrict__ flag, int dtop) {
@@ -718,9 +719,10 @@ __global__ void __launch_bounds__(SORT_TPB) k_sort_digits_sel(const uint32_t* __
     const uint32_t nctr = flat ? nbin : (uint32_t)W * nbin;
     for (uint32_t j = threadIdx.x; j < nctr; j += SORT_TPB) smem[j] = 0;
     __syncthreads();
-    const size_t base = (size_t)blockIdx.x * per_block;
-    for (uint32_t k = threadIdx.x; k < per_block; k += SORT_TPB) {
-        const size_t i = base + k;
+    // blocks blockIdx.x, blockIdx.x + gridDim.x, ... of SORT_TPB scalars (group_vtable.h sort_digit_grid), one histogram
+    const size_t nblocks = (n + SORT_TPB - 1) / SORT_TPB;
+    for (size_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
+        const size_t i = blk * SORT_TPB + threadIdx.x;
         if (i >= n) break;
         uint32_t s[FRW];
         load_scalar_sel(s, shared, sel, i, mont);
@@ -863,7 +865,7 @@ __global__ void __launch_bounds__(TPB) k_scalar_bits(const void* __restrict__ sc
 // kind's full width tests nothing and flag is not touched.
 template <int KIND>
 __global__ void __launch_bounds__(SORT_TPB) k_sort_digits_short(const void* __restrict__ scalars, size_t n, int mont, int c,
-                                                                int W, int hb, uint32_t per_block, int32_t* __restrict__ digits,
+                                                                int W, int hb, uint32_t block, int32_t* __restrict__ digits,
                                                                 size_t stride, uint32_t* __restrict__ coarse_counts,
                                                                 int limit_bits, uint32_t* __restrict__ flag) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];   // [W][2^hb]
@@ -872,10 +874,12 @@ __global__ void __launch_bounds__(SORT_TPB) k_sort_digits_short(const void* __re
     const uint32_t nctr = (uint32_t)W * nbin;
     for (uint32_t j = threadIdx.x; j < nctr; j += SORT_TPB) smem[j] = 0;
     __syncthreads();
-    const size_t base = (size_t)blockIdx.x * per_block;
+    // blocks blockIdx.x, blockIdx.x + gridDim.x, ... of `block` <= SORT_TPB work items (group_vtable.h sort_digit_grid),
+    // one histogram; the threads at and past `block` of a workgroup only help to clear and to merge it
     if constexpr (KIND == 0) {
-        for (uint32_t k = threadIdx.x; k < per_block; k += SORT_TPB) {
-            const size_t i = base + k;
+        const size_t nblocks = (n + block - 1) / block;
+        for (size_t blk = blockIdx.x; blk < nblocks && threadIdx.x < block; blk += gridDim.x) {
+            const size_t i = blk * block + threadIdx.x;
             if (i >= n) break;
             uint32_t s[FRW];
             load_scalar(s, reinterpret_cast<const uint32_t*>(scalars), i, mont);
@@ -918,8 +922,9 @@ __global__ void __launch_bounds__(SORT_TPB) k_sort_digits_short(const void* __re
                 }
             });
         };
-        for (uint32_t k = threadIdx.x; k < per_block; k += SORT_TPB) {
-            const size_t t = base + k;
+        const size_t nblocks = (items + block - 1) / block;
+        for (size_t blk = blockIdx.x; blk < nblocks && threadIdx.x < block; blk += gridDim.x) {
+            const size_t t = blk * block + threadIdx.x;
             if (t >= items) break;
             if (t < sp.nvec) {
                 uint32_t v[4];
@@ -3912,6 +3917,38 @@ int l_sort_top_window(int mode, int mont, int c, int W, size_t columns, int* tb_
     if (tb_out) *tb_out = tb;
     return flat ? 0 : sort_top_shift(tb, c, W, sort_geometry(columns, c, W).fb);
 }
+// Workgroups of a digit-pass kernel the current device holds at once with `lds` bytes of dynamic LDS: resident workgroups
+// per CU times CUs, asked once per (thread, device, kernel, LDS size) and remembered -- consecutive calls of a context
+// repeat the same question.  AMDMSM_SORT_DIGIT_WGS overrides.
+uint32_t digit_pass_workgroups(const void* kernel, size_t lds) {
+    // AMDMSM_SORT_DIGIT_WGS=k: the digit pass on k workgroups (tests, sweeps); 0 / unset: what the device holds at once
+    static const int forced = getenv("AMDMSM_SORT_DIGIT_WGS") ? atoi(getenv("AMDMSM_SORT_DIGIT_WGS")) : 0;
+    if (forced > 0) return (uint32_t)forced;
+    struct answer {
+        int dev;
+        const void* kernel;
+        size_t lds;
+        uint32_t wgs;
+    };
+    // seven digit kernels (k_sort_digits, _sel, _short<0, 1, 2, 4, 8>), each with the LDS sizes of the plans in use
+    constexpr unsigned MEMO = 32;
+    thread_local answer memo[MEMO] = {};
+    thread_local unsigned next = 0;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    for (const answer& a : memo)
+        if (a.wgs && a.dev == dev && a.kernel == kernel && a.lds == lds) return a.wgs;
+    int cus = 0, per_cu = 0;
+    // a query that fails is not remembered and not replaced by a guess: 0 = unknown, the grid rule's fallback
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0 ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, SORT_TPB, lds) != hipSuccess || per_cu <= 0) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    answer& a = memo[next++ % MEMO];
+    a = answer{dev, kernel, lds, (uint32_t)cus * (uint32_t)per_cu};
+    return a.wgs;
+}
 // digits / lists may alias (digits are dead once k_sort_coarse has run)
 // sel != null: the selecting form of the digit pass (group_vtable::sort_sel); everything behind it is the same
 void sort_launch(hipStream_t st, const uint32_t* scalars, size_t n, int mont, int c, int W, uint32_t* coarse,
@@ -3931,35 +3968,38 @@ void sort_launch(hipStream_t st, const uint32_t* scalars, size_t n, int mont, in
     // by the data and have no bound of the plan's
     const int dtop = ss ? 0 : l_sort_top_window(mode, mont, c, W, ne, nullptr);
     const uint32_t wtop = (uint32_t)We - 1u;
-    // scalars per k_sort_digits workgroup: enough workgroups for every CU, few enough global atomics
-    uint32_t per_block = 8192;
-    while (per_block > SORT_TPB && (n + per_block - 1) / per_block < 1024) per_block >>= 1;
+    // The digit pass on at most the workgroups the device holds at once, each with one LDS histogram over all its blocks
+    // and one merge into the global counters (group_vtable.h sort_digit_grid).  The grid used to be 1024 workgroups or
+    // more whatever the length, so a 2^20-point call paid two global atomics per scalar on the same 65 cache lines.
+    const size_t lds = (size_t)We * nbin * 4;
     if (ss) {
-        // packed integers: a work item is one 16-byte vector of elements, so the workgroups are cut by items and may
-        // be smaller than SORT_TPB items (a million bytes are 65536 items)
+        // packed integers: a work item is one 16-byte vector of elements, so a block may be smaller than SORT_TPB items
+        // (a million bytes are 65536 items)
         const int k = ss->kind;
         const size_t items = k == 1 ? packed_items<1>(scalars, n) : k == 2 ? packed_items<2>(scalars, n) : k == 4 ? packed_items<4>(scalars, n)
                              : k == 8 ? packed_items<8>(scalars, n) : n;
-        uint32_t pb = 8192;
-        while (pb > (k ? 256u : (uint32_t)SORT_TPB) && (items + pb - 1) / pb < 1024) pb >>= 1;
-        const dim3 grid((unsigned)((items + pb - 1) / pb));
-        const size_t lds = (size_t)W * nbin * 4;
 #define AMDMSM_LAUNCH_SHORT(K)                                                                                              \
-    hipLaunchKernelGGL(k_sort_digits_short<K>, grid, dim3(SORT_TPB), lds, st, (const void*)scalars, n, mont, c, W, hb, pb, digits, \
-                       stride, coarse, ss->limit_bits, ss->flag)
+    do {                                                                                                                    \
+        const digit_grid dg = sort_digit_grid(items, K ? 256u : (uint32_t)SORT_TPB,                                         \
+                                              digit_pass_workgroups((const void*)k_sort_digits_short<K>, lds));             \
+        hipLaunchKernelGGL(k_sort_digits_short<K>, dim3(dg.grid), dim3(SORT_TPB), lds, st, (const void*)scalars, n, mont, c, W, hb, \
+                           dg.block, digits, stride, coarse, ss->limit_bits, ss->flag);                                   \
+    } while (0)
         if (k == 1) AMDMSM_LAUNCH_SHORT(1);
         else if (k == 2) AMDMSM_LAUNCH_SHORT(2);
         else if (k == 4) AMDMSM_LAUNCH_SHORT(4);
         else if (k == 8) AMDMSM_LAUNCH_SHORT(8);
         else AMDMSM_LAUNCH_SHORT(0);
 #undef AMDMSM_LAUNCH_SHORT
-    } else if (sel)
-        hipLaunchKernelGGL(k_sort_digits_sel, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(SORT_TPB),
-                           (size_t)(flat ? 1 : W) * nbin * 4, st, scalars, n, mont, c, W, hb, per_block, digits, stride, coarse,
-                           mode, sel->index, sel->offset, sel->shared_n, sel->flag, dtop);
-    else
-        hipLaunchKernelGGL(k_sort_digits, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(SORT_TPB),
-                           (size_t)(flat ? 1 : W) * nbin * 4, st, scalars, n, mont, c, W, hb, per_block, digits, stride, coarse, mode, dtop);
+    } else if (sel) {
+        const digit_grid dg = sort_digit_grid(n, SORT_TPB, digit_pass_workgroups((const void*)k_sort_digits_sel, lds));
+        hipLaunchKernelGGL(k_sort_digits_sel, dim3(dg.grid), dim3(SORT_TPB), lds, st, scalars, n, mont, c, W, hb, digits, stride,
+                           coarse, mode, sel->index, sel->offset, sel->shared_n, sel->flag, dtop);
+    } else {
+        const digit_grid dg = sort_digit_grid(n, SORT_TPB, digit_pass_workgroups((const void*)k_sort_digits, lds));
+        hipLaunchKernelGGL(k_sort_digits, dim3(dg.grid), dim3(SORT_TPB), lds, st, scalars, n, mont, c, W, hb, digits, stride,
+                           coarse, mode, dtop);
+    }
     sort_key_t* tmp_key16 = reinterpret_cast<sort_key_t*>(tmp_key);   // W * stride fine keys
     const dim3 coarse_grid((unsigned)((ne + SORT_TILE - 1) / SORT_TILE), We);
     if (c <= 17)   // the bucket index has c - 1 bits

@@ -43,7 +43,7 @@ MAX_PHASES = 8
 
 EXPORTED_SYMBOLS = [
     "amdmsm_abi_version", "amdmsm_device_count", "amdmsm_ctx_create", "amdmsm_ctx_destroy", "amdmsm_strerror",
-    "amdmsm_last_error", "amdmsm_sizes", "amdmsm_plan", "amdmsm_plan_ex", "amdmsm_plan_sort", "amdmsm_plan_top_window", "amdmsm_endomorphism_info",
+    "amdmsm_last_error", "amdmsm_sizes", "amdmsm_plan", "amdmsm_plan_ex", "amdmsm_plan_sort", "amdmsm_plan_sort_digit_grid", "amdmsm_plan_top_window", "amdmsm_endomorphism_info",
     "amdmsm_endomorphism_digits_device", "amdmsm_pippenger_optimal_c",
     "amdmsm_bdlo12_signed_optimal_c", "amdmsm_multi_exp", "amdmsm_multi_exp_batch", "amdmsm_multi_exp_batch_items",
     "amdmsm_msm_device_batch_items", "amdmsm_multi_exp_filter_one_zero",
@@ -208,6 +208,16 @@ def plan_sort(curve, group, n, window_bits=0, endomorphism=0):
     if rc:
         raise AmdMsmError(f"amdmsm_plan_sort: {rc}")
     return {"columns": out[0], "coarse_bits": out[1], "fine_bits": out[2], "chunk_cap": out[3], "big_thresh": out[4]}
+
+
+def plan_sort_digit_grid(items, workgroups, block_min=0):
+    """Grid of the sort's digit pass over ``items`` work items on a device that holds ``workgroups`` of its workgroups
+    at once (read-only): workgroup g walks blocks g, g + grid, ... of ``block`` consecutive items."""
+    out = (ctypes.c_size_t * 3)()
+    rc = load_library().amdmsm_plan_sort_digit_grid(ctypes.c_size_t(items), int(block_min), int(workgroups), out)
+    if rc:
+        raise AmdMsmError(f"amdmsm_plan_sort_digit_grid: {rc}")
+    return {"block": out[0], "blocks": out[1], "grid": out[2]}
 
 
 def plan_fold(curve, group, k, n, chunk_points=0, endomorphism=0):
