@@ -485,6 +485,10 @@ def _np_ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+# include/amdmsm.h amdmsm_read_fn: size_t read(void *read_ctx, void *dst, size_t bytes)
+_READ_FN = ctypes.CFUNCTYPE(ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
+
+
 def _records(a, stride_bytes, g_bytes):
     """libff records in the array ``a``, ``stride_bytes`` apart (None: the rows of a packed 2-d array)"""
     if stride_bytes is None:
@@ -527,8 +531,10 @@ class Engine:
 
     def _check(self, rc, what):
         if rc:
-            raise AmdMsmError("%s failed: %s (%s)" % (what, self.lib.amdmsm_strerror(rc).decode(),
+            err = AmdMsmError("%s failed: %s (%s)" % (what, self.lib.amdmsm_strerror(rc).decode(),
                                                       self.lib.amdmsm_last_error(self.h).decode()))
+            err.code = rc   # the AMDMSM_ERR_* value of include/amdmsm.h
+            raise err
 
     def _opts(self, window_bits=0, segment_len=0, out_form=OUT_LIBFF, scalars_plain=False, stream=None):
         # self.endomorphism: amdmsm_opts.endomorphism for every call of this engine (0 = only where the
@@ -788,6 +794,54 @@ class Engine:
             _np_ptr(scalars) if scalars.shape[0] else None, ctypes.c_size_t(scalars.shape[0]),
             ctypes.c_size_t(precompute_c), ctypes.c_size_t(chunk_points), _np_ptr(out), ctypes.byref(o))
         self._check(rc, "amdmsm_multi_exp_stream_with_precompute_file")
+        return out
+
+    def multi_exp_stream(self, curve, group, reader, scalars, *, chunk_points=0, compressed=False, precompute_c=0,
+                         out=None, out_form=OUT_AFFINE, scalars_plain=False):
+        """The reader-callback entries ``amdmsm_multi_exp_stream`` / ``_compressed`` / ``_with_precompute`` (what the
+        C++ shim of include/libff_amd/multiexp_stream.hpp calls): the records of the ``_file`` methods above, pulled
+        through ``reader(nbytes) -> bytes``.  A reader may deliver fewer bytes than asked for (it is asked again for the
+        rest, never for more than the call still needs); ``b""`` is the end of the stream.  ``compressed``: compressed
+        records; ``precompute_c`` > 0: precompute_num_digits(curve, c) multiples per scalar.  ``out``: result record to
+        fill; it is written only when the call succeeds.  An exception raised by ``reader`` ends the stream and is
+        raised again after the call."""
+        assert not (compressed and precompute_c), "the reference has no compressed precompute stream"
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64)
+        s = sizes(curve, group)
+        if out is None:
+            out = np.zeros(s["g_bytes"] // 8, dtype=np.uint64)
+        assert out.dtype == np.uint64 and out.flags.c_contiguous and out.nbytes == s["g_bytes"]
+        raised = []
+
+        def read(_ctx, dst, nbytes):
+            try:
+                piece = bytes(reader(int(nbytes)))
+                assert len(piece) <= nbytes, "reader returned more than it was asked for"
+                ctypes.memmove(dst, piece, len(piece))
+                return len(piece)
+            except BaseException as e:   # an exception cannot cross the C frames: end the stream, raise afterwards
+                raised.append(e)
+                return 0
+
+        cb = _READ_FN(read)   # referenced from this frame for as long as the library may call it
+        o = self._opts(out_form=out_form, scalars_plain=scalars_plain)
+        n = scalars.shape[0]
+        args = (_np_ptr(scalars) if n else None, ctypes.c_size_t(n))
+        tail = (ctypes.c_size_t(chunk_points), _np_ptr(out), ctypes.byref(o))
+        if precompute_c:
+            what = "amdmsm_multi_exp_stream_with_precompute"
+            rc = self.lib.amdmsm_multi_exp_stream_with_precompute(self.h, curve, group, cb, None, *args,
+                                                                  ctypes.c_size_t(precompute_c), *tail)
+        elif compressed:
+            what = "amdmsm_multi_exp_stream_compressed"
+            rc = self.lib.amdmsm_multi_exp_stream_compressed(self.h, curve, group, cb, None, *args, *tail)
+        else:
+            what = "amdmsm_multi_exp_stream"
+            rc = self.lib.amdmsm_multi_exp_stream(self.h, curve, group, cb, None, *args, *tail)
+        del cb
+        if raised:
+            raise raised[0]
+        self._check(rc, what)
         return out
 
     def precompute_table(self, curve, group, bases, c, num_digits=None):

@@ -194,6 +194,24 @@ class Curve:
         assert self.on_curve(P), "result off the curve"
         return P
 
+    def disk_write(self, pts):
+        """libff's on-disk records of the points, group_write<encoding_binary, form_montgomery, compression_off>
+        (curve_serialization.tcc:78-101): affine X then Y, every Fq component (c0 before c1) the Montgomery residue as
+        8 * WORDS big-endian bytes (field_serialization.tcc:125-208); zero is (0, one)"""
+        F = self.F
+        out = bytearray()
+        for P in pts:
+            for v in ((F.zero(), F.c(1)) if P is INF else P):
+                for c in F.comps(v):
+                    out += self.fq_mont(c).to_bytes(8 * WORDS, "big")
+        return bytes(out)
+
+    def scalars_plain(self, ks):
+        out = np.zeros((len(ks), WORDS), dtype=np.uint64)
+        for i, k in enumerate(ks):
+            out[i] = words(k)
+        return out
+
     def scalars_mont(self, ks):
         rr = RADIX % self.r
         out = np.zeros((len(ks), WORDS), dtype=np.uint64)
