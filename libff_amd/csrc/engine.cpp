@@ -155,12 +155,13 @@ struct amdmsm_ctx {
     fb_state fb;
     stream_state ss;
     hipEvent_t aux_ev[5] = {};                    // phases of the last amdmsm_batch_exp
-    // phase marks of the last timed amdmsm_group_fft: the time from a mark to the next belongs to the mark's phase, so the
-    // phases of all stages and chunks add up (grow-only; the ring above holds one set of six events per call)
-    std::vector<hipEvent_t> fft_ev;
-    std::vector<unsigned char> fft_phase;
-    size_t fft_marks = 0;
-    long long fft_ticket = -1;
+    // phase marks of the last timed call between call_begin and call_end (the group FFT, every Fr entry): the time from a
+    // mark to the next belongs to the mark's phase, so the phases of all stages and chunks add up (grow-only; the ring
+    // above holds one set of six events per call)
+    std::vector<hipEvent_t> call_ev;
+    std::vector<unsigned char> call_phase;
+    size_t call_marks = 0;
+    long long call_ticket = -1;
     float aux_ms[4] = {};
     fr_tw_entry fr_tw[2];                         // a prover alternates omega and omega^-1 over one domain
     uint64_t fr_clock = 0;
@@ -537,7 +538,7 @@ int ensure_ws(amdmsm_ctx *ctx, ws_slot &sl, size_t bytes) {
 }
 
 constexpr uint64_t TIMING_RING = 64;
-// The events of `ring`, aux_ev and fft_ev only measure time, so they are created with hipEventDisableSystemFence: a
+// The events of `ring`, aux_ev and call_ev only measure time, so they are created with hipEventDisableSystemFence: a
 // plain event writes the caches back and invalidates them where it is recorded -- six times inside every timed call --
 // and the kernels behind it pay for that (2^20 points: 1.593 -> 1.578 ms per step, profiles/digit_pass_and_step_gaps.txt).
 // The flag is right for them because their only readers are hipEventElapsedTime calls behind an event or stream
@@ -1203,7 +1204,7 @@ void amdmsm_ctx_destroy(amdmsm_ctx *ctx) {
         for (auto &e : ctx->aux_ev) {
             if (e) (void)hipEventDestroy(e);
         }
-        for (auto &e : ctx->fft_ev) (void)hipEventDestroy(e);
+        for (auto &e : ctx->call_ev) (void)hipEventDestroy(e);
         for (auto &t : ctx->fr_tw) {
             if (t.buf.p) (void)hipFree(t.buf.p);
             if (t.ev) (void)hipEventDestroy(t.ev);
@@ -1412,15 +1413,15 @@ int amdmsm_get_timings_by_ticket(amdmsm_ctx *ctx, long long ticket, float ms[AMD
     hipEvent_t *ev = ctx->ring[(uint64_t)ticket % TIMING_RING];
     dev_guard g(ctx->device);
     HIP_TRY(ctx, hipEventSynchronize(ev[5]));
-    if (ticket == ctx->fft_ticket && ctx->fft_marks >= 2) {   // amdmsm_group_fft: phases summed over stages and chunks
-        const size_t last = ctx->fft_marks - 1;
-        HIP_TRY(ctx, hipEventSynchronize(ctx->fft_ev[last]));
+    if (ticket == ctx->call_ticket && ctx->call_marks >= 2) {   // a marked call: phases summed over stages and chunks
+        const size_t last = ctx->call_marks - 1;
+        HIP_TRY(ctx, hipEventSynchronize(ctx->call_ev[last]));
         for (size_t i = 0; i < last; ++i) {
             float d = 0.f;
-            HIP_TRY(ctx, hipEventElapsedTime(&d, ctx->fft_ev[i], ctx->fft_ev[i + 1]));
-            ms[ctx->fft_phase[i]] += d;
+            HIP_TRY(ctx, hipEventElapsedTime(&d, ctx->call_ev[i], ctx->call_ev[i + 1]));
+            ms[ctx->call_phase[i]] += d;
         }
-        HIP_TRY(ctx, hipEventElapsedTime(&ms[AMDMSM_PH_TOTAL], ctx->fft_ev[0], ctx->fft_ev[last]));
+        HIP_TRY(ctx, hipEventElapsedTime(&ms[AMDMSM_PH_TOTAL], ctx->call_ev[0], ctx->call_ev[last]));
         return AMDMSM_OK;
     }
     for (int i = 0; i < 5; ++i) HIP_TRY(ctx, hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
@@ -3317,7 +3318,7 @@ namespace {
 // butterfly, smv_table's 2 * smv_entries records and the gathered B operand the table is built from: that part is what
 // vec_chunk_points is given, a chunk being at most the n / 2 butterflies of a stage.
 constexpr size_t FFT_MAX_N = (size_t)1 << 28;
-constexpr size_t FFT_MAX_MARKS = (size_t)1 << 16;
+constexpr size_t CALL_MAX_MARKS = (size_t)1 << 16;
 struct fft_plan {
     int stages;
     size_t cn, chunk_bytes, off_a, off_b, off_xyz, off_chunk, ws_bytes;
@@ -3337,18 +3338,18 @@ fft_plan fft_make_plan(const group_vtable *vt, size_t n, size_t chunk_points) {
     return p;
 }
 
-// phase mark of a timed call (amdmsm_ctx::fft_ev)
-void fft_mark(amdmsm_ctx *ctx, hipStream_t st, int phase, bool last = false) {
+// phase mark of a timed call (amdmsm_ctx::call_ev)
+void call_mark(amdmsm_ctx *ctx, hipStream_t st, int phase, bool last = false) {
     if (!ctx->timing) return;
-    if (ctx->fft_marks >= FFT_MAX_MARKS && !last) return;   // the time stays with the phase of the mark before
-    if (ctx->fft_marks == ctx->fft_ev.size()) {
+    if (ctx->call_marks >= CALL_MAX_MARKS && !last) return;   // the time stays with the phase of the mark before
+    if (ctx->call_marks == ctx->call_ev.size()) {
         hipEvent_t e = nullptr;
         if (timing_event(&e) != hipSuccess) return;
-        ctx->fft_ev.push_back(e);
-        ctx->fft_phase.push_back(0);
+        ctx->call_ev.push_back(e);
+        ctx->call_phase.push_back(0);
     }
-    (void)hipEventRecord(ctx->fft_ev[ctx->fft_marks], st);
-    ctx->fft_phase[ctx->fft_marks++] = (unsigned char)phase;
+    (void)hipEventRecord(ctx->call_ev[ctx->call_marks], st);
+    ctx->call_phase[ctx->call_marks++] = (unsigned char)phase;
 }
 
 // the argument rules all entries share; nothing is launched or written before they hold
@@ -3371,7 +3372,7 @@ int fft_stages(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, const ff
     uint32_t *table = gathered + p.cn * (size_t)vt->el_words * 2, *tmp = table + smv_table_bytes(vt, p.cn) / 4;
     const size_t xyz_words = (size_t)vt->el_words * 3, half = n / 2;
     if (n == 1) {   // the point itself, in special form -- which is a libff record too
-        fft_mark(ctx, st, 3);
+        call_mark(ctx, st, 3);
         vt->export_affine(st, d_in, 1, d_out);
         HIP_TRY(ctx, hipGetLastError());
         return AMDMSM_OK;
@@ -3385,17 +3386,17 @@ int fft_stages(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, const ff
         for (size_t b0 = 0; b0 < half; b0 += p.cn) {
             const size_t m = half - b0 < p.cn ? half - b0 : p.cn;
             if (t == 0) {   // every twiddle is 1
-                fft_mark(ctx, st, 2);
+                call_mark(ctx, st, 2);
                 vt->fft_butterfly(st, nullptr, m, cur, b0, rsh, d_tw, vo.mont, half, dst);
             } else {
-                fft_mark(ctx, st, 1);
+                call_mark(ctx, st, 1);
                 vt->fft_gather(st, cur, b0, m, rsh, gathered);
                 vt->smv_table(st, gathered, m, tmp, table);
-                fft_mark(ctx, st, 2);
+                call_mark(ctx, st, 2);
                 vt->fft_butterfly(st, table, m, cur, b0, rsh, d_tw, vo.mont, half, dst);
             }
         }
-        fft_mark(ctx, st, 3);
+        call_mark(ctx, st, 3);
         if (!last) {
             vt->import_bases(st, dst, xyz_words, 0, n, next);
             cur = next;
@@ -3407,19 +3408,20 @@ int fft_stages(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, const ff
     return AMDMSM_OK;
 }
 
-// the slot and the first mark of a call whose phases are marked (group_fft, fr_fft); the last mark and the end of the call
-int fft_begin(amdmsm_ctx *ctx, hipStream_t st, size_t ws_bytes, ws_slot *&sl) {
+// the slot and the first mark of a call whose phases are marked (group_fft, the Fr entries); the last mark and the end of
+// the call
+int call_begin(amdmsm_ctx *ctx, hipStream_t st, size_t ws_bytes, ws_slot *&sl) {
     const int rc = slot_begin(ctx, st, ws_bytes, sl);
     if (rc) return rc;
-    ctx->fft_marks = 0;
-    ctx->fft_ticket = -1;
+    ctx->call_marks = 0;
+    ctx->call_ticket = -1;
     record(ctx, *sl, 0, st);
-    fft_mark(ctx, st, 0);
+    call_mark(ctx, st, 0);
     return AMDMSM_OK;
 }
-int fft_end(amdmsm_ctx *ctx, hipStream_t st, ws_slot &sl, int last_phase = 3) {
-    fft_mark(ctx, st, last_phase, true);
-    if (ctx->timing) ctx->fft_ticket = (long long)ctx->ticket;   // the ticket slot_end hands out
+int call_end(amdmsm_ctx *ctx, hipStream_t st, ws_slot &sl, int last_phase = 3) {
+    call_mark(ctx, st, last_phase, true);
+    if (ctx->timing) ctx->call_ticket = (long long)ctx->ticket;   // the ticket slot_end hands out
     return slot_end(ctx, st, sl);
 }
 
@@ -3460,12 +3462,12 @@ int amdmsm_group_fft_device(amdmsm_ctx *ctx, int curve, int group, const void *d
     hipStream_t st = stream_of(ctx, opts);
     const fft_plan p = fft_make_plan(vt, n, chunk_points);
     ws_slot *sl = nullptr;
-    rc = fft_begin(ctx, st, p.ws_bytes, sl);
+    rc = call_begin(ctx, st, p.ws_bytes, sl);
     if (rc) return rc;
     rc = fft_stages(ctx, vt, st, p, (const uint32_t *)d_points_affine, (const uint32_t *)d_twiddles, n, (uint32_t *)d_out_xyz,
                     vec_opts_of(opts), (char *)sl->ws);
     if (rc) return rc;
-    return fft_end(ctx, st, *sl);
+    return call_end(ctx, st, *sl);
 }
 
 int amdmsm_group_fft(amdmsm_ctx *ctx, int curve, int group, const void *points_xyz, size_t stride_bytes, int base_form, size_t n,
@@ -3485,7 +3487,7 @@ int amdmsm_group_fft(amdmsm_ctx *ctx, int curve, int group, const void *points_x
     rc = ensure_buf(ctx, ctx->hb_src, piece * stride_bytes);
     if (rc == AMDMSM_OK && n > 2) rc = ensure_buf(ctx, ctx->hb_sc, n / 2 * fr_bytes);
     ws_slot *sl = nullptr;
-    if (rc == AMDMSM_OK) rc = fft_begin(ctx, st, p.ws_bytes, sl);
+    if (rc == AMDMSM_OK) rc = call_begin(ctx, st, p.ws_bytes, sl);
     if (rc) return rc;
     char *ws = (char *)sl->ws;
     uint32_t *d_in = (uint32_t *)(ws + p.off_a), *d_res = (uint32_t *)(ws + p.off_xyz);
@@ -3503,7 +3505,7 @@ int amdmsm_group_fft(amdmsm_ctx *ctx, int curve, int group, const void *points_x
         return rc;
     }
     HIP_TRY(ctx, hipMemcpyAsync(out_xyz, d_res, n * xyz_bytes, hipMemcpyDeviceToHost, st));
-    rc = fft_end(ctx, st, *sl);
+    rc = call_end(ctx, st, *sl);
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return rc;
 }
@@ -3845,6 +3847,29 @@ fr_rec fr_read(const fr_vtable *f, const void *rec, bool plain) {
     const fr_rec r = fr_from_words(f, (const uint32_t *)rec);
     return plain ? fr_mul(f, r, fr_from_words(f, f->r2)) : r;
 }
+fr_rec fr_small(uint32_t k) {
+    fr_rec r;
+    r.v[0] = k;
+    return r;
+}
+// out of Montgomery form: the product with the integer 1
+fr_rec fr_from_mont(const fr_vtable *f, const fr_rec &x) { return fr_mul(f, x, fr_small(1)); }
+// r - x word by word, x <= r: r - 1 in either form (x = 1, x = R mod r), the Fermat exponent r - 2
+fr_rec fr_r_minus(const fr_vtable *f, const fr_rec &x) {
+    fr_rec d;
+    uint64_t borrow = 0;
+    for (int j = 0; j < f->words; ++j) {
+        const uint64_t w = (uint64_t)f->modulus[j] - x.v[j] - borrow;
+        d.v[j] = (uint32_t)w;
+        borrow = (w >> 63) & 1u;
+    }
+    return d;
+}
+// an environment switch: set, not empty and not "0"
+bool env_flag(const char *name) {
+    const char *e = getenv(name);
+    return e && *e && strcmp(e, "0") != 0;
+}
 // base^(2^(shift + b)), b < FR_POW_TABLE, packed records of the field's width: what fr_vtable::powers takes for the
 // powers of base^(2^shift)
 std::vector<uint32_t> fr_pow_table(const fr_vtable *f, fr_rec x, int shift) {
@@ -3914,13 +3939,8 @@ int frfft_check(amdmsm_ctx *ctx, const fr_vtable *f, const void *values, size_t 
     pr.plain = opts && opts->scalars_plain;
     if (n > 1) {
         pr.omega = fr_read(f, omega, pr.plain);
-        fr_rec x = pr.omega, minus_one;   // -1 as a Montgomery residue: r - R
-        uint64_t borrow = 0;
-        for (int j = 0; j < f->words; ++j) {
-            const uint64_t d = (uint64_t)f->modulus[j] - f->one[j] - borrow;
-            minus_one.v[j] = (uint32_t)d;
-            borrow = (d >> 63) & 1u;
-        }
+        fr_rec x = pr.omega;
+        const fr_rec minus_one = fr_r_minus(f, fr_from_words(f, f->one));   // -1 as a Montgomery residue: r - R
         for (int b = 0; b + 1 < plan.log_n; ++b) x = fr_mul(f, x, x);
         if (!fr_same(f, x, minus_one))
             return fail(ctx, AMDMSM_ERR_BAD_ARG, "omega is not a primitive n-th root of unity: omega^(n/2) != r - 1 (n = 2^" +
@@ -3981,7 +4001,7 @@ int frfft_run(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, const frfft_p
         f->powers(st, fr_pow_table(f, pr.post, p.log_n - p.t_last).data(), pr.scale.v, 0, (size_t)1 << p.t_last, post_row);
     }
     HIP_TRY(ctx, hipGetLastError());
-    fft_mark(ctx, st, 1);
+    call_mark(ctx, st, 1);
     // pass k of P reads what pass k - 1 wrote; the last one writes d_out, and no pass reads and writes one vector --
     // except a lone pass, which is one workgroup that loads everything before it stores anything
     uint32_t *w1 = (uint32_t *)ws, *w2 = (uint32_t *)(ws + p.off_w2);
@@ -4017,16 +4037,65 @@ int frfft_run(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, const frfft_p
     return AMDMSM_OK;
 }
 
-// device vectors are moved 16 bytes at a time, 8 for the 10-word fields (fp_load / fp_store)
-bool fr_misaligned(const fr_vtable *f, std::initializer_list<const void *> ptrs) {
-    const uintptr_t mask = f->words % 4 ? 7 : 15;
+// ---- the rules for vectors in device memory, for every Fr entry that takes one.  An absent vector (null) keeps them all.
+// Device vectors are moved 16 bytes at a time, 8 for the 10-word fields (fp_load / fp_store); align: another unit than
+// the field's (a counter).  what: the operands, as the message names them.
+int fr_check_aligned(amdmsm_ctx *ctx, const fr_vtable *f, const char *what, std::initializer_list<const void *> ptrs, size_t align = 0) {
+    if (!align) align = f->words % 4 ? 8 : 16;
     for (const void *p : ptrs)
-        if ((uintptr_t)p & mask) return true;
-    return false;
+        if ((uintptr_t)p & (align - 1))
+            return fail(ctx, AMDMSM_ERR_BAD_ARG, std::string(what) + ": not aligned to " + std::to_string(align) + " bytes");
+    return AMDMSM_OK;
 }
-bool ranges_overlap(const void *a, const void *b, size_t bytes) {
+bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + bytes && y < x + bytes;
+    return a && b && a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
+}
+// two vectors that share bytes; same_ok: unless they are one vector (a kernel that reads record i before it writes it)
+int fr_check_apart(amdmsm_ctx *ctx, const char *na, const void *a, size_t a_bytes, const char *nb, const void *b, size_t b_bytes,
+                   bool same_ok = true) {
+    if ((same_ok && a == b) || !ranges_overlap(a, a_bytes, b, b_bytes)) return AMDMSM_OK;
+    return fail(ctx, AMDMSM_ERR_BAD_ARG, std::string(na) + " and " + nb + " overlap" + (same_ok ? " without being the same vector" : ""));
+}
+// a small result (a total, a counter) that lies inside one of the vectors of `bytes` each
+int fr_check_outside(amdmsm_ctx *ctx, const char *what, const void *small, size_t small_bytes, std::initializer_list<const void *> vecs,
+                     size_t bytes) {
+    for (const void *v : vecs)
+        if (ranges_overlap(small, small_bytes, v, bytes)) return fail(ctx, AMDMSM_ERR_BAD_ARG, std::string(what) + " lies inside a vector");
+    return AMDMSM_OK;
+}
+
+// ---- the skeleton of a call on Fr vectors.  A device entry stages nothing: staged = 0, no copies; it takes a
+// slot of ws_bytes, runs and ends with phase 1 as its last.  A host entry's vectors lie in the first `staged` bytes of the
+// slot, each at the 256-byte-aligned offset its fr_copy names, in front of the same workspace: `up` goes up, run(staged
+// vectors, workspace) enqueues the kernels on them, mark 2, `down` comes down, and the stream is drained -- so the caller's
+// memory is touched by nothing once the call has returned.  A copy whose host pointer is null or that has no bytes is
+// left out.  run places mark 1 itself (the FFT's comes behind its power tables).
+struct fr_copy {
+    const void *host;
+    size_t off, bytes;
+};
+template <class Run>
+int fr_call(amdmsm_ctx *ctx, hipStream_t st, size_t staged, size_t ws_bytes, std::initializer_list<fr_copy> up,
+            std::initializer_list<fr_copy> down, Run run) {
+    ws_slot *sl = nullptr;
+    int rc = call_begin(ctx, st, staged + ws_bytes, sl);
+    if (rc) return rc;
+    char *base = (char *)sl->ws;
+    for (const fr_copy &c : up)
+        if (c.host && c.bytes) HIP_TRY(ctx, hipMemcpyAsync(base + c.off, c.host, c.bytes, hipMemcpyHostToDevice, st));
+    rc = run(base, base + staged);
+    if (!staged) return rc ? rc : call_end(ctx, st, *sl, 1);
+    if (rc) {
+        (void)hipDeviceSynchronize();   // nothing of this call may still read the caller's vectors
+        return rc;
+    }
+    call_mark(ctx, st, 2);
+    for (const fr_copy &c : down)
+        if (c.host && c.bytes) HIP_TRY(ctx, hipMemcpyAsync((void *)c.host, base + c.off, c.bytes, hipMemcpyDeviceToHost, st));
+    rc = call_end(ctx, st, *sl, 2);
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return rc;
 }
 
 #define FR_ENTER(ctx)                                                 \
@@ -4060,10 +4129,7 @@ int amdmsm_fr_root_of_unity(int curve, int log2_n, void *r_plain_out) {
     if (!r_plain_out || log2_n < 0 || log2_n > f->two_adicity) return AMDMSM_ERR_BAD_ARG;
     fr_rec x = fr_from_words(f, f->root);
     for (int b = f->two_adicity; b > log2_n; --b) x = fr_mul(f, x, x);
-    fr_rec one;
-    one.v[0] = 1;
-    x = fr_mul(f, x, one);   // out of Montgomery form
-    memcpy(r_plain_out, x.v, (size_t)f->words * 4);
+    memcpy(r_plain_out, fr_from_mont(f, x).v, (size_t)f->words * 4);
     return AMDMSM_OK;
 }
 
@@ -4076,19 +4142,15 @@ int amdmsm_fr_fft_device(amdmsm_ctx *ctx, int curve, const void *d_values, size_
     frfft_params pr;
     int rc = frfft_check(ctx, f, d_values, n, omega, pre, post, scale, tile_log2, opts, d_out, p, pr);
     if (rc) return rc;
-    if (n && fr_misaligned(f, {d_values, d_out}))
-        return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_values / d_out: not aligned to " + std::to_string(f->words % 4 ? 8 : 16) + " bytes");
-    if (n && d_values != d_out && ranges_overlap(d_values, d_out, n * p.rec))
-        return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_values and d_out overlap without being the same vector");
+    if (n) rc = fr_check_aligned(ctx, f, "d_values / d_out", {d_values, d_out});
+    if (!rc) rc = fr_check_apart(ctx, "d_values", d_values, n * p.rec, "d_out", d_out, n * p.rec);
+    if (rc) return rc;
     FR_ENTER(ctx);
     if (!n) return AMDMSM_OK;
     hipStream_t st = stream_of(ctx, opts);
-    ws_slot *sl = nullptr;
-    rc = fft_begin(ctx, st, frfft_ws_bytes(p, d_values == d_out), sl);
-    if (rc) return rc;
-    rc = frfft_run(ctx, f, st, p, pr, (const uint32_t *)d_values, (uint32_t *)d_out, n, (char *)sl->ws);
-    if (rc) return rc;
-    return fft_end(ctx, st, *sl, 1);
+    return fr_call(ctx, st, 0, frfft_ws_bytes(p, d_values == d_out), {}, {}, [&](char *, char *ws) {
+        return frfft_run(ctx, f, st, p, pr, (const uint32_t *)d_values, (uint32_t *)d_out, n, ws);
+    });
 }
 
 int amdmsm_fr_fft(amdmsm_ctx *ctx, int curve, const void *values, size_t n, const void *omega, const void *pre, const void *post,
@@ -4103,22 +4165,10 @@ int amdmsm_fr_fft(amdmsm_ctx *ctx, int curve, const void *values, size_t n, cons
     FR_ENTER(ctx);
     if (!n) return AMDMSM_OK;
     hipStream_t st = ctx->stream;
-    ws_slot *sl = nullptr;
-    // the uploaded vector in front of the device entry's workspace; the transform runs in place on it
-    rc = fft_begin(ctx, st, p.vec + frfft_ws_bytes(p, true), sl);
-    if (rc) return rc;
-    uint32_t *d_vec = (uint32_t *)sl->ws;
-    HIP_TRY(ctx, hipMemcpyAsync(d_vec, values, n * p.rec, hipMemcpyHostToDevice, st));
-    rc = frfft_run(ctx, f, st, p, pr, d_vec, d_vec, n, (char *)sl->ws + p.vec);
-    if (rc) {
-        (void)hipDeviceSynchronize();   // nothing of this call may still read the caller's vector
-        return rc;
-    }
-    fft_mark(ctx, st, 2);
-    HIP_TRY(ctx, hipMemcpyAsync(out, d_vec, n * p.rec, hipMemcpyDeviceToHost, st));
-    rc = fft_end(ctx, st, *sl, 2);
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return rc;
+    // one staged vector; the transform runs in place on it
+    return fr_call(ctx, st, p.vec, frfft_ws_bytes(p, true), {{values, 0, n * p.rec}}, {{out, 0, n * p.rec}}, [&](char *vec, char *ws) {
+        return frfft_run(ctx, f, st, p, pr, (const uint32_t *)vec, (uint32_t *)vec, n, ws);
+    });
 }
 
 int amdmsm_fr_powers_device(amdmsm_ctx *ctx, int curve, const void *base, size_t n, const amdmsm_opts *opts, void *d_out) {
@@ -4127,7 +4177,7 @@ int amdmsm_fr_powers_device(amdmsm_ctx *ctx, int curve, const void *base, size_t
     CHECK_OPTS(ctx, opts);
     if (n && (!base || !d_out)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null pointer");
     if (n > ((size_t)1 << 32)) return fail(ctx, AMDMSM_ERR_TOO_LARGE, "n = " + std::to_string(n) + ": at most 2^32 records");
-    if (n && fr_misaligned(f, {d_out})) return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_out: misaligned");
+    if (n && fr_check_aligned(ctx, f, "d_out", {d_out})) return AMDMSM_ERR_BAD_ARG;
     FR_ENTER(ctx);
     if (!n) return AMDMSM_OK;
     const bool plain = opts && opts->scalars_plain;
@@ -4142,7 +4192,7 @@ int amdmsm_fr_muladd_device(amdmsm_ctx *ctx, int curve, size_t n, const void *d_
     if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
     CHECK_OPTS(ctx, opts);
     if (n && (!d_a || !d_b || !d_out)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null pointer");
-    if (n && fr_misaligned(f, {d_a, d_b, d_c, d_out})) return fail(ctx, AMDMSM_ERR_BAD_ARG, "a device vector is misaligned");
+    if (n && fr_check_aligned(ctx, f, "d_a / d_b / d_c / d_out", {d_a, d_b, d_c, d_out})) return AMDMSM_ERR_BAD_ARG;
     FR_ENTER(ctx);
     if (!n) return AMDMSM_OK;
     const bool plain = opts && opts->scalars_plain;
@@ -4163,10 +4213,7 @@ uint32_t frm_env(const char *name) {
     const char *e = getenv(name);
     return e ? (uint32_t)strtoul(e, nullptr, 10) : 0u;
 }
-bool frm_naive_env() {
-    const char *e = getenv("AMDMSM_FR_MATRIX_NAIVE");
-    return e && *e && strcmp(e, "0") != 0;
-}
+bool frm_naive_env() { return env_flag("AMDMSM_FR_MATRIX_NAIVE"); }
 
 bool fr_below_modulus(const fr_vtable *f, const uint32_t *w) {
     for (int j = f->words - 1; j >= 0; --j)
@@ -4181,18 +4228,8 @@ int frm_prepare(amdmsm_ctx *ctx, const fr_vtable *f, size_t n_rows, size_t n_col
     const int bad = frm_validate(n_rows, n_cols, offsets, cols, coeffs != nullptr, err);
     if (bad) return fail(ctx, bad == 2 ? AMDMSM_ERR_TOO_LARGE : AMDMSM_ERR_BAD_ARG, err);
     // 1 and r - 1 in the form the coefficients come in
-    const int N = f->words;
-    fr_rec one, minus_one;
-    if (coeffs_plain) one.v[0] = 1;
-    else one = fr_from_words(f, f->one);
-    uint64_t borrow = 0;
-    for (int j = 0; j < N; ++j) {
-        const uint64_t d = (uint64_t)f->modulus[j] - one.v[j] - borrow;
-        minus_one.v[j] = (uint32_t)d;
-        borrow = (d >> 63) & 1u;
-    }
-    const fr_rec zero;
-    const size_t rec = (size_t)N * 4;
+    const fr_rec one = coeffs_plain ? fr_small(1) : fr_from_words(f, f->one), minus_one = fr_r_minus(f, one), zero;
+    const size_t rec = (size_t)f->words * 4;
     uint64_t bad_entry = 0;
     const auto cls_of = [&](uint64_t k) -> uint32_t {
         uint32_t w[FR_MAX_WORDS];
@@ -4252,20 +4289,20 @@ int frm_check_apply(amdmsm_ctx *ctx, uint64_t mat, const void *x, size_t n_x, co
         return fail(ctx, AMDMSM_ERR_TOO_LARGE, "n_x / n_out: at most 2^28 records");
     if (n_out && !out) return fail(ctx, AMDMSM_ERR_BAD_ARG, "output: null pointer");
     if (m->kept && !x) return fail(ctx, AMDMSM_ERR_BAD_ARG, "x: null pointer");
-    if (device) {
-        if (fr_misaligned(f, {x, out}))
-            return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_x / d_out: not aligned to " + std::to_string(f->words % 4 ? 8 : 16) + " bytes");
-        const size_t rec = (size_t)f->words * 4;
-        const uintptr_t a = (uintptr_t)x, b = (uintptr_t)out;
-        if (x && out && n_x && n_out && a < b + n_out * rec && b < a + n_x * rec)
-            return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_x and d_out overlap");
-    }
-    return AMDMSM_OK;
+    if (!device) return AMDMSM_OK;
+    const size_t rec = (size_t)f->words * 4;
+    const int rc = fr_check_aligned(ctx, f, "d_x / d_out", {x, out});
+    // stricter than the other entries: a row reads any column, so d_x == d_out is refused too
+    return rc ? rc : fr_check_apart(ctx, "d_x", x, n_x * rec, "d_out", out, n_out * rec, false);
 }
 
-// the kernels of one apply on device vectors; partial: room for n_partials records
+// the workspace of an apply: the partial sums
+size_t frm_ws_bytes(const fr_vtable *f, const fr_matrix *m) { return align_up(((size_t)m->n_partials + 1) * f->words * 4, 256); }
+
+// the kernels of one apply on device vectors, behind mark 1; partial: room for n_partials records
 int frm_run(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, fr_matrix *m, const uint32_t *d_x, uint32_t *d_out, size_t n_out,
             uint32_t *partial) {
+    call_mark(ctx, st, 1);
     if (m->naive) {
         f->matrix_naive(st, m->n_rows, n_out, (const uint64_t *)m->offsets, (const uint32_t *)m->cols, (const uint32_t *)m->coef, d_x,
                         d_out);
@@ -4406,13 +4443,9 @@ int amdmsm_fr_matrix_apply_device(amdmsm_ctx *ctx, uint64_t mat, const void *d_x
     if (rc) return rc;
     if (!n_out) return AMDMSM_OK;
     hipStream_t st = stream_of(ctx, opts);
-    ws_slot *sl = nullptr;
-    rc = fft_begin(ctx, st, align_up(((size_t)m->n_partials + 1) * f->words * 4, 256), sl);
-    if (rc) return rc;
-    fft_mark(ctx, st, 1);
-    rc = frm_run(ctx, f, st, m, (const uint32_t *)d_x, (uint32_t *)d_out, n_out, (uint32_t *)sl->ws);
-    if (rc) return rc;
-    return fft_end(ctx, st, *sl, 1);
+    return fr_call(ctx, st, 0, frm_ws_bytes(f, m), {}, {}, [&](char *, char *ws) {
+        return frm_run(ctx, f, st, m, (const uint32_t *)d_x, (uint32_t *)d_out, n_out, (uint32_t *)ws);
+    });
 }
 
 int amdmsm_fr_matrix_apply(amdmsm_ctx *ctx, uint64_t mat, const void *x, size_t n_x, void *out, size_t n_out,
@@ -4426,24 +4459,12 @@ int amdmsm_fr_matrix_apply(amdmsm_ctx *ctx, uint64_t mat, const void *x, size_t 
     if (!n_out) return AMDMSM_OK;
     hipStream_t st = ctx->stream;
     const size_t rec = (size_t)f->words * 4;
-    // the uploaded vector, the result and the partial sums, in that order
+    // staged: the vector and the result, in that order
     const size_t x_bytes = align_up((n_x ? n_x : 1) * rec, 256), out_bytes = align_up(n_out * rec, 256);
-    ws_slot *sl = nullptr;
-    rc = fft_begin(ctx, st, x_bytes + out_bytes + align_up(((size_t)m->n_partials + 1) * rec, 256), sl);
-    if (rc) return rc;
-    uint32_t *d_x = (uint32_t *)sl->ws, *d_out = (uint32_t *)((char *)sl->ws + x_bytes);
-    if (n_x && x) HIP_TRY(ctx, hipMemcpyAsync(d_x, x, n_x * rec, hipMemcpyHostToDevice, st));
-    fft_mark(ctx, st, 1);
-    rc = frm_run(ctx, f, st, m, d_x, d_out, n_out, (uint32_t *)((char *)sl->ws + x_bytes + out_bytes));
-    if (rc) {
-        (void)hipDeviceSynchronize();   // nothing of this call may still read the caller's vector
-        return rc;
-    }
-    fft_mark(ctx, st, 2);
-    HIP_TRY(ctx, hipMemcpyAsync(out, d_out, n_out * rec, hipMemcpyDeviceToHost, st));
-    rc = fft_end(ctx, st, *sl, 2);
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return rc;
+    return fr_call(ctx, st, x_bytes + out_bytes, frm_ws_bytes(f, m), {{x, 0, n_x * rec}}, {{out, x_bytes, n_out * rec}},
+                   [&](char *vecs, char *ws) {
+                       return frm_run(ctx, f, st, m, (const uint32_t *)vecs, (uint32_t *)(vecs + x_bytes), n_out, (uint32_t *)ws);
+                   });
 }
 
 }  // extern "C"
@@ -4454,24 +4475,15 @@ namespace {
 constexpr int FRS_KIND_MASK = AMDMSM_SCAN_KIND_A | AMDMSM_SCAN_KIND_B | AMDMSM_SCAN_KIND_INVERT;
 constexpr int FRS_FLAG_MASK = AMDMSM_SCAN_REVERSE | AMDMSM_SCAN_EXCLUSIVE;
 
-bool frs_naive_env() {
-    const char *e = getenv("AMDMSM_FR_SCAN_NAIVE");
-    return e && *e && strcmp(e, "0") != 0;
-}
+bool frs_naive_env() { return env_flag("AMDMSM_FR_SCAN_NAIVE"); }
 
 // x^(r - 2) for a Montgomery residue x: one Fermat power, r - 2 scanned from its top bit
 fr_rec fr_inv_host(const fr_vtable *f, const fr_rec &x) {
-    uint32_t e[FR_MAX_WORDS];
-    uint64_t borrow = 2;
-    for (int j = 0; j < f->words; ++j) {
-        const uint64_t d = (uint64_t)f->modulus[j] - borrow;
-        e[j] = (uint32_t)d;
-        borrow = (d >> 63) & 1u;
-    }
+    const fr_rec e = fr_r_minus(f, fr_small(2));
     fr_rec acc = fr_from_words(f, f->one);
     for (int i = f->words * 32 - 1; i >= 0; --i) {
         acc = fr_mul(f, acc, acc);
-        if ((e[i >> 5] >> (i & 31)) & 1u) acc = fr_mul(f, acc, x);
+        if ((e.v[i >> 5] >> (i & 31)) & 1u) acc = fr_mul(f, acc, x);
     }
     return acc;
 }
@@ -4509,24 +4521,17 @@ int frs_check(amdmsm_ctx *ctx, const fr_vtable *f, size_t n, const void *vec_a, 
         if (!out) return fail(ctx, AMDMSM_ERR_BAD_ARG, std::string(no) + ": null pointer");
     }
     if (device) {
-        const std::string to = std::to_string(f->words % 4 ? 8 : 16) + " bytes";
-        if (n && fr_misaligned(f, {vec_a})) return fail(ctx, AMDMSM_ERR_BAD_ARG, std::string("d_") + na + ": not aligned to " + to);
-        if (n && fr_misaligned(f, {vec_b})) return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_b: not aligned to " + to);
-        if (n && fr_misaligned(f, {out})) return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_out: not aligned to " + to);
-        if (invert ? ((uintptr_t)total & 7) != 0 : fr_misaligned(f, {total}))
-            return fail(ctx, AMDMSM_ERR_BAD_ARG, invert ? "d_zero_count: not aligned to 8 bytes" : "d_total: not aligned to " + to);
+        const char *da = invert ? "d_values" : "d_a", *dt = invert ? "d_zero_count" : "d_total";
         const size_t bytes = n * c.rec;
-        if (n && vec_a && vec_a != out && ranges_overlap(vec_a, out, bytes))
-            return fail(ctx, AMDMSM_ERR_BAD_ARG, std::string("d_") + na + " and d_out overlap without being the same vector");
-        if (n && vec_b && vec_b != out && ranges_overlap(vec_b, out, bytes))
-            return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_b and d_out overlap without being the same vector");
-        if (n && total) {
-            const size_t tb = invert ? 8 : c.rec;
-            const uintptr_t t = (uintptr_t)total;
-            for (const void *v : {vec_a, vec_b, out})
-                if (v && t < (uintptr_t)v + bytes && (uintptr_t)v < t + tb)
-                    return fail(ctx, AMDMSM_ERR_BAD_ARG, invert ? "d_zero_count lies inside a vector" : "d_total lies inside a vector");
-        }
+        int rc = AMDMSM_OK;
+        if (n) rc = fr_check_aligned(ctx, f, da, {vec_a});
+        if (n && !rc) rc = fr_check_aligned(ctx, f, "d_b", {vec_b});
+        if (n && !rc) rc = fr_check_aligned(ctx, f, "d_out", {out});
+        if (!rc) rc = fr_check_aligned(ctx, f, dt, {total}, invert ? 8 : 0);
+        if (!rc) rc = fr_check_apart(ctx, da, vec_a, bytes, "d_out", out, bytes);
+        if (!rc) rc = fr_check_apart(ctx, "d_b", vec_b, bytes, "d_out", out, bytes);
+        if (!rc) rc = fr_check_outside(ctx, dt, total, invert ? 8 : c.rec, {vec_a, vec_b, out}, bytes);
+        if (rc) return rc;
     }
     if (!frs_make_layout(n, tile_log2, c.rec, invert, c.naive, c.L))
         return fail(ctx, AMDMSM_ERR_BAD_ARG, "tile_log2 = " + std::to_string(tile_log2) + ": 0 or " + std::to_string(FRS_TILE_MIN) +
@@ -4539,9 +4544,10 @@ int frs_check(amdmsm_ctx *ctx, const fr_vtable *f, size_t n, const void *vec_a, 
     return AMDMSM_OK;
 }
 
-// the launches of one call on device vectors; ws: the layout's workspace
+// the launches of one call on device vectors, behind mark 1; ws: the layout's workspace
 int frs_run(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, const frs_call &c, size_t n, const void *d_a, const void *d_b,
             void *d_out, void *d_total, char *ws) {
+    call_mark(ctx, st, 1);
     frs_args a = {};
     a.a = (const uint32_t *)d_a;
     a.b = (const uint32_t *)d_b;
@@ -4580,13 +4586,8 @@ int frs_device_entry(amdmsm_ctx *ctx, int curve, size_t n, const void *d_a, cons
     FR_ENTER(ctx);
     if (!n && !d_total) return AMDMSM_OK;
     hipStream_t st = stream_of(ctx, opts);
-    ws_slot *sl = nullptr;
-    rc = fft_begin(ctx, st, c.L.ws_bytes, sl);
-    if (rc) return rc;
-    fft_mark(ctx, st, 1);
-    rc = frs_run(ctx, f, st, c, n, d_a, d_b, d_out, d_total, (char *)sl->ws);
-    if (rc) return rc;
-    return fft_end(ctx, st, *sl, 1);
+    return fr_call(ctx, st, 0, c.L.ws_bytes, {}, {},
+                   [&](char *, char *ws) { return frs_run(ctx, f, st, c, n, d_a, d_b, d_out, d_total, ws); });
 }
 
 int frs_host_entry(amdmsm_ctx *ctx, int curve, size_t n, const void *a, const void *a_const, const void *b, const void *init,
@@ -4600,29 +4601,14 @@ int frs_host_entry(amdmsm_ctx *ctx, int curve, size_t n, const void *a, const vo
     FR_ENTER(ctx);
     if (!n && !total) return AMDMSM_OK;
     hipStream_t st = ctx->stream;
-    // the uploaded vectors, the total (or the zero count) and the kernels' workspace, in that order; the result takes
-    // the place of the first vector
-    const size_t vec = align_up((n ? n : 1) * c.rec, 256);
-    ws_slot *sl = nullptr;
-    rc = fft_begin(ctx, st, 2 * vec + 256 + c.L.ws_bytes, sl);
-    if (rc) return rc;
-    char *base = (char *)sl->ws;
-    void *d_a = a ? base : nullptr, *d_b = b ? base + vec : nullptr, *d_out = a ? base : base + vec;
-    void *d_total = total ? base + 2 * vec : nullptr;
-    if (n && a) HIP_TRY(ctx, hipMemcpyAsync(d_a, a, n * c.rec, hipMemcpyHostToDevice, st));
-    if (n && b) HIP_TRY(ctx, hipMemcpyAsync(d_b, b, n * c.rec, hipMemcpyHostToDevice, st));
-    fft_mark(ctx, st, 1);
-    rc = frs_run(ctx, f, st, c, n, d_a, d_b, d_out, d_total, base + 2 * vec + 256);
-    if (rc) {
-        (void)hipDeviceSynchronize();   // nothing of this call may still read the caller's vectors
-        return rc;
-    }
-    fft_mark(ctx, st, 2);
-    if (n) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, n * c.rec, hipMemcpyDeviceToHost, st));
-    if (total) HIP_TRY(ctx, hipMemcpyAsync(total, d_total, invert ? 8 : c.rec, hipMemcpyDeviceToHost, st));
-    rc = fft_end(ctx, st, *sl, 2);
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return rc;
+    // staged: the two vectors and the total (or the zero count), in that order; the result takes the place of the first
+    // vector that is given
+    const size_t vec = align_up((n ? n : 1) * c.rec, 256), bytes = n * c.rec, off_out = a ? 0 : vec, off_total = 2 * vec;
+    return fr_call(ctx, st, 2 * vec + 256, c.L.ws_bytes, {{a, 0, bytes}, {b, vec, bytes}},
+                   {{out, off_out, bytes}, {total, off_total, invert ? 8 : c.rec}}, [&](char *vecs, char *ws) {
+                       return frs_run(ctx, f, st, c, n, a ? vecs : nullptr, b ? vecs + vec : nullptr, vecs + off_out,
+                                      total ? vecs + off_total : nullptr, ws);
+                   });
 }
 
 }   // namespace
@@ -4636,11 +4622,7 @@ int amdmsm_fr_inverse(int curve, const void *x, int plain, void *out) {
     const fr_rec raw = fr_from_words(f, (const uint32_t *)x), zero;
     if (!fr_below_modulus(f, raw.v) || fr_same(f, raw, zero)) return AMDMSM_ERR_BAD_ARG;
     fr_rec r = fr_inv_host(f, fr_read(f, x, plain != 0));
-    if (plain) {   // out of Montgomery form
-        fr_rec one;
-        one.v[0] = 1;
-        r = fr_mul(f, r, one);
-    }
+    if (plain) r = fr_from_mont(f, r);
     memcpy(out, r.v, (size_t)f->words * 4);
     return AMDMSM_OK;
 }

@@ -261,7 +261,7 @@ def fft_twiddles(curve, n, inverse=False):
     n does not divide the 2-part of r - 1."""
     n = int(n)
     r = fr_modulus(curve, G1)
-    limbs = sizes(curve, G1)["fr_bytes"] // 8
+    limbs = _fr_limbs(curve)
     if n < 1 or n & (n - 1):
         raise ValueError(f"n = {n} is not a power of two")
     if (r - 1) % n:
@@ -313,10 +313,9 @@ FR_MATRIX_PLAN_WORDS = 16   # include/amdmsm.h AMDMSM_FR_MATRIX_PLAN_WORDS
 
 def _csr_arrays(curve, offsets, cols, coeffs):
     """the CSR arrays as the C entries take them: uint64 offsets, uint32 columns, (nnz, fr_limbs) uint64 records"""
-    limbs = sizes(curve, G1)["fr_bytes"] // 8
     offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
     cols = np.ascontiguousarray(cols, dtype=np.uint32)
-    coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64).reshape(-1, limbs)
+    coeffs, _ = _fr_array(curve, coeffs)
     assert offsets.ndim == 1 and cols.ndim == 1 and cols.shape[0] == coeffs.shape[0], "cols and coeffs: one per entry"
     assert offsets.shape[0] == 0 or int(offsets[-1]) <= cols.shape[0], "offsets reach beyond the entries given"
     ptr = lambda a: _np_ptr(a) if a.size else None
@@ -389,7 +388,7 @@ def plan_fr_scan(curve, n, a=True, b=False, invert=False, reverse=False, exclusi
 def fr_inverse(curve, x, plain=True):
     """``1 / x`` in Fr of the curve (``amdmsm_fr_inverse``: one Fermat power on the host), ``x`` and the result ints --
     with ``plain=False`` both are taken as Montgomery residues.  ValueError for 0 and for a value not below r."""
-    limbs = sizes(curve, G1)["fr_bytes"] // 8
+    limbs = _fr_limbs(curve)
     x = int(x)
     if x < 0 or x >> (64 * limbs):
         raise ValueError("x does not fit an Fr record")
@@ -483,6 +482,24 @@ def _vp(x):
 
 def _np_ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _opt_ptr(a):
+    return None if a is None else _np_ptr(a)   # a host array that may be absent
+
+
+def _opt_dev(p):
+    return None if p is None else _vp(p)   # a device address that may be absent
+
+
+def _fr_limbs(curve):
+    return sizes(curve, G1)["fr_bytes"] // 8
+
+
+def _fr_array(curve, a):
+    """``a`` as a contiguous (n, fr_limbs) uint64 array, and its n; None stays None, with n = 0"""
+    a = None if a is None else np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, _fr_limbs(curve))
+    return a, 0 if a is None else a.shape[0]
 
 
 # include/amdmsm.h amdmsm_read_fn: size_t read(void *read_ctx, void *dst, size_t bytes)
@@ -1011,7 +1028,7 @@ class Engine:
         """(omega, pre, post, scale) records of a transform of ``n`` scalars; the inverses are Python's.  ``given``: the
         caller's own (pre, post, scale) of the general form, each taking the place of the derived one"""
         r = fr_modulus(curve, G1)
-        limbs = sizes(curve, G1)["fr_bytes"] // 8
+        limbs = _fr_limbs(curve)
         w = (fr_root_of_unity(curve, n) if omega is None else int(omega)) if n > 1 else None
         pre = post = scale = None
         if inverse:
@@ -1032,7 +1049,7 @@ class Engine:
         ``coset`` also g^-j on the way out: the inverse of the two above.  ``tile_log2``: stages per global pass, 0 =
         default (``plan_fr_fft`` tells).  ``pre``, ``post``, ``scale`` (ints): the general form
         ``out[j] = post^j scale sum_i pre^i values[i] w^(i j)``, each in place of what the flags derive."""
-        limbs = sizes(curve, G1)["fr_bytes"] // 8
+        limbs = _fr_limbs(curve)
         values = np.ascontiguousarray(values, dtype=np.uint64)
         n = int(values.shape[0]) if values.ndim == 2 else 0
         if n:
@@ -1042,9 +1059,8 @@ class Engine:
         assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape == (n, limbs)
         w, pre, post, scale = self._fr_params(curve, n, omega, inverse, coset, plain, (pre, post, scale))
         o = self._opts(scalars_plain=plain)
-        ptr = lambda a: None if a is None else _np_ptr(a)
-        rc = self.lib.amdmsm_fr_fft(self.h, curve, _np_ptr(values) if n else None, ctypes.c_size_t(n), ptr(w), ptr(pre),
-                                    ptr(post), ptr(scale), int(tile_log2), ctypes.byref(o), _np_ptr(out) if n else None)
+        rc = self.lib.amdmsm_fr_fft(self.h, curve, _np_ptr(values) if n else None, ctypes.c_size_t(n), _opt_ptr(w), _opt_ptr(pre),
+                                    _opt_ptr(post), _opt_ptr(scale), int(tile_log2), ctypes.byref(o), _np_ptr(out) if n else None)
         self._check(rc, "amdmsm_fr_fft")
         return out
 
@@ -1063,14 +1079,12 @@ class Engine:
         """``out[i] = sum_k coeffs[k] x[cols[k]]`` over row i (``amdmsm_fr_matrix_apply``): ``x`` (n_x >= n_cols, fr_limbs)
         uint64 records in the form ``plain`` says, the result -- ``n_out`` records, the rows and zeros behind them --
         in the same form."""
-        limbs = sizes(mat.curve, G1)["fr_bytes"] // 8
-        x = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, limbs)
+        x, n_x = _fr_array(mat.curve, x)
         n_out = mat.n_rows if n_out is None else int(n_out)
-        out = np.zeros((n_out, limbs), dtype=np.uint64)
+        out = np.zeros((n_out, x.shape[1]), dtype=np.uint64)
         o = self._opts(scalars_plain=plain)
-        rc = self.lib.amdmsm_fr_matrix_apply(self.h, ctypes.c_uint64(mat.handle), _np_ptr(x) if x.size else None,
-                                             ctypes.c_size_t(x.shape[0]), _np_ptr(out) if n_out else None,
-                                             ctypes.c_size_t(n_out), ctypes.byref(o))
+        rc = self.lib.amdmsm_fr_matrix_apply(self.h, ctypes.c_uint64(mat.handle), _np_ptr(x) if n_x else None, ctypes.c_size_t(n_x),
+                                             _np_ptr(out) if n_out else None, ctypes.c_size_t(n_out), ctypes.byref(o))
         self._check(rc, "amdmsm_fr_matrix_apply")
         return out
 
@@ -1079,8 +1093,7 @@ class Engine:
         synchronised; records n_rows .. n_out - 1 of ``d_out`` are written as zero."""
         o = self._opts(scalars_plain=plain, stream=stream)
         self._check(self.lib.amdmsm_fr_matrix_apply_device(self.h, ctypes.c_uint64(mat.handle),
-                                                           None if d_x is None else _vp(d_x), ctypes.c_size_t(n_x),
-                                                           None if d_out is None else _vp(d_out), ctypes.c_size_t(n_out),
+                                                           _opt_dev(d_x), ctypes.c_size_t(n_x), _opt_dev(d_out), ctypes.c_size_t(n_out),
                                                            ctypes.byref(o)), "amdmsm_fr_matrix_apply_device")
 
     def _scan_flags(self, reverse, exclusive):
@@ -1091,17 +1104,14 @@ class Engine:
         """The recurrence ``y_i = a_i y_(i-1) + b_i`` over host arrays (``amdmsm_fr_scan``): ``a`` / ``b`` (n, fr_limbs)
         uint64 records or None, ``a_const`` / ``init`` ints (or records as arrays).  ``reverse``: from the last record
         down; ``exclusive``: ``out[i]`` is the value that enters record i.  Returns ``(out, total)``, total a record."""
-        limbs = sizes(curve, G1)["fr_bytes"] // 8
-        r = fr_modulus(curve, G1)
-        a = None if a is None else np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, limbs)
-        b = None if b is None else np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, limbs)
-        n = a.shape[0] if a is not None else (b.shape[0] if b is not None else 0)
+        limbs, r = _fr_limbs(curve), fr_modulus(curve, G1)
+        (a, n_a), (b, n_b) = _fr_array(curve, a), _fr_array(curve, b)
+        n = n_b if a is None else n_a
         assert a is None or b is None or a.shape == b.shape, "a and b: one record each per position"
         out, total = np.zeros((n, limbs), dtype=np.uint64), np.zeros(limbs, dtype=np.uint64)
         ac, ini = _fr_host_record(a_const, limbs, r, plain), _fr_host_record(init, limbs, r, plain)
         o = self._opts(scalars_plain=plain)
-        ptr = lambda v: None if v is None else _np_ptr(v)
-        rc = self.lib.amdmsm_fr_scan(self.h, curve, ctypes.c_size_t(n), ptr(a), ptr(ac), ptr(b), ptr(ini),
+        rc = self.lib.amdmsm_fr_scan(self.h, curve, ctypes.c_size_t(n), _opt_ptr(a), _opt_ptr(ac), _opt_ptr(b), _opt_ptr(ini),
                                      self._scan_flags(reverse, exclusive) if flags is None else int(flags), int(tile_log2),
                                      ctypes.byref(o), _np_ptr(out), _np_ptr(total))
         self._check(rc, "amdmsm_fr_scan")
@@ -1111,12 +1121,10 @@ class Engine:
                        exclusive=False, plain=False, tile_log2=0, stream=None, flags=None):
         """``fr_scan`` on ``n`` device-resident records (``amdmsm_fr_scan_device``); ``d_out`` may be ``d_a`` or ``d_b``,
         ``d_total`` (one record) may be None; enqueued on ``stream``, not synchronised."""
-        limbs = sizes(curve, G1)["fr_bytes"] // 8
-        r = fr_modulus(curve, G1)
+        limbs, r = _fr_limbs(curve), fr_modulus(curve, G1)
         ac, ini = _fr_host_record(a_const, limbs, r, plain), _fr_host_record(init, limbs, r, plain)
         o = self._opts(scalars_plain=plain, stream=stream)
-        ptr = lambda v: None if v is None else _np_ptr(v)
-        dev = lambda v: None if v is None else _vp(v)
+        ptr, dev = _opt_ptr, _opt_dev
         self._check(self.lib.amdmsm_fr_scan_device(self.h, curve, ctypes.c_size_t(n), dev(d_a), ptr(ac), dev(d_b), ptr(ini),
                                                    self._scan_flags(reverse, exclusive) if flags is None else int(flags),
                                                    int(tile_log2), ctypes.byref(o), dev(d_out), dev(d_total)),
@@ -1125,10 +1133,8 @@ class Engine:
     def fr_batch_invert(self, curve, values, plain=False):
         """``out[i] = 1 / values[i]``, 0 where ``values[i]`` is 0 (``amdmsm_fr_batch_invert``): (n, fr_limbs) uint64
         records in the form ``plain`` says.  Returns ``(out, zero_count)``."""
-        limbs = sizes(curve, G1)["fr_bytes"] // 8
-        values = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, limbs)
-        n = values.shape[0]
-        out, zeros = np.zeros((n, limbs), dtype=np.uint64), ctypes.c_uint64(0)
+        values, n = _fr_array(curve, values)
+        out, zeros = np.zeros_like(values), ctypes.c_uint64(0)
         o = self._opts(scalars_plain=plain)
         rc = self.lib.amdmsm_fr_batch_invert(self.h, curve, ctypes.c_size_t(n), _np_ptr(values) if n else None, ctypes.byref(o),
                                              _np_ptr(out) if n else None, ctypes.byref(zeros))
@@ -1139,9 +1145,8 @@ class Engine:
         """``fr_batch_invert`` on ``n`` device-resident records (``amdmsm_fr_batch_invert_device``); ``d_out`` may be
         ``d_values``; ``d_zero_count``: a uint64 in device memory or None; enqueued on ``stream``, not synchronised."""
         o = self._opts(scalars_plain=plain, stream=stream)
-        dev = lambda v: None if v is None else _vp(v)
-        self._check(self.lib.amdmsm_fr_batch_invert_device(self.h, curve, ctypes.c_size_t(n), dev(d_values), int(tile_log2),
-                                                           ctypes.byref(o), dev(d_out), dev(d_zero_count)),
+        self._check(self.lib.amdmsm_fr_batch_invert_device(self.h, curve, ctypes.c_size_t(n), _opt_dev(d_values), int(tile_log2),
+                                                           ctypes.byref(o), _opt_dev(d_out), _opt_dev(d_zero_count)),
                     "amdmsm_fr_batch_invert_device")
 
     def batch_exp_timings(self):
@@ -1292,30 +1297,25 @@ class Engine:
         not synchronised."""
         w, pre, post, scale = self._fr_params(curve, n, omega, inverse, coset, plain, (pre, post, scale))
         o = self._opts(scalars_plain=plain, stream=stream)
-        ptr = lambda a: None if a is None else _np_ptr(a)
-        self._check(self.lib.amdmsm_fr_fft_device(self.h, curve, None if d_values is None else _vp(d_values),
-                                                  ctypes.c_size_t(n), ptr(w), ptr(pre), ptr(post), ptr(scale), int(tile_log2),
-                                                  ctypes.byref(o), None if d_out is None else _vp(d_out)),
+        self._check(self.lib.amdmsm_fr_fft_device(self.h, curve, _opt_dev(d_values), ctypes.c_size_t(n), _opt_ptr(w), _opt_ptr(pre),
+                                                  _opt_ptr(post), _opt_ptr(scale), int(tile_log2), ctypes.byref(o), _opt_dev(d_out)),
                     "amdmsm_fr_fft_device")
 
     def fr_powers_device(self, curve, base, n, d_out, plain=False, stream=None):
         """``d_out[i] = base^i`` for i < n (``amdmsm_fr_powers_device``; ``base`` an int): twiddles for
         ``group_fft_device``, coset powers for ``scalar_mul_vec_device``; enqueued on ``stream``, not synchronised."""
-        limbs = sizes(curve, G1)["fr_bytes"] // 8
-        b = _fr_record(base, limbs, fr_modulus(curve, G1), plain)
+        b = _fr_record(base, _fr_limbs(curve), fr_modulus(curve, G1), plain)
         o = self._opts(scalars_plain=plain, stream=stream)
-        self._check(self.lib.amdmsm_fr_powers_device(self.h, curve, _np_ptr(b), ctypes.c_size_t(n), ctypes.byref(o),
-                                                     None if d_out is None else _vp(d_out)), "amdmsm_fr_powers_device")
+        self._check(self.lib.amdmsm_fr_powers_device(self.h, curve, _np_ptr(b), ctypes.c_size_t(n), ctypes.byref(o), _opt_dev(d_out)),
+                    "amdmsm_fr_powers_device")
 
     def fr_muladd_device(self, curve, n, d_a, d_b, d_out, d_c=None, k=None, plain=False, stream=None):
         """``d_out[i] = (a_i * b_i - c_i) * k`` (``amdmsm_fr_muladd_device``; ``d_c`` None = 0, ``k`` an int, None = 1);
         ``d_out`` may be any input; enqueued on ``stream``, not synchronised."""
-        limbs = sizes(curve, G1)["fr_bytes"] // 8
-        kk = None if k is None else _fr_record(k, limbs, fr_modulus(curve, G1), plain)
+        kk = None if k is None else _fr_record(k, _fr_limbs(curve), fr_modulus(curve, G1), plain)
         o = self._opts(scalars_plain=plain, stream=stream)
-        self._check(self.lib.amdmsm_fr_muladd_device(self.h, curve, ctypes.c_size_t(n), _vp(d_a), _vp(d_b),
-                                                     None if d_c is None else _vp(d_c), None if kk is None else _np_ptr(kk),
-                                                     ctypes.byref(o), _vp(d_out)), "amdmsm_fr_muladd_device")
+        self._check(self.lib.amdmsm_fr_muladd_device(self.h, curve, ctypes.c_size_t(n), _vp(d_a), _vp(d_b), _opt_dev(d_c),
+                                                     _opt_ptr(kk), ctypes.byref(o), _vp(d_out)), "amdmsm_fr_muladd_device")
 
     def msm_device_segments(self, curve, group, d_bases_affine, n_bases, d_scalars, n_terms, offsets, d_out, *,
                             shared_bases=False, long_from=0, out_form=OUT_LIBFF, scalars_plain=False, chunk_terms=0,

@@ -10,58 +10,21 @@ import pytest
 
 import fr_fft_model as model
 import group_fft_model as gmodel
+from fr_dev import BAD_ARG, FOUR, OK, SENTINEL, TOO_LARGE, UNSUPPORTED, Dev, at, hip_runtime
 
 pytestmark = pytest.mark.gpu
 
 import libff_amd  # noqa: E402
 from libff_amd import OUT_AFFINE, fft_twiddles, multi_exp_base_form_special, plan_fr_fft  # noqa: E402
 
-OK, BAD_ARG, UNSUPPORTED, TOO_LARGE = 0, -2, -3, -5
 CURVES = sorted(model.CURVES)
 IDS = [model.CURVES[c] for c in CURVES]
-THREE = [pytest.param(0, id="alt_bn128"), pytest.param(4, id="mnt4"), pytest.param(2, id="bw6_761")]   # 8, 10, 12 words
-SENTINEL = 0x5a5a5a5a5a5a5a5a
+THREE = FOUR[:3]   # 8, 10, 12 words
 
 
 def tiles(curve):
     p = plan_fr_fft(curve, 1)
     return p["tile_log2"], p["tile_min"]
-
-
-class Dev:
-    """device buffers of a test, freed together"""
-
-    def __init__(self, engine):
-        self.e, self.ptrs = engine, []
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for p in self.ptrs:
-            self.e.free(p)
-
-    def buf(self, nbytes):
-        p = self.e.malloc(max(nbytes, 64))
-        self.ptrs.append(p)
-        return p
-
-    def up(self, arr):
-        p = self.buf(arr.nbytes)
-        if arr.nbytes:
-            self.e.h2d(p, arr)
-        return p
-
-    def down(self, p, shape):
-        out = np.zeros(shape, dtype=np.uint64)
-        self.e.synchronize()
-        if out.nbytes:
-            self.e.d2h(out, p)
-        return out
-
-
-def at(p, nbytes):
-    return ctypes.c_void_p(p.value + nbytes)
 
 
 _want = {}
@@ -179,14 +142,7 @@ def test_device_entry(engine, curve):
     f = model.field(curve)
     T, _ = tiles(curve)
     rec = f.limbs * 8
-    hip = None
-    for path in ("libamdhip64.so", "/opt/rocm/lib/libamdhip64.so"):
-        try:
-            hip = ctypes.CDLL(path)
-            break
-        except OSError:
-            continue
-    assert hip is not None
+    hip = hip_runtime()
     T, t = tiles(curve)
     # two passes at the default tile; three at the smallest, where an in-place call takes a second vector
     for tile, n, passes in ((0, 1 << (T + 1), 2), (t, 1 << (2 * t + 1), 3)):

@@ -3,9 +3,7 @@ six scalar fields, the default path and the straightforward one behind AMDMSM_FR
 from tests/fr_matrix_model.py -- Python integers, the definition -- and everything is compared bit for bit, as
 records.  Nothing here knows how a matrix is stored: the row lengths are chosen from what libff_amd.plan_fr_matrix
 reports (the thresholds between the row classes, the chain length T of the field)."""
-import contextlib
 import ctypes
-import os
 import random
 
 import numpy as np
@@ -13,6 +11,7 @@ import pytest
 
 import fr_matrix_model as model
 import group_fft_model as gmodel
+from fr_dev import BAD_ARG, FOUR, OK, SENTINEL, TOO_LARGE, UNSUPPORTED, Dev, at, env_path, hip_runtime, poly_eval
 from fr_fft_model import GENERATOR
 from fr_fft_model import fft as model_fft
 
@@ -21,27 +20,14 @@ pytestmark = pytest.mark.gpu
 import libff_amd  # noqa: E402
 from libff_amd import OUT_AFFINE, multi_exp_base_form_special, plan_fr_matrix  # noqa: E402
 
-OK, BAD_ARG, UNSUPPORTED, TOO_LARGE = 0, -2, -3, -5
 CURVES = sorted(model.CURVES)
 IDS = [model.CURVES[c] for c in CURVES]
-# 8, 10 and 12 words, and bls12_381 for its chain of two products
-FOUR = [pytest.param(0, id="alt_bn128"), pytest.param(4, id="mnt4"), pytest.param(2, id="bw6_761"), pytest.param(3, id="bls12_381")]
 PATHS = [pytest.param(False, id="resident"), pytest.param(True, id="naive")]
-SENTINEL = 0x5a5a5a5a5a5a5a5a
 
 
-@contextlib.contextmanager
 def path(naive):
     """the environment of a load: AMDMSM_FR_MATRIX_NAIVE decides the form the handle keeps"""
-    old = os.environ.pop("AMDMSM_FR_MATRIX_NAIVE", None)
-    if naive:
-        os.environ["AMDMSM_FR_MATRIX_NAIVE"] = "1"
-    try:
-        yield
-    finally:
-        os.environ.pop("AMDMSM_FR_MATRIX_NAIVE", None)
-        if old is not None:
-            os.environ["AMDMSM_FR_MATRIX_NAIVE"] = old
+    return env_path("AMDMSM_FR_MATRIX_NAIVE", naive)
 
 
 def load(engine, curve, m, plain, naive):
@@ -54,51 +40,6 @@ def thresholds(curve):
     f = model.field(curve)
     p = plan_fr_matrix(curve, np.zeros(1, dtype=np.uint64), np.zeros(0, dtype=np.uint32), np.zeros((0, f.limbs), dtype=np.uint64), 0)
     return p["wave_row"], p["split_row"], p["chunk"]
-
-
-class Dev:
-    """device buffers of a test, freed together"""
-
-    def __init__(self, engine):
-        self.e, self.ptrs = engine, []
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for p in self.ptrs:
-            self.e.free(p)
-
-    def buf(self, nbytes):
-        p = self.e.malloc(max(nbytes, 64))
-        self.ptrs.append(p)
-        return p
-
-    def up(self, arr):
-        p = self.buf(arr.nbytes)
-        if arr.nbytes:
-            self.e.h2d(p, arr)
-        return p
-
-    def down(self, p, shape):
-        out = np.zeros(shape, dtype=np.uint64)
-        self.e.synchronize()
-        if out.nbytes:
-            self.e.d2h(out, p)
-        return out
-
-
-def at(p, nbytes):
-    return ctypes.c_void_p(p.value + nbytes)
-
-
-def hip_runtime():
-    for name in ("libamdhip64.so", "/opt/rocm/lib/libamdhip64.so"):
-        try:
-            return ctypes.CDLL(name)
-        except OSError:
-            continue
-    raise AssertionError("libamdhip64.so not found")
 
 
 _cases = {}
@@ -398,13 +339,6 @@ def test_a_record_that_is_no_field_element_stays_in_its_rows(engine):
     assert (got[clean] == want[clean]).all()
 
 
-def _poly_eval(coeffs, t, r):
-    acc = 0
-    for c in reversed(coeffs):
-        acc = (acc * t + c) % r
-    return acc
-
-
 @pytest.mark.parametrize("naive", PATHS)
 def test_from_the_assignment_to_the_quotient(engine, port, naive):
     """a satisfied constraint system -- z_{k+2} = z_k z_{k+1} and a few linear rows -- from z on the device to Az o Bz - Cz
@@ -463,6 +397,6 @@ def test_from_the_assignment_to_the_quotient(engine, port, naive):
     winv, ninv = pow(w, -1, r), pow(n, -1, r)
     pa, pb, pc = (model_fft(v, winv, r, scale=ninv) for v in (az, bz, cz))
     tau = rng.randrange(r)
-    lhs = (_poly_eval(pa, tau, r) * _poly_eval(pb, tau, r) - _poly_eval(pc, tau, r)) % r
-    assert lhs == _poly_eval(h, tau, r) * (pow(tau, n, r) - 1) % r
+    lhs = (poly_eval(pa, tau, r) * poly_eval(pb, tau, r) - poly_eval(pc, tau, r)) % r
+    assert lhs == poly_eval(h, tau, r) * (pow(tau, n, r) - 1) % r
     assert any(h)

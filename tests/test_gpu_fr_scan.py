@@ -3,9 +3,7 @@ fr_batch_invert_device), all six scalar fields, the tiled path and the one-lane 
 Expected values come from tests/fr_scan_model.py -- Python integers, the recurrence as a loop and the inverse as a power
 -- and everything is compared record for record.  Nothing here knows how a tile is cut: the sizes come from what
 libff_amd.plan_fr_scan reports (the smallest tile T0, the tiles S0 of a spine step, the default tile)."""
-import contextlib
 import ctypes
-import os
 import random
 
 import numpy as np
@@ -13,36 +11,24 @@ import pytest
 
 import fr_scan_model as model
 import group_fft_model as gmodel
+from fr_dev import BAD_ARG, FOUR, OK, SENTINEL, TOO_LARGE, UNSUPPORTED, Dev, at, env_path, hip_runtime, poly_eval
 
 pytestmark = pytest.mark.gpu
 
 import libff_amd  # noqa: E402
 from libff_amd import OUT_AFFINE, fr_inverse, multi_exp_base_form_special, plan_fr_scan  # noqa: E402
 
-OK, BAD_ARG, UNSUPPORTED, TOO_LARGE = 0, -2, -3, -5
 CURVES = sorted(model.CURVES)
 IDS = [model.CURVES[c] for c in CURVES]
-# 8, 10 and 12 words, and bls12_381
-FOUR = [pytest.param(0, id="alt_bn128"), pytest.param(4, id="mnt4"), pytest.param(2, id="bw6_761"), pytest.param(3, id="bls12_381")]
 PATHS = [pytest.param(False, id="tiled"), pytest.param(True, id="naive")]
-SENTINEL = 0x5a5a5a5a5a5a5a5a
 # which operands a scan is given: (a vector, a_const, b vector)
 COMBOS = [(True, False, False), (True, False, True), (False, True, False), (False, True, True), (False, False, True)]
 FLAGS = [(False, False), (False, True), (True, False), (True, True)]   # (reverse, exclusive)
 
 
-@contextlib.contextmanager
 def path(naive):
     """the environment of a call: AMDMSM_FR_SCAN_NAIVE is read per call"""
-    old = os.environ.pop("AMDMSM_FR_SCAN_NAIVE", None)
-    if naive:
-        os.environ["AMDMSM_FR_SCAN_NAIVE"] = "1"
-    try:
-        yield
-    finally:
-        os.environ.pop("AMDMSM_FR_SCAN_NAIVE", None)
-        if old is not None:
-            os.environ["AMDMSM_FR_SCAN_NAIVE"] = old
+    return env_path("AMDMSM_FR_SCAN_NAIVE", naive)
 
 
 def geometry(curve):
@@ -52,51 +38,6 @@ def geometry(curve):
     small = plan_fr_scan(curve, 0, tile_log2=lo)
     assert small["tile"] == 1 << lo <= 1 << 8 and small["tile"] * small["spine_step"] <= 1 << 17
     return lo, small["tile"], small["spine_step"], p["tile"]
-
-
-class Dev:
-    """device buffers of a test, freed together"""
-
-    def __init__(self, engine):
-        self.e, self.ptrs = engine, []
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for p in self.ptrs:
-            self.e.free(p)
-
-    def buf(self, nbytes):
-        p = self.e.malloc(max(nbytes, 64))
-        self.ptrs.append(p)
-        return p
-
-    def up(self, arr):
-        p = self.buf(arr.nbytes)
-        if arr.nbytes:
-            self.e.h2d(p, arr)
-        return p
-
-    def down(self, p, shape):
-        out = np.zeros(shape, dtype=np.uint64)
-        self.e.synchronize()
-        if out.nbytes:
-            self.e.d2h(out, p)
-        return out
-
-
-def at(p, nbytes):
-    return ctypes.c_void_p(p.value + nbytes)
-
-
-def hip_runtime():
-    for name in ("libamdhip64.so", "/opt/rocm/lib/libamdhip64.so"):
-        try:
-            return ctypes.CDLL(name)
-        except OSError:
-            continue
-    raise AssertionError("libamdhip64.so not found")
 
 
 _vecs = {}
@@ -565,13 +506,6 @@ def test_refused_calls_leave_the_output_alone(engine, curve):
 
 
 # ---- end to end: device entries only between upload and download ------------------------------------------------------------
-def _poly_eval(coeffs, t, r):
-    acc = 0
-    for c in reversed(coeffs):
-        acc = (acc * t + c) % r
-    return acc
-
-
 @pytest.mark.parametrize("naive", PATHS)
 def test_lagrange_coefficients(engine, naive):
     """L_i(t) = (t^n - 1) / n * w^i / (t - w^i) from the powers of w, one product step and one batch inversion; then
@@ -602,7 +536,7 @@ def test_lagrange_coefficients(engine, naive):
         engine.fr_fft_device(curve, d_f, n, d_f)
         engine.fr_muladd_device(curve, n, d_f, d_l, d_f)
         engine.fr_scan_device(curve, n, d_f, None, d_f, d_total=d_sum)
-        assert f.ints(d.down(d_sum, (1, f.limbs)), False) == [_poly_eval(coeffs, t, r)]
+        assert f.ints(d.down(d_sum, (1, f.limbs)), False) == [poly_eval(coeffs, t, r)]
 
 
 @pytest.mark.parametrize("naive", PATHS)
@@ -645,7 +579,7 @@ def test_kzg_quotient_into_the_msm(engine, port, naive):
         d_p, d_q, d_pz = d.up(f.records(p, False)), d.buf(n * rec), d.buf(rec)
         engine.fr_scan_device(curve, n, d_q, None, d_p, a_const=z, init=0, reverse=True, exclusive=True, d_total=d_pz)
         q, pz = f.ints(d.down(d_q, (n, f.limbs)), False), f.ints(d.down(d_pz, (1, f.limbs)), False)[0]
-        assert model.synthetic_division_holds(r, p, z, q, pz) and pz == _poly_eval(p, z, r)
+        assert model.synthetic_division_holds(r, p, z, q, pz) and pz == poly_eval(p, z, r)
         # the bases [tau^i] G: n copies of G times the powers of tau
         d_g, d_gaff = d.up(np.repeat(grp.records([1]), n, axis=0)), d.buf(n * s["affine_bytes"])
         d_tau, d_xyz, d_bases, d_pt = d.buf(n * rec), d.buf(n * s["g_bytes"]), d.buf(n * s["affine_bytes"]), d.buf(s["g_bytes"])
@@ -655,4 +589,4 @@ def test_kzg_quotient_into_the_msm(engine, port, naive):
         engine.import_bases_device(grp.curve, grp.group, d_xyz, s["g_bytes"], multi_exp_base_form_special, n, d_bases)
         engine.msm_device(grp.curve, grp.group, d_bases, d_q, n, d_pt, out_form=OUT_AFFINE)
         got = d.down(d_pt, (1, grp.gl))
-    assert (got == grp.records([_poly_eval(q, tau, r)])).all()
+    assert (got == grp.records([poly_eval(q, tau, r)])).all()
