@@ -301,7 +301,7 @@ int amdmsm_fr_modulus(int curve, int group, void *r_plain);
  * first pass loads and post^j * scale as the last pass stores.  Workspace, from the context's slots: one vector of n
  * records (two for an in-place call of an odd number of passes above one; the host entry adds the uploaded vector),
  * and the powers of pre and post a pass needs: (n >> stages) + 2^stages records of its first / last pass.  The n / 2
- * powers of omega are kept with the context for the last two (curve, n, omega) it served and freed with it.
+ * powers of omega are kept with the context for the last four (curve, n, omega) it served and freed with it.
  * n = 0 succeeds and writes nothing; n = 1 writes scale * a_0.
  * AMDMSM_ERR_UNSUPPORTED for an unknown curve.  AMDMSM_ERR_BAD_ARG, with amdmsm_last_error naming the condition, before
  * anything is launched or written: n not a power of two, a null vector pointer with n > 0, null omega with n > 1, an
@@ -393,6 +393,70 @@ int amdmsm_plan_fr_scan(int curve, size_t n, int kind_and_flags, int tile_log2, 
    power on the host, no context: n^-1, g^-1 and omega^-1 of an inverse transform.  AMDMSM_ERR_BAD_ARG for 0 and for a
    value not below r */
 int amdmsm_fr_inverse(int curve, const void *x, int plain, void *out);
+
+/* Evaluation domains over Fr as libfqfft chooses them -- what libsnark's r1cs_to_qap_witness_map gets from
+ * get_evaluation_domain(num_constraints + num_inputs + 1), a size that is hardly ever a power of two -- and on them the
+ * transforms, the vanishing polynomial and the division by it on a coset: a quotient whose H-query belongs to a step
+ * radix-2 domain stays on the device.  Restated from libfqfft's step_radix2_domain and get_evaluation_domain, not checked
+ * against its code: the point sets and their order below are the contract.  root(n) is amdmsm_fr_root_of_unity, log2 the
+ * ceiling log, s the 2-adicity of r - 1.
+ * Choice, min_size >= 2: big = 2^(log2(min_size) - 1), small = min_size - big, rounded = 2^log2(small).  min_size a
+ * power of two: the basic radix-2 domain of min_size.  Else small a power of two: the step domain of min_size.  Else
+ * big + rounded a power of two: the basic domain of it.  Else the step domain of big + rounded.
+ *   basic, m points:      x_j = root(m)^j;                                   Z = X^m - 1;      needs log2 m <= s
+ *   step, m = B + S, B and S powers of two, S < B, w = root(2 B), sigma = root(S):
+ *                         x_j = w^(2 j), j < B;  x_j = w sigma^(j - B), B <= j < m;
+ *                         Z = (X^B - 1) (X^S - w^S);                                           needs log2(2 B) <= s
+ * Where libfqfft would go on to its extended radix-2 domain (m = 2^(s + 1): MNT6 at 2^18) or to a geometric sequence
+ * (everything else above 2^s on MNT6) the answer is AMDMSM_ERR_UNSUPPORTED, the message of an entry with a context naming
+ * that domain; min_size < 2 is AMDMSM_ERR_BAD_ARG, m > 2^28 AMDMSM_ERR_TOO_LARGE.
+ *
+ * amdmsm_fr_domain: out[0] = the kind, out[1] = m, out[2] = B (m for a basic domain), out[3] = S (0 for a basic domain),
+ * out[4] = log2 of the order of w, out[5] = workspace bytes of an out-of-place device transform with a coset.
+ * amdmsm_fr_domain_element: x_idx.  amdmsm_fr_domain_vanishing: Z(t).  amdmsm_fr_domain_z_terms: Z as *count <= 4 pairs
+ * (idx[k], coefficient k), the highest index first -- what libfqfft's add_poly_Z adds, times a constant, to a
+ * coefficient vector.  amdmsm_fr_multiplicative_generator: libff's Fr::multiplicative_generator, the coset shift of a
+ * quotient.  One record in host memory each, Montgomery residues or with plain != 0 plain integers; no context; the
+ * four entries that take m answer AMDMSM_ERR_BAD_ARG for an m that amdmsm_fr_domain would not answer with. */
+#define AMDMSM_DOMAIN_BASIC_RADIX2 0
+#define AMDMSM_DOMAIN_STEP_RADIX2 1
+int amdmsm_fr_domain(int curve, size_t min_size, size_t out[6]);
+int amdmsm_fr_domain_element(int curve, size_t m, size_t idx, int plain, void *out);
+int amdmsm_fr_domain_vanishing(int curve, size_t m, const void *t, int plain, void *out);
+int amdmsm_fr_domain_z_terms(int curve, size_t m, int plain, size_t idx[4], void *coeffs, int *count);
+int amdmsm_fr_multiplicative_generator(int curve, int plain, void *out);
+/* The transform over the domain of m points, records and device vectors as for amdmsm_fr_fft:
+ *   forward   out[j] = A(g x_j), A(X) = sum over i < m of values[i] X^i
+ *   inverse   (AMDMSM_DOMAIN_INVERSE) out = the m coefficients of the A of degree < m with A(g x_j) = values[j]
+ *   coset     g, one record in host memory, NULL = 1; tile_log2 as for amdmsm_fr_fft, for the passes
+ * A basic domain is amdmsm_fr_fft with libff's root.  A step domain is one sweep in front of (the fold) or behind (the
+ * merge) radix-2 transforms of B and of S records, which are amdmsm_fr_fft's passes: the sweep reads the m records once,
+ * applies g^i and w^i, converts plain records, and sums the K = B / S rows of a K x S matrix column by column -- over
+ * lanes and workgroups, the partial sums by further launches in stream order; no kernel waits for another workgroup
+ * (DESIGN section 22).  Workspace from the context's slots (amdmsm_fr_domain reports it); the B powers of w and the powers
+ * of the two transforms stay in the context's cache of four.
+ * amdmsm_fr_domain_divide_by_z: out[j] = values[j] / Z(g x_j), the step between the coset transform and the inverse
+ * coset transform of a quotient; coset is required.  Below B the denominator takes K values, built on the device and
+ * inverted by the batch inversion above; from B on, and for a basic domain, it is one value, inverted on the host.
+ * Device entries: enqueued on opts->stream (or the context's), not synchronised; d_out may be d_values, any other overlap
+ * is refused.  The host entries upload, run, download and synchronise.
+ * Refused before anything is launched or written and before the context is looked at, amdmsm_last_error naming the
+ * argument: AMDMSM_ERR_UNSUPPORTED for an unknown curve and the domains left out; AMDMSM_ERR_TOO_LARGE for m > 2^28;
+ * AMDMSM_ERR_BAD_ARG for an m that is no domain size (the message names the size amdmsm_fr_domain chooses), m < 2, a
+ * null or misaligned vector, a partial overlap, unknown flags, a tile_log2 out of range, a wrong opts->struct_size, a
+ * coset not below r or zero, and for the division a missing coset or one with g^(2 B) = 1 (step) or g^m = 1 (basic),
+ * where Z has a zero.
+ * With timing enabled (amdmsm_get_timings): [0] the powers (host entries: with the upload), [1] the kernels, [2] the
+ * download (host entries), [AMDMSM_PH_TOTAL] the call. */
+#define AMDMSM_DOMAIN_INVERSE 1
+int amdmsm_fr_domain_fft(amdmsm_ctx *ctx, int curve, const void *values, size_t m, int flags, const void *coset, int tile_log2,
+                         const amdmsm_opts *opts, void *out);
+int amdmsm_fr_domain_fft_device(amdmsm_ctx *ctx, int curve, const void *d_values, size_t m, int flags, const void *coset,
+                                int tile_log2, const amdmsm_opts *opts, void *d_out);
+int amdmsm_fr_domain_divide_by_z(amdmsm_ctx *ctx, int curve, size_t m, const void *values, const void *coset,
+                                 const amdmsm_opts *opts, void *out);
+int amdmsm_fr_domain_divide_by_z_device(amdmsm_ctx *ctx, int curve, size_t m, const void *d_values, const void *coset,
+                                        const amdmsm_opts *opts, void *d_out);
 
 /* Sparse matrix times Fr vector -- the rows <A_i, z>, <B_i, z>, <C_i, z> of a constraint system on a resident
  * assignment, the vectors the transforms above start from -- and any other sparse linear map over Fr:

@@ -163,7 +163,7 @@ struct amdmsm_ctx {
     size_t call_marks = 0;
     long long call_ticket = -1;
     float aux_ms[4] = {};
-    fr_tw_entry fr_tw[2];                         // a prover alternates omega and omega^-1 over one domain
+    fr_tw_entry fr_tw[4];                         // a prover alternates omega and omega^-1; a step domain has two transforms each way
     uint64_t fr_clock = 0;
     std::vector<fr_matrix *> fr_mats;
     std::string err;
@@ -3921,6 +3921,7 @@ size_t frfft_ws_bytes(const frfft_plan &p, bool in_place) { return frfft_third(p
 // what a call is given, as Montgomery residues
 struct frfft_params {
     bool plain = false, has_pre = false, has_post = false, has_scale = false;
+    bool mont_in = false, mont_out = false;   // plain: the records of this end are Montgomery residues all the same (a step domain's sweeps convert)
     fr_rec omega, pre, post, scale;
 };
 
@@ -3955,7 +3956,7 @@ int frfft_check(amdmsm_ctx *ctx, const fr_vtable *f, const void *values, size_t 
     return AMDMSM_OK;
 }
 
-// the n / 2 powers of omega, from the context's two most recent or built now; the caller records e->ev when it is done
+// the n / 2 powers of omega, from the context's four most recent or built now; the caller records e->ev when it is done
 int frfft_twiddles(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, size_t n, const frfft_params &pr, fr_tw_entry *&e) {
     fr_tw_entry *hit = nullptr, *lru = &ctx->fr_tw[0];
     for (auto &t : ctx->fr_tw) {
@@ -4024,8 +4025,8 @@ int frfft_run(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, const frfft_p
         a.log_r = t;
         a.log_s = log_s;
         a.log_c = std::min(FR_LDS_LOG2 - t, p.log_n - t);
-        a.in_plain = first && pr.plain;
-        a.out_plain = last && pr.plain;
+        a.in_plain = first && pr.plain && !pr.mont_in;
+        a.out_plain = last && pr.plain && !pr.mont_out;
         a.has_scale = last && pr.has_scale && !pr.has_post;
         memcpy(a.scale, pr.scale.v, sizeof(a.scale));
         f->pass(st, a);
@@ -4670,6 +4671,527 @@ int amdmsm_fr_batch_invert_device(amdmsm_ctx *ctx, int curve, size_t n, const vo
 int amdmsm_fr_batch_invert(amdmsm_ctx *ctx, int curve, size_t n, const void *values, const amdmsm_opts *opts, void *out,
                            uint64_t *zero_count) {
     return frs_host_entry(ctx, curve, n, values, nullptr, nullptr, nullptr, 0, 0, opts, out, zero_count, true);
+}
+
+}  // extern "C"
+
+// ---- evaluation domains over Fr: libfqfft's choice, transforms over the step radix-2 domain, division by Z --------
+namespace {
+
+// a - b mod r, both canonical
+fr_rec fr_sub_host(const fr_vtable *f, const fr_rec &a, const fr_rec &b) {
+    fr_rec d;
+    uint64_t borrow = 0;
+    for (int j = 0; j < f->words; ++j) {
+        const uint64_t w = (uint64_t)a.v[j] - b.v[j] - borrow;
+        d.v[j] = (uint32_t)w;
+        borrow = (w >> 63) & 1u;
+    }
+    if (!borrow) return d;
+    uint64_t carry = 0;
+    for (int j = 0; j < f->words; ++j) {
+        const uint64_t w = (uint64_t)d.v[j] + f->modulus[j] + carry;
+        d.v[j] = (uint32_t)w;
+        carry = w >> 32;
+    }
+    return d;
+}
+fr_rec fr_one(const fr_vtable *f) { return fr_from_words(f, f->one); }
+fr_rec fr_neg_host(const fr_vtable *f, const fr_rec &a) { return fr_sub_host(f, fr_rec(), a); }
+fr_rec fr_pow_host(const fr_vtable *f, fr_rec x, size_t e) {
+    fr_rec acc = fr_one(f);
+    for (; e; e >>= 1) {
+        if (e & 1u) acc = fr_mul(f, acc, x);
+        x = fr_mul(f, x, x);
+    }
+    return acc;
+}
+fr_rec fr_sqr_times(const fr_vtable *f, fr_rec x, int k) {
+    for (int b = 0; b < k; ++b) x = fr_mul(f, x, x);
+    return x;
+}
+// the integer k as a Montgomery residue
+fr_rec fr_mont_small(const fr_vtable *f, uint32_t k) { return fr_mul(f, fr_small(k), fr_from_words(f, f->r2)); }
+bool fr_is_zero(const fr_vtable *f, const fr_rec &a) { return fr_same(f, a, fr_rec()); }
+// libff's get_root_of_unity(2^log2_n), Montgomery
+fr_rec fr_root_host(const fr_vtable *f, int log2_n) { return fr_sqr_times(f, fr_from_words(f, f->root), f->two_adicity - log2_n); }
+void fr_write(const fr_vtable *f, void *out, const fr_rec &x, bool plain) {
+    const fr_rec r = plain ? fr_from_mont(f, x) : x;
+    memcpy(out, r.v, (size_t)f->words * 4);
+}
+
+// A domain of m points: basic (S = 0, B = m, the points w^j, w = root(m)) or step (m = B + S: w = root(2 B), the points
+// w^(2 j), j < B, then w sigma^(j - B), sigma = root(S))
+struct frdom {
+    bool step = false;
+    size_t m = 0, B = 0, S = 0;
+    int log_b = 0, log_s = 0, log_w = 0;   // log_w: log2 of the order of w
+};
+
+// libfqfft's get_evaluation_domain(min_size) as far as it ends in one of the two domains above; `why`: what went wrong
+int frdom_choose(const fr_vtable *f, size_t min_size, frdom &d, std::string &why) {
+    if (min_size < 2) {
+        why = "min_size = " + std::to_string(min_size) + ": a domain has at least 2 points";
+        return AMDMSM_ERR_BAD_ARG;
+    }
+    const std::string large = ": a domain of at most 2^28 points";
+    if (min_size > FR_FFT_MAX_N) {
+        why = "min_size = " + std::to_string(min_size) + large;
+        return AMDMSM_ERR_TOO_LARGE;
+    }
+    const int lg = log2_exact(min_size);
+    const size_t big = (size_t)1 << (lg - 1), small = min_size - big, rounded = (size_t)1 << log2_exact(small);
+    d = frdom();
+    if (!(min_size & (min_size - 1))) {
+        d.m = min_size;
+    } else if (!(small & (small - 1))) {
+        d.step = true;
+        d.m = min_size;
+    } else if (!((big + rounded) & (big + rounded - 1))) {
+        d.m = big + rounded;
+    } else {
+        d.step = true;
+        d.m = big + rounded;
+    }
+    if (d.m > FR_FFT_MAX_N) {
+        why = "m = " + std::to_string(d.m) + large;
+        return AMDMSM_ERR_TOO_LARGE;
+    }
+    if (d.step) {
+        d.B = big;
+        d.S = d.m - big;
+        d.log_b = lg - 1;
+        d.log_s = log2_exact(d.S);
+        d.log_w = lg;
+    } else {
+        d.B = d.m;
+        d.log_b = d.log_w = log2_exact(d.m);
+    }
+    if (d.log_w > f->two_adicity) {
+        // libfqfft goes on: the extended radix-2 domain serves 2^(s + 1) alone, everything else above 2^s is geometric
+        const bool extended = !d.step && d.log_w == f->two_adicity + 1;
+        why = "m = " + std::to_string(d.m) + ": beyond the 2-adicity " + std::to_string(f->two_adicity) + " of r - 1 libfqfft uses its " +
+              (extended ? "extended radix-2" : "geometric sequence") + " domain, which is left out";
+        return AMDMSM_ERR_UNSUPPORTED;
+    }
+    return AMDMSM_OK;
+}
+// the domain of exactly m points, or why there is none
+int frdom_exact(const fr_vtable *f, size_t m, frdom &d, std::string &why) {
+    const int rc = frdom_choose(f, m, d, why);
+    if (rc || d.m == m) return rc;
+    why = "m = " + std::to_string(m) + " is not a domain size: amdmsm_fr_domain chooses " + std::to_string(d.m) + " points for it";
+    return AMDMSM_ERR_BAD_ARG;
+}
+
+// Workspace of a transform: the passes' own (in place, the larger of the two transforms), two vectors of partial sums
+// that take turns -- at most B / 16 and B / 1024 records (frd_iters) -- the S sums of the inverse, and the two tables of
+// the coset's powers.  A basic domain has the passes' alone.
+struct frdom_plan {
+    frdom d;
+    frfft_plan pb, ps;
+    size_t rec = 0, off_pa = 0, off_pb = 0, off_sums = 0, off_glo = 0, off_ghi = 0, ws_bytes = 0;
+};
+int frdom_make_plan(const fr_vtable *f, const frdom &d, int tile_log2, frdom_plan &p) {
+    p.d = d;
+    p.rec = (size_t)f->words * 4;
+    if (frfft_make_plan(f, d.B, tile_log2, p.pb)) return AMDMSM_ERR_BAD_ARG;
+    if (!d.step) {
+        p.ws_bytes = frfft_ws_bytes(p.pb, true);
+        return AMDMSM_OK;
+    }
+    frfft_make_plan(f, d.S, tile_log2, p.ps);
+    p.off_pa = std::max(frfft_ws_bytes(p.pb, true), frfft_ws_bytes(p.ps, true));
+    p.off_pb = p.off_pa + align_up(std::max<size_t>(1, d.B >> 4) * p.rec, 256);
+    p.off_sums = p.off_pb + align_up(std::max<size_t>(1, d.B >> 10) * p.rec, 256);
+    p.off_glo = p.off_sums + align_up(d.S * p.rec, 256);
+    p.off_ghi = p.off_glo + align_up(((size_t)1 << FRD_LO_LOG2) * p.rec, 256);
+    p.ws_bytes = p.off_ghi + align_up(((d.m >> FRD_LO_LOG2) + 1) * p.rec, 256);
+    return AMDMSM_OK;
+}
+
+// what a transform runs with, Montgomery residues: w, the coset shift (its inverse for the inverse transform), 1 / 2, and
+// the parameters of the radix-2 transforms in between
+struct frdom_params {
+    bool plain = false, inverse = false, has_g = false;
+    fr_rec w, g, half;
+    frfft_params prb, prs;
+};
+
+// The argument rules of both transform entries; nothing is launched or written and the context is not looked at before
+// they hold.  device: the vectors are HBM addresses
+int frdom_check(amdmsm_ctx *ctx, const fr_vtable *f, const void *values, size_t m, int flags, const void *coset, int tile_log2,
+                const amdmsm_opts *opts, const void *out, bool device, frdom_plan &p, frdom_params &q) {
+    frdom d;
+    std::string why;
+    int rc = frdom_exact(f, m, d, why);
+    if (rc) return fail(ctx, rc, why);
+    if (flags & ~AMDMSM_DOMAIN_INVERSE) return fail(ctx, AMDMSM_ERR_BAD_ARG, "flags = " + std::to_string(flags) + ": unknown bits");
+    if (frdom_make_plan(f, d, tile_log2, p))
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "tile_log2 = " + std::to_string(tile_log2) + ": 0 or " + std::to_string(FR_TILE_MIN) +
+                                                 " .. " + std::to_string(FR_TILE_MAX));
+    if (!values) return fail(ctx, AMDMSM_ERR_BAD_ARG, "values: null pointer");
+    if (!out) return fail(ctx, AMDMSM_ERR_BAD_ARG, "output: null pointer");
+    if (device) {
+        rc = fr_check_aligned(ctx, f, "d_values / d_out", {values, out});
+        if (!rc) rc = fr_check_apart(ctx, "d_values", values, m * p.rec, "d_out", out, m * p.rec);
+        if (rc) return rc;
+    }
+    q.plain = opts && opts->scalars_plain;
+    q.inverse = (flags & AMDMSM_DOMAIN_INVERSE) != 0;
+    if (coset && !fr_below_modulus(f, (const uint32_t *)coset)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "coset: not below r");
+    q.has_g = coset != nullptr;
+    if (coset) q.g = fr_read(f, coset, q.plain);
+    if (q.has_g && fr_is_zero(f, q.g)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "coset: zero");
+    if (q.has_g && q.inverse) q.g = fr_inv_host(f, q.g);
+    q.w = fr_root_host(f, d.log_w);
+    q.half = fr_inv_host(f, fr_mont_small(f, 2));
+    // the radix-2 transforms: a basic domain takes the coset as pre / post, a step domain's sweeps apply it and hold
+    // Montgomery residues between themselves and the passes
+    const fr_rec wi = q.inverse ? fr_inv_host(f, q.w) : q.w;
+    q.prb.plain = q.prs.plain = q.plain;
+    if (!d.step) {
+        q.prb.omega = wi;
+        q.prb.has_pre = q.has_g && !q.inverse && m > 1;
+        q.prb.has_post = q.has_g && q.inverse && m > 1;
+        q.prb.pre = q.prb.post = q.g;
+    } else {
+        q.prb.omega = fr_mul(f, wi, wi);
+        q.prs.omega = fr_sqr_times(f, wi, d.log_w - d.log_s);
+        q.prb.mont_in = q.prs.mont_in = !q.inverse;
+        q.prb.mont_out = q.prs.mont_out = q.inverse;
+    }
+    q.prb.scale = q.prs.scale = fr_one(f);
+    if (q.inverse) {
+        q.prb.has_scale = true;
+        q.prb.scale = fr_inv_host(f, fr_mont_small(f, (uint32_t)d.B));
+        q.prs.has_scale = d.step;
+        if (d.step) q.prs.scale = fr_inv_host(f, fr_mont_small(f, (uint32_t)d.S));
+    }
+    return AMDMSM_OK;
+}
+
+// the sweep over the K x S matrix and, launch after launch, over the rows of partial sums it leaves; the last launch
+// writes the S sums to `final`
+void frdom_sweeps(const fr_vtable *f, hipStream_t st, const frdom_plan &p, frd_sweep a, uint32_t *final, char *ws) {
+    uint32_t *turn[2] = {(uint32_t *)(ws + p.off_pa), (uint32_t *)(ws + p.off_pb)};
+    a.log_b = p.d.log_b;
+    a.log_s = p.d.log_s;
+    a.log_w = std::min(p.d.log_s, FRD_TILE_LOG2);
+    a.rows = (uint32_t)(p.d.B >> p.d.log_s);
+    a.iters = frd_iters(a.log_w);
+    for (int k = 0;; k ^= 1) {
+        const uint32_t per = (256u >> a.log_w) * a.iters, left = (a.rows + per - 1) / per;
+        a.sums = left == 1 ? final : turn[k];
+        f->domain_sweep(st, a);
+        if (left == 1) return;
+        a.in = a.sums;
+        a.mode = FRD_REDUCE;
+        a.rows = left;
+        a.iters = FRD_ITERS_REDUCE;
+    }
+}
+
+// The transform on device-resident vectors, d_out == d_in or apart; ws: frdom_plan's workspace.  Phase 0 builds every
+// table of powers the call reads, phase 1 is the sweeps and the passes.
+int frdom_run(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, const frdom_plan &p, const frdom_params &q, const uint32_t *d_in,
+              uint32_t *d_out, char *ws) {
+    const frdom &d = p.d;
+    if (!d.step) return frfft_run(ctx, f, st, p.pb, q.prb, d_in, d_out, d.m, ws);
+    const size_t nw = (size_t)f->words;
+    fr_tw_entry *tw = nullptr, *pre = nullptr;
+    frfft_params pw;
+    pw.omega = q.w;
+    int rc = frfft_twiddles(ctx, f, st, 2 * d.B, pw, tw);   // the B powers of w: the fold's and the merge's factors
+    // the passes' own powers now, so that they fall into phase 0; frfft_run finds them again
+    if (!rc && d.B > 1) rc = frfft_twiddles(ctx, f, st, d.B, q.prb, pre);
+    if (!rc && d.S > 1) rc = frfft_twiddles(ctx, f, st, d.S, q.prs, pre);
+    if (rc) return rc;
+    uint32_t *g_lo = nullptr, *g_hi = nullptr;
+    if (q.has_g) {
+        g_lo = (uint32_t *)(ws + p.off_glo);
+        g_hi = (uint32_t *)(ws + p.off_ghi);
+        f->powers(st, fr_pow_table(f, q.g, 0).data(), nullptr, 0, (size_t)1 << FRD_LO_LOG2, g_lo);
+        f->powers(st, fr_pow_table(f, q.g, FRD_LO_LOG2).data(), nullptr, 0, (d.m >> FRD_LO_LOG2) + 1, g_hi);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    call_mark(ctx, st, 1);
+    frd_sweep a = {};
+    a.tw = (const uint32_t *)tw->buf.p;
+    a.g_lo = g_lo;
+    a.g_hi = g_hi;
+    a.plain = q.plain ? 1 : 0;
+    uint32_t *hi = d_out + d.B * nw;
+    if (!q.inverse) {
+        // c to d_out[0 .. B) -- a lane reads the records i and B + i before it writes record i, and no other lane reads
+        // them, so d_out may be d_in -- the sums e to d_out[B .. m), then both transforms in place
+        a.mode = FRD_FOLD;
+        a.in = d_in;
+        a.out = d_out;
+        a.store = (d_in != d_out || q.plain || q.has_g) ? 1 : 0;
+        frdom_sweeps(f, st, p, a, hi, ws);
+        HIP_TRY(ctx, hipGetLastError());
+        rc = frfft_run(ctx, f, st, p.pb, q.prb, d_out, d_out, d.B, ws);
+        if (!rc) rc = frfft_run(ctx, f, st, p.ps, q.prs, hi, hi, d.S, ws);
+        if (rc) return rc;
+    } else {
+        rc = frfft_run(ctx, f, st, p.pb, q.prb, d_in, d_out, d.B, ws);
+        if (!rc) rc = frfft_run(ctx, f, st, p.ps, q.prs, d_in + d.B * nw, hi, d.S, ws);
+        if (rc) return rc;
+        uint32_t *sums = (uint32_t *)(ws + p.off_sums);
+        a.mode = FRD_MERGE;
+        a.in = d_out;
+        a.out = d_out;
+        a.store = (q.plain || q.has_g) ? 1 : 0;
+        frdom_sweeps(f, st, p, a, sums, ws);
+        frd_combine c = {};
+        c.out = d_out;
+        c.sums = sums;
+        c.tw = a.tw;
+        c.g_lo = g_lo;
+        c.g_hi = g_hi;
+        c.log_b = d.log_b;
+        c.log_s = d.log_s;
+        c.plain = a.plain;
+        memcpy(c.half, q.half.v, sizeof(c.half));
+        f->domain_combine(st, c);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(tw->ev, st));
+    return AMDMSM_OK;
+}
+
+// ---- division by Z on the coset g D: out[j] = values[j] / Z(g x_j) --------------------------------------------------------
+// Step domain: below B the denominator (g^B - 1) (g^S rho^j - w^S), rho = w^(2 S) of order K, takes K values -- built as
+// powers of rho, inverted by the batch inversion of section 20 and indexed by j mod K; from B on it is the one value
+// -(g^B + 1) w^S (g^S - 1), inverted here.  Basic domain: g^m - 1 throughout.
+struct frdiv_call {
+    frdom d;
+    size_t rec = 0, K = 0, off_scan = 0, ws_bytes = 0;
+    bool plain = false;
+    fr_rec rho, first, sub, tail;   // den[k] = first rho^k - sub
+    frs_call inv;
+};
+int frdiv_check(amdmsm_ctx *ctx, const fr_vtable *f, size_t m, const void *values, const void *coset, const amdmsm_opts *opts,
+                const void *out, bool device, frdiv_call &c) {
+    std::string why;
+    int rc = frdom_exact(f, m, c.d, why);
+    if (rc) return fail(ctx, rc, why);
+    c.rec = (size_t)f->words * 4;
+    if (!values) return fail(ctx, AMDMSM_ERR_BAD_ARG, "values: null pointer");
+    if (!out) return fail(ctx, AMDMSM_ERR_BAD_ARG, "output: null pointer");
+    if (!coset) return fail(ctx, AMDMSM_ERR_BAD_ARG, "coset: null pointer (Z is zero on the domain itself)");
+    if (device) {
+        rc = fr_check_aligned(ctx, f, "d_values / d_out", {values, out});
+        if (!rc) rc = fr_check_apart(ctx, "d_values", values, m * c.rec, "d_out", out, m * c.rec);
+        if (rc) return rc;
+    }
+    c.plain = opts && opts->scalars_plain;
+    if (!fr_below_modulus(f, (const uint32_t *)coset)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "coset: not below r");
+    const frdom &d = c.d;
+    const fr_rec g = fr_read(f, coset, c.plain), one = fr_one(f);
+    const fr_rec gb = fr_pow_host(f, g, d.B);
+    const size_t order = d.step ? 2 * d.B : d.m;
+    if (fr_same(f, fr_pow_host(f, g, order), one))
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "coset: g^" + std::to_string(order) + " = 1, Z has a zero on the coset");
+    if (!d.step) {
+        c.tail = fr_inv_host(f, fr_sub_host(f, gb, one));
+        return AMDMSM_OK;
+    }
+    c.K = d.B >> d.log_s;
+    const fr_rec w = fr_root_host(f, d.log_w), ws = fr_pow_host(f, w, d.S), gs = fr_pow_host(f, g, d.S);
+    const fr_rec lead = fr_sub_host(f, gb, one);
+    c.rho = fr_mul(f, ws, ws);
+    c.first = fr_mul(f, lead, gs);
+    c.sub = fr_mul(f, lead, ws);
+    // (g w sigma^t)^B - 1 = -g^B - 1 and (g w sigma^t)^S - w^S = w^S (g^S - 1)
+    const fr_rec tail = fr_mul(f, fr_neg_host(f, fr_sub_host(f, gb, fr_neg_host(f, one))), fr_mul(f, ws, fr_sub_host(f, gs, one)));
+    c.tail = fr_inv_host(f, tail);
+    // the K denominators and their inversion in place, Montgomery residues whatever the caller's records are
+    c.inv.rec = c.rec;
+    c.inv.invert = true;
+    c.inv.naive = frs_naive_env();
+    c.inv.has_a = 1;
+    frs_make_layout(c.K, 0, c.rec, true, c.inv.naive, c.inv.L);
+    c.off_scan = align_up(c.K * c.rec, 256);
+    c.ws_bytes = c.off_scan + c.inv.L.ws_bytes;
+    return AMDMSM_OK;
+}
+int frdiv_run(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, const frdiv_call &c, const uint32_t *d_in, uint32_t *d_out, char *ws) {
+    const frdom &d = c.d;
+    uint32_t *den = (uint32_t *)ws;
+    if (d.step) {
+        f->powers(st, fr_pow_table(f, c.rho, 0).data(), c.first.v, 0, c.K, den);
+        f->domain_den(st, c.K, den, c.sub.v);
+        HIP_TRY(ctx, hipGetLastError());
+        const int rc = frs_run(ctx, f, st, c.inv, c.K, den, nullptr, den, nullptr, ws + c.off_scan);   // marks phase 1
+        if (rc) return rc;
+    } else {
+        call_mark(ctx, st, 1);
+    }
+    f->domain_divide(st, d.m, d.step ? d.B : 0, c.K, d_in, den, c.tail.v, d_out);
+    HIP_TRY(ctx, hipGetLastError());
+    return AMDMSM_OK;
+}
+
+}   // namespace
+
+extern "C" {
+
+int amdmsm_fr_domain(int curve, size_t min_size, size_t out[6]) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return AMDMSM_ERR_UNSUPPORTED;
+    if (!out) return AMDMSM_ERR_BAD_ARG;
+    frdom d;
+    std::string why;
+    const int rc = frdom_choose(f, min_size, d, why);
+    if (rc) return rc;
+    frdom_plan p;
+    frdom_make_plan(f, d, 0, p);
+    out[0] = d.step ? AMDMSM_DOMAIN_STEP_RADIX2 : AMDMSM_DOMAIN_BASIC_RADIX2;
+    out[1] = d.m;
+    out[2] = d.B;
+    out[3] = d.S;
+    out[4] = (size_t)d.log_w;
+    out[5] = p.ws_bytes;
+    return AMDMSM_OK;
+}
+
+int amdmsm_fr_domain_element(int curve, size_t m, size_t idx, int plain, void *out) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return AMDMSM_ERR_UNSUPPORTED;
+    frdom d;
+    std::string why;
+    const int rc = frdom_exact(f, m, d, why);
+    if (rc) return rc;
+    if (!out || idx >= m) return AMDMSM_ERR_BAD_ARG;
+    const fr_rec w = fr_root_host(f, d.log_w);
+    fr_rec x;
+    if (!d.step) x = fr_pow_host(f, w, idx);
+    else if (idx < d.B) x = fr_pow_host(f, w, 2 * idx);
+    else x = fr_mul(f, w, fr_pow_host(f, fr_root_host(f, d.log_s), idx - d.B));
+    fr_write(f, out, x, plain != 0);
+    return AMDMSM_OK;
+}
+
+int amdmsm_fr_domain_vanishing(int curve, size_t m, const void *t, int plain, void *out) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return AMDMSM_ERR_UNSUPPORTED;
+    frdom d;
+    std::string why;
+    const int rc = frdom_exact(f, m, d, why);
+    if (rc) return rc;
+    if (!t || !out || !fr_below_modulus(f, (const uint32_t *)t)) return AMDMSM_ERR_BAD_ARG;
+    const fr_rec x = fr_read(f, t, plain != 0), one = fr_one(f);
+    fr_rec z = fr_sub_host(f, fr_pow_host(f, x, d.B), one);
+    if (d.step) z = fr_mul(f, z, fr_sub_host(f, fr_pow_host(f, x, d.S), fr_pow_host(f, fr_root_host(f, d.log_w), d.S)));
+    fr_write(f, out, z, plain != 0);
+    return AMDMSM_OK;
+}
+
+int amdmsm_fr_domain_z_terms(int curve, size_t m, int plain, size_t idx[4], void *coeffs, int *count) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return AMDMSM_ERR_UNSUPPORTED;
+    frdom d;
+    std::string why;
+    const int rc = frdom_exact(f, m, d, why);
+    if (rc) return rc;
+    if (!idx || !coeffs || !count) return AMDMSM_ERR_BAD_ARG;
+    const fr_rec one = fr_one(f), minus_one = fr_neg_host(f, one);
+    const size_t rec = (size_t)f->words * 4;
+    char *c = (char *)coeffs;
+    if (!d.step) {   // X^m - 1
+        idx[0] = m;
+        idx[1] = 0;
+        fr_write(f, c, one, plain != 0);
+        fr_write(f, c + rec, minus_one, plain != 0);
+        *count = 2;
+        return AMDMSM_OK;
+    }
+    // (X^B - 1) (X^S - w^S) = X^(B+S) - w^S X^B - X^S + w^S
+    const fr_rec ws = fr_pow_host(f, fr_root_host(f, d.log_w), d.S);
+    idx[0] = d.B + d.S;
+    idx[1] = d.B;
+    idx[2] = d.S;
+    idx[3] = 0;
+    fr_write(f, c, one, plain != 0);
+    fr_write(f, c + rec, fr_neg_host(f, ws), plain != 0);
+    fr_write(f, c + 2 * rec, minus_one, plain != 0);
+    fr_write(f, c + 3 * rec, ws, plain != 0);
+    *count = 4;
+    return AMDMSM_OK;
+}
+
+int amdmsm_fr_multiplicative_generator(int curve, int plain, void *out) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return AMDMSM_ERR_UNSUPPORTED;
+    if (!out) return AMDMSM_ERR_BAD_ARG;
+    fr_write(f, out, fr_from_words(f, f->generator), plain != 0);
+    return AMDMSM_OK;
+}
+
+int amdmsm_fr_domain_fft_device(amdmsm_ctx *ctx, int curve, const void *d_values, size_t m, int flags, const void *coset,
+                                int tile_log2, const amdmsm_opts *opts, void *d_out) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
+    CHECK_OPTS(ctx, opts);
+    frdom_plan p;
+    frdom_params q;
+    const int rc = frdom_check(ctx, f, d_values, m, flags, coset, tile_log2, opts, d_out, true, p, q);
+    if (rc) return rc;
+    FR_ENTER(ctx);
+    hipStream_t st = stream_of(ctx, opts);
+    return fr_call(ctx, st, 0, p.ws_bytes, {}, {}, [&](char *, char *ws) {
+        return frdom_run(ctx, f, st, p, q, (const uint32_t *)d_values, (uint32_t *)d_out, ws);
+    });
+}
+
+int amdmsm_fr_domain_fft(amdmsm_ctx *ctx, int curve, const void *values, size_t m, int flags, const void *coset, int tile_log2,
+                         const amdmsm_opts *opts, void *out) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
+    CHECK_OPTS(ctx, opts);
+    frdom_plan p;
+    frdom_params q;
+    const int rc = frdom_check(ctx, f, values, m, flags, coset, tile_log2, opts, out, false, p, q);
+    if (rc) return rc;
+    FR_ENTER(ctx);
+    hipStream_t st = ctx->stream;
+    // one staged vector; the transform runs in place on it
+    const size_t vec = align_up(m * p.rec, 256);
+    return fr_call(ctx, st, vec, p.ws_bytes, {{values, 0, m * p.rec}}, {{out, 0, m * p.rec}}, [&](char *v, char *ws) {
+        return frdom_run(ctx, f, st, p, q, (const uint32_t *)v, (uint32_t *)v, ws);
+    });
+}
+
+int amdmsm_fr_domain_divide_by_z_device(amdmsm_ctx *ctx, int curve, size_t m, const void *d_values, const void *coset,
+                                        const amdmsm_opts *opts, void *d_out) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
+    CHECK_OPTS(ctx, opts);
+    frdiv_call c;
+    const int rc = frdiv_check(ctx, f, m, d_values, coset, opts, d_out, true, c);
+    if (rc) return rc;
+    FR_ENTER(ctx);
+    hipStream_t st = stream_of(ctx, opts);
+    return fr_call(ctx, st, 0, std::max<size_t>(c.ws_bytes, 256), {}, {}, [&](char *, char *ws) {
+        return frdiv_run(ctx, f, st, c, (const uint32_t *)d_values, (uint32_t *)d_out, ws);
+    });
+}
+
+int amdmsm_fr_domain_divide_by_z(amdmsm_ctx *ctx, int curve, size_t m, const void *values, const void *coset,
+                                 const amdmsm_opts *opts, void *out) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
+    CHECK_OPTS(ctx, opts);
+    frdiv_call c;
+    const int rc = frdiv_check(ctx, f, m, values, coset, opts, out, false, c);
+    if (rc) return rc;
+    FR_ENTER(ctx);
+    hipStream_t st = ctx->stream;
+    const size_t vec = align_up(m * c.rec, 256);
+    return fr_call(ctx, st, vec, std::max<size_t>(c.ws_bytes, 256), {{values, 0, m * c.rec}}, {{out, 0, m * c.rec}},
+                   [&](char *v, char *ws) { return frdiv_run(ctx, f, st, c, (const uint32_t *)v, (uint32_t *)v, ws); });
 }
 
 }  // extern "C"

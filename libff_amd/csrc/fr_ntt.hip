@@ -1,6 +1,6 @@
 // Scalar-field translation unit: the radix-2 FFT over a vector of Fr records, the powers of an Fr element, the
-// element-wise product step between transforms, the sparse matrix times vector (fr_matrix.inc) and the scans and batch
-// inversion (fr_scan.inc).  Compiled once per curve:
+// element-wise product step between transforms, the sparse matrix times vector (fr_matrix.inc), the scans and batch
+// inversion (fr_scan.inc) and the sweeps of the step radix-2 domains (fr_domain.inc).  Compiled once per curve:
 //   -DAMDMSM_FR=<curve>_fr -DAMDMSM_FR_VT=frvt_<curve> -DAMDMSM_FR_CURVE=<curve id>
 // (libff_amd/build.py).  The host side -- plan, argument rules, parameter arithmetic, twiddle cache -- is engine.cpp;
 // DESIGN section 18 has the pass structure, the LDS layout and the measurements.
@@ -197,6 +197,9 @@ __global__ void __launch_bounds__(TPB) k_fr_muladd(size_t n, const uint32_t* a, 
 // ---- scans and batch inversion ----------------------------------------------------------------------------------------
 #include "fr_scan.inc"
 
+// ---- step radix-2 domains: the fold in front of the passes, the merge behind them, the division by Z ----------------
+#include "fr_domain.inc"
+
 // ---- launchers ------------------------------------------------------------------------------------------------------
 void l_pass(hipStream_t st, const fr_pass& a) {
     const unsigned tiles = 1u << (a.log_n - a.log_r - a.log_c);
@@ -228,6 +231,7 @@ void l_muladd(hipStream_t st, size_t n, const uint32_t* d_a, const uint32_t* d_b
 const fr_vtable g_frvt = {
     AMDMSM_FR_CURVE, N, FR::SQRT_S, FR::INV, FR::P, FR::R, FR::R2, FR::ROOT_OF_UNITY, l_powers, l_pass, l_muladd,
     FRM_T, l_matrix_apply, l_matrix_naive, l_scan, l_scan_naive,
+    FR::MULT_GENERATOR, l_domain_sweep, l_domain_combine, l_domain_den, l_domain_divide,
 };
 
 }  // namespace

@@ -62,6 +62,35 @@ struct frs_args {
     uint32_t a_const[FR_MAX_WORDS], init[FR_MAX_WORDS];   // Montgomery
 };
 
+// one sweep over the K x S matrix of a step-domain transform, m = B + S, K = B / S (k_frd_sweep, fr_domain.inc): a
+// workgroup takes 2^log_w columns and (256 >> log_w) * iters rows and leaves one row of partial sums
+constexpr int FRD_FOLD = 0, FRD_MERGE = 1, FRD_REDUCE = 2;
+constexpr int FRD_LO_LOG2 = 10;        // g^i = g_lo[i mod 2^10] * g_hi[i >> 10]
+constexpr int FRD_TILE_LOG2 = 8;       // columns of a workgroup at the most (log2): one lane each
+// Rows a lane walks.  A tile is 256 * iters records and leaves 2^log_w sums, partial sums that are written and read
+// once more: 1 / ((256 >> log_w) * iters) of the records -- a sixteenth where a lane has a column to itself, a
+// thousandth where the 256 lanes share one -- and the shorter walk gives the many-row tiles four times the workgroups
+constexpr uint32_t FRD_ITERS_REDUCE = 64;
+inline uint32_t frd_iters(int log_w) { return log_w >= 7 ? 16 : (log_w >= 5 ? 8 : 4); }
+struct frd_sweep {
+    const uint32_t* in;          // fold: the m input records; merge: U0 | U1, the output vector; reduce: rows x S partial sums
+    uint32_t* out;               // fold: c_i to out[i]; merge: a_i to out[i], rows 1 .. K - 1 (may be in)
+    uint32_t* sums;              // ceil(rows / ((256 >> log_w) * iters)) rows of S sums
+    const uint32_t* tw;          // the B powers of w, Montgomery (fold, merge)
+    const uint32_t *g_lo, *g_hi; // a coset: the powers of g (fold) or of 1 / g (merge), else null
+    int log_b, log_s, log_w, mode;
+    uint32_t rows, iters;
+    int plain;                   // fold: the input is plain; merge: the output is
+    int store;                   // rows 1 .. K - 1 are written: the records change or go to another vector
+};
+// row 0 of the inverse (k_frd_combine): out[i], out[B + i], i < S, from U0_i, U1_i and the sums
+struct frd_combine {
+    uint32_t* out;
+    const uint32_t *sums, *tw, *g_lo, *g_hi;
+    int log_b, log_s, plain;
+    uint32_t half[FR_MAX_WORDS];   // 1 / 2, Montgomery
+};
+
 struct fr_vtable {
     int curve, words, two_adicity;
     uint32_t inv;                                  // -r^-1 mod 2^32
@@ -82,6 +111,15 @@ struct fr_vtable {
     void (*scan)(hipStream_t, const frs_args&);
     // the same by one lane that walks the vector: AMDMSM_FR_SCAN_NAIVE=1
     void (*scan_naive)(hipStream_t, const frs_args&);
+    // step radix-2 domains (fr_domain.inc): libff's Fr::multiplicative_generator (Montgomery), the fold / merge / partial-sum
+    // sweep, row 0 of the inverse, d_den[k] -= c (c: a host record), and d_out[j] = d_in[j] * (j < B ? d_inv[j mod K] : tail)
+    // for j < m (tail: a host record; B = 0: tail throughout)
+    const uint32_t* generator;
+    void (*domain_sweep)(hipStream_t, const frd_sweep&);
+    void (*domain_combine)(hipStream_t, const frd_combine&);
+    void (*domain_den)(hipStream_t, size_t n, uint32_t* d_den, const uint32_t* c);
+    void (*domain_divide)(hipStream_t, size_t m, size_t B, size_t K, const uint32_t* d_in, const uint32_t* d_inv, const uint32_t* tail,
+                          uint32_t* d_out);
 };
 
 const fr_vtable* frvt_alt_bn128() __attribute__((weak));

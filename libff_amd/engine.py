@@ -72,6 +72,9 @@ EXPORTED_SYMBOLS = [
     "amdmsm_fr_matrix_free",
     "amdmsm_fr_scan", "amdmsm_fr_scan_device", "amdmsm_fr_batch_invert", "amdmsm_fr_batch_invert_device", "amdmsm_plan_fr_scan",
     "amdmsm_fr_inverse",
+    "amdmsm_fr_domain", "amdmsm_fr_domain_element", "amdmsm_fr_domain_vanishing", "amdmsm_fr_domain_z_terms",
+    "amdmsm_fr_multiplicative_generator", "amdmsm_fr_domain_fft", "amdmsm_fr_domain_fft_device",
+    "amdmsm_fr_domain_divide_by_z", "amdmsm_fr_domain_divide_by_z_device",
 ]
 SEG_SHARED_BASES = 1            # include/amdmsm.h AMDMSM_SEG_SHARED_BASES
 SEG_LONG_NEVER = 2 ** 64 - 1    # long_from = SIZE_MAX: no segment takes the single-MSM route
@@ -397,6 +400,79 @@ def fr_inverse(curve, x, plain=True):
     rc = load_library().amdmsm_fr_inverse(curve, _np_ptr(src), int(bool(plain)), _np_ptr(out))
     if rc:
         raise ValueError(f"amdmsm_fr_inverse: {rc} (x = 0 or x >= r)")
+    return int.from_bytes(out.tobytes(), "little")
+
+
+# include/amdmsm.h AMDMSM_DOMAIN_*
+DOMAIN_BASIC_RADIX2, DOMAIN_STEP_RADIX2 = 0, 1
+DOMAIN_INVERSE = 1
+
+
+def _domain_error(what, rc):
+    err = AmdMsmError(f"{what}: {rc}")
+    err.code = rc   # the AMDMSM_ERR_* value of include/amdmsm.h
+    return err
+
+
+def fr_domain(curve, min_size):
+    """The evaluation domain libfqfft's ``get_evaluation_domain(min_size)`` chooses over Fr of the curve
+    (``amdmsm_fr_domain``, no device): ``kind`` (``DOMAIN_BASIC_RADIX2`` or ``DOMAIN_STEP_RADIX2``), its size ``m`` >=
+    min_size, ``B`` and ``S`` (m = B + S for a step domain; B = m and S = 0 for a basic one), ``omega_log2`` (log2 of the
+    order of the domain's root) and the workspace bytes of a device transform.  AmdMsmError with ``code`` -3 where
+    libfqfft would use a domain that is left out, -5 above 2^28 points, -2 below 2."""
+    out = (ctypes.c_size_t * 6)()
+    rc = load_library().amdmsm_fr_domain(curve, ctypes.c_size_t(int(min_size) if min_size >= 0 else 0), out)
+    if rc:
+        raise _domain_error("amdmsm_fr_domain", rc)
+    return {"kind": out[0], "m": out[1], "B": out[2], "S": out[3], "omega_log2": out[4], "workspace_bytes": out[5]}
+
+
+def _fr_host_int(curve, x):
+    limbs = _fr_limbs(curve)
+    x = int(x)
+    if x < 0 or x >> (64 * limbs):
+        raise ValueError("the value does not fit an Fr record")
+    return np.frombuffer(x.to_bytes(8 * limbs, "little"), dtype="<u8").astype(np.uint64)
+
+
+def fr_domain_element(curve, m, idx, plain=True):
+    """Element ``idx`` of the domain of ``m`` points (``amdmsm_fr_domain_element``), an int; ``plain=False``: its
+    Montgomery residue."""
+    out = np.zeros(_fr_limbs(curve), dtype=np.uint64)
+    rc = load_library().amdmsm_fr_domain_element(curve, ctypes.c_size_t(m), ctypes.c_size_t(idx), int(bool(plain)), _np_ptr(out))
+    if rc:
+        raise _domain_error("amdmsm_fr_domain_element", rc)
+    return int.from_bytes(out.tobytes(), "little")
+
+
+def fr_domain_vanishing(curve, m, t, plain=True):
+    """``Z(t)`` of the domain of ``m`` points (``amdmsm_fr_domain_vanishing``); ``t`` and the result ints in the form
+    ``plain`` says."""
+    src, out = _fr_host_int(curve, t), np.zeros(_fr_limbs(curve), dtype=np.uint64)
+    rc = load_library().amdmsm_fr_domain_vanishing(curve, ctypes.c_size_t(m), _np_ptr(src), int(bool(plain)), _np_ptr(out))
+    if rc:
+        raise _domain_error("amdmsm_fr_domain_vanishing", rc)
+    return int.from_bytes(out.tobytes(), "little")
+
+
+def fr_domain_z_terms(curve, m, plain=True):
+    """The vanishing polynomial of the domain of ``m`` points as a list of ``(index, coefficient)``, the highest index
+    first (``amdmsm_fr_domain_z_terms``): two terms for a basic domain, four for a step domain."""
+    limbs = _fr_limbs(curve)
+    idx, coeffs, count = (ctypes.c_size_t * 4)(), np.zeros((4, limbs), dtype=np.uint64), ctypes.c_int(0)
+    rc = load_library().amdmsm_fr_domain_z_terms(curve, ctypes.c_size_t(m), int(bool(plain)), idx, _np_ptr(coeffs), ctypes.byref(count))
+    if rc:
+        raise _domain_error("amdmsm_fr_domain_z_terms", rc)
+    return [(int(idx[k]), int.from_bytes(coeffs[k].tobytes(), "little")) for k in range(count.value)]
+
+
+def fr_multiplicative_generator(curve, plain=True):
+    """libff's ``Fr::multiplicative_generator`` (``amdmsm_fr_multiplicative_generator``), an int: the coset shift of a
+    quotient."""
+    out = np.zeros(_fr_limbs(curve), dtype=np.uint64)
+    rc = load_library().amdmsm_fr_multiplicative_generator(curve, int(bool(plain)), _np_ptr(out))
+    if rc:
+        raise _domain_error("amdmsm_fr_multiplicative_generator", rc)
     return int.from_bytes(out.tobytes(), "little")
 
 
@@ -1148,6 +1224,59 @@ class Engine:
         self._check(self.lib.amdmsm_fr_batch_invert_device(self.h, curve, ctypes.c_size_t(n), _opt_dev(d_values), int(tile_log2),
                                                            ctypes.byref(o), _opt_dev(d_out), _opt_dev(d_zero_count)),
                     "amdmsm_fr_batch_invert_device")
+
+    def _coset_record(self, curve, coset, plain):
+        return None if coset is None else _fr_record(coset, _fr_limbs(curve), fr_modulus(curve, G1), plain)
+
+    def fr_domain_fft(self, curve, values, inverse=False, coset=None, plain=False, tile_log2=0, out=None):
+        """The transform over libfqfft's evaluation domain of ``len(values)`` points (``amdmsm_fr_domain_fft``;
+        ``fr_domain`` tells which sizes are domain sizes): ``out[j] = A(g x_j)`` for the polynomial with the coefficients
+        ``values``, or with ``inverse`` the coefficients from the values.  ``coset`` (an int g): the shift, None = 1.
+        Records and ``tile_log2`` as for ``fr_fft``."""
+        values, m = _fr_array(curve, values)
+        limbs = _fr_limbs(curve)
+        if out is None:
+            out = np.zeros((m, limbs), dtype=np.uint64)
+        assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape == (m, limbs)
+        g = self._coset_record(curve, coset, plain)
+        o = self._opts(scalars_plain=plain)
+        rc = self.lib.amdmsm_fr_domain_fft(self.h, curve, _opt_ptr(values), ctypes.c_size_t(m), DOMAIN_INVERSE if inverse else 0,
+                                           _opt_ptr(g), int(tile_log2), ctypes.byref(o), _np_ptr(out))
+        self._check(rc, "amdmsm_fr_domain_fft")
+        return out
+
+    def fr_domain_fft_device(self, curve, d_values, m, d_out, inverse=False, coset=None, plain=False, tile_log2=0, stream=None):
+        """``fr_domain_fft`` on ``m`` device-resident records; ``d_out`` may be ``d_values``; enqueued on ``stream``, not
+        synchronised."""
+        g = self._coset_record(curve, coset, plain)
+        o = self._opts(scalars_plain=plain, stream=stream)
+        self._check(self.lib.amdmsm_fr_domain_fft_device(self.h, curve, _opt_dev(d_values), ctypes.c_size_t(m),
+                                                         DOMAIN_INVERSE if inverse else 0, _opt_ptr(g), int(tile_log2),
+                                                         ctypes.byref(o), _opt_dev(d_out)), "amdmsm_fr_domain_fft_device")
+
+    def fr_domain_divide_by_z(self, curve, values, coset, plain=False, out=None):
+        """``out[j] = values[j] / Z(g x_j)`` over the domain of ``len(values)`` points (``amdmsm_fr_domain_divide_by_z``),
+        g = ``coset`` (an int); refused where Z has a zero on the coset."""
+        values, m = _fr_array(curve, values)
+        limbs = _fr_limbs(curve)
+        if out is None:
+            out = np.zeros((m, limbs), dtype=np.uint64)
+        assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape == (m, limbs)
+        g = self._coset_record(curve, coset, plain)
+        o = self._opts(scalars_plain=plain)
+        rc = self.lib.amdmsm_fr_domain_divide_by_z(self.h, curve, ctypes.c_size_t(m), _opt_ptr(values), _opt_ptr(g), ctypes.byref(o),
+                                                   _np_ptr(out))
+        self._check(rc, "amdmsm_fr_domain_divide_by_z")
+        return out
+
+    def fr_domain_divide_by_z_device(self, curve, m, d_values, d_out, coset, plain=False, stream=None):
+        """``fr_domain_divide_by_z`` on ``m`` device-resident records; ``d_out`` may be ``d_values``; enqueued on
+        ``stream``, not synchronised."""
+        g = self._coset_record(curve, coset, plain)
+        o = self._opts(scalars_plain=plain, stream=stream)
+        self._check(self.lib.amdmsm_fr_domain_divide_by_z_device(self.h, curve, ctypes.c_size_t(m), _opt_dev(d_values), _opt_ptr(g),
+                                                                 ctypes.byref(o), _opt_dev(d_out)),
+                    "amdmsm_fr_domain_divide_by_z_device")
 
     def batch_exp_timings(self):
         """device times (ms) of the last batch_exp: inputs H2D, window table (0 = reused), exponentiations, results D2H"""

@@ -397,6 +397,8 @@ def emit_device_header():
             assert pow(root, 1 << (sq_s - 1), p) == p - 1
             w(f"    static constexpr uint32_t ROOT_OF_UNITY[{n}] = {c_arr(limbs(root * f['R'] % p, n, 32), '0x%08xu')};   "
               f"// {gen}^t, Montgomery form: Fr::root_of_unity")
+            w(f"    static constexpr uint32_t MULT_GENERATOR[{n}] = {c_arr(limbs(gen * f['R'] % p, n, 32), '0x%08xu')};   "
+              f"// {gen}, Montgomery form: Fr::multiplicative_generator")
         w("};")
         w("")
 
