@@ -19,54 +19,48 @@ SO_PATH = os.path.join(HERE, "libamdmsm.so")
 
 GROUPS = ["alt_bn128_g1", "alt_bn128_g2", "bls12_377_g1", "bls12_377_g2", "bw6_761_g1", "bw6_761_g2",
           "bls12_381_g1", "bls12_381_g2", "mnt4_g1", "mnt4_g2", "mnt6_g1"]
-# per-group code-generation policy (see fp.cuh Fp<P, INL> and msm_group.hip):
-#   AMDMSM_HOT_INLINE  inline the Montgomery product inside the bucket-accumulation loop
-#   AMDMSM_BENCH_BOTH  also build the inline variants of the throughput probes
-GROUP_FLAGS = {g: ["-DAMDMSM_HOT_INLINE=1", "-DAMDMSM_BENCH_BOTH=1"] for g in GROUPS}
-# register budget of the bucket-accumulation kernel: 4 waves per SIMD (128 VGPRs, 3 dwords of
-# scratch) instead of the 137 VGPRs / 3 waves the compiler picks unconstrained: -4 % at 2^20
-# (superseded by the reduced-radix loop below, which is built for three)
-# overlap mode (several MSMs in flight: the tail of one under the sort and accumulation of the next, engine.cpp
-# amdmsm_ctx::bulk_stream): the tail kernels get the 128 registers three accumulation waves leave of a SIMD
-# (round 4: the tail kernels' serial sums run on reduced-radix limbs and want ~195 registers; capped at 128 for the overlap
-# mode -- which stays off by default, it measured slower -- they spilled 292 B per lane: reduction phase 0.327 / 1.108 / 3.19 ms
-# at 2^20 / 2^23 / 2^26 capped against 0.310 / 1.025 / 3.11 uncapped, profiles/r04_experiments.txt.  No cap any more.)
-GROUP_FLAGS["alt_bn128_g1"] = GROUP_FLAGS["alt_bn128_g1"] + ["-DAMDMSM_OVERLAP_OK=1"]
-# wide fields: unconstrained, the kernel takes 256 VGPRs plus 50..125 AGPRs as spill space and
-# runs ONE wave per SIMD; capped at 256 registers (two waves per SIMD, a little scratch) it is
-# 23-25 % faster (bls12_377 G2 2^21: 28.1 -> 22.9 ms, bw6_761 G1 2^21: 43.8 -> 35.0 ms);
-# 12-limb G1: 168 registers / three waves, +4 %.  alt_bn128 G2 is fastest unconstrained
-# (249 VGPRs, two waves).
-for _g in ("bls12_377_g2", "bls12_381_g2", "bw6_761_g1", "bw6_761_g2"):
-    GROUP_FLAGS[_g] = GROUP_FLAGS[_g] + ["-DAMDMSM_ACC_WAVES=2"]
-# 8- and 12-limb G1: Montgomery products inlined in the cold kernels too (fix-up, bucket reduction,
-# butterfly; no call / operand moves around the ~1 us product of a lone wave): reduction phase
-# 0.72 -> 0.66 ms (alt_bn128 2^20), 2.74 -> 2.10 ms (bls12_377 2^22).  No gain for Fq2 / 24 limbs.
-for _g in ("alt_bn128_g1", "bls12_377_g1", "bls12_381_g1"):
-    GROUP_FLAGS[_g] = GROUP_FLAGS[_g] + ["-DAMDMSM_COLD_INLINE=1"]
-# Fq2 groups: every element split over a pair of lanes in k_accumulate (fp2h.cuh): same
-# multiply-accumulate count, half the registers per lane -- bls12_377 G2 256 VGPRs + 16 B of scratch
-# at two waves instead of + 440 B: 22.4 -> 18.1 ms at 2^21 (1.86 G madd/s, 0.90 of the MAC bound);
-# alt_bn128 G2 168 VGPRs at three waves: 4.67 -> 4.57 ms at 2^20
-for _g in ("bls12_377_g2", "bls12_381_g2", "alt_bn128_g2"):
-    GROUP_FLAGS[_g] = GROUP_FLAGS[_g] + ["-DAMDMSM_ACC_SPLIT=1"]
-GROUP_FLAGS["alt_bn128_g2"] = GROUP_FLAGS["alt_bn128_g2"] + ["-DAMDMSM_ACC_WAVES=3"]
-for _g in ("bls12_377_g1", "bls12_381_g1"):
-    GROUP_FLAGS[_g] = GROUP_FLAGS[_g] + ["-DAMDMSM_ACC_WAVES=3"]
-# k_accumulate on reduced-radix limbs for the prime-field groups (rr.cuh: 28 / 29-bit signed limbs, one
-# v_mad_i64_i32 per limb product and no carry instruction behind it, limb-wise linear operations): 1.3x the
-# mixed additions per second of the 32-bit loop on every field (tools/proto_rr.hip).  Register budget: three
-# waves per SIMD for the 9-limb field (134 registers), two for 14 and 28 limbs.
-for _g, _w in (("alt_bn128_g1", 3), ("bls12_377_g1", 2), ("bls12_381_g1", 2), ("bw6_761_g1", 2), ("bw6_761_g2", 2),
-               ("alt_bn128_g2", 3), ("bls12_377_g2", 2), ("bls12_381_g2", 2)):
-    GROUP_FLAGS[_g] = [f for f in GROUP_FLAGS[_g] if not f.startswith("-DAMDMSM_ACC_WAVES=")] + ["-DAMDMSM_ACC_RR=1", f"-DAMDMSM_ACC_WAVES={_w}"]
-# MNT4-298 / MNT6-298 G1 (a != 0, 10-word field): the 32-bit Montgomery accumulation loop -- rr.cuh's limb shapes and
-# doublings are written for the pairing fields and a = 0 -- at three waves per SIMD, products inlined in the hot loop
-# and in the cold kernels as for the other fields of fewer than 16 words
-for _g in ("mnt4_g1", "mnt6_g1"):
-    GROUP_FLAGS[_g] = GROUP_FLAGS[_g] + ["-DAMDMSM_COLD_INLINE=1", "-DAMDMSM_ACC_WAVES=3"]
-# MNT4 G2 (Fq2 = Fq[u]/(u^2 - 17), a' = 34): the 32-bit loop with whole Fq2 elements per lane, two waves per SIMD
-GROUP_FLAGS["mnt4_g2"] = GROUP_FLAGS["mnt4_g2"] + ["-DAMDMSM_ACC_WAVES=2"]
+# Per-group code-generation policy (fp.cuh Fp<P, INL>, msm_group.hip), one row per group.  Every group gets
+#   AMDMSM_HOT_INLINE  the Montgomery product inlined inside the bucket-accumulation loop
+#   AMDMSM_BENCH_BOTH  the inline variants of the throughput probes built too
+# and a row adds
+#   AMDMSM_ACC_WAVES   waves per SIMD k_accumulate is compiled for (register budget 512 / waves)
+#   AMDMSM_ACC_RR      k_accumulate on reduced-radix limbs (rr.cuh: 28 / 29-bit signed limbs, one v_mad_i64_i32 per limb
+#                      product and no carry instruction behind it): 1.3x the mixed additions per second of the 32-bit loop on
+#                      every pairing field (tools/proto_rr.hip); written for a = 0, so not for the MNT curves
+#   AMDMSM_ACC_SPLIT   every Fq2 element split over a pair of lanes in k_accumulate (fp2h.cuh): same multiply-accumulate
+#                      count, half the registers per lane
+#   AMDMSM_COLD_INLINE products inlined in the cold kernels too (fix-up, bucket reduction, butterfly): fields of fewer than
+#                      16 words; no gain for Fq2 / 24 limbs
+#   AMDMSM_OVERLAP_OK  the accumulation may run one workgroup per CU short (overlap mode, engine.cpp amdmsm_ctx::bulk_stream;
+#                      off by default, it measured slower).  The tail kernels are not capped for it: at 128 registers they
+#                      spilled 292 B per lane (profiles/r04_experiments.txt)
+def _flags(acc_waves, *on):
+    return (["-DAMDMSM_HOT_INLINE=1", "-DAMDMSM_BENCH_BOTH=1"] + [f"-DAMDMSM_{m}=1" for m in on]
+            + [f"-DAMDMSM_ACC_WAVES={acc_waves}"])
+
+
+GROUP_FLAGS = {
+    # 9 reduced-radix limbs at three waves (134 registers); cold inline: reduction phase 0.72 -> 0.66 ms at 2^20
+    "alt_bn128_g1": _flags(3, "OVERLAP_OK", "COLD_INLINE", "ACC_RR"),
+    # lane pairs: 168 VGPRs at three waves, 4.67 -> 4.57 ms at 2^20
+    "alt_bn128_g2": _flags(3, "ACC_SPLIT", "ACC_RR"),
+    # 14 limbs at two waves; cold inline: reduction phase 2.74 -> 2.10 ms at 2^22
+    "bls12_377_g1": _flags(2, "COLD_INLINE", "ACC_RR"),
+    # lane pairs: 256 VGPRs + 16 B of scratch at two waves instead of + 440 B, 22.4 -> 18.1 ms at 2^21 (1.86 G madd/s, 0.90
+    # of the MAC bound); unconstrained the kernel ran ONE wave per SIMD (28.1 -> 22.9 ms capped at two)
+    "bls12_377_g2": _flags(2, "ACC_SPLIT", "ACC_RR"),
+    # 28 limbs at two waves (capped at 256 registers: 43.8 -> 35.0 ms at 2^21 against one wave unconstrained)
+    "bw6_761_g1": _flags(2, "ACC_RR"),
+    "bw6_761_g2": _flags(2, "ACC_RR"),
+    "bls12_381_g1": _flags(2, "COLD_INLINE", "ACC_RR"),     # as bls12_377 G1
+    "bls12_381_g2": _flags(2, "ACC_SPLIT", "ACC_RR"),       # as bls12_377 G2
+    # MNT4-298 / MNT6-298 G1 (a != 0, 10-word field): the 32-bit Montgomery loop at three waves per SIMD
+    "mnt4_g1": _flags(3, "COLD_INLINE"),
+    # MNT4 G2 (Fq2 = Fq[u]/(u^2 - 17), a' = 34): the 32-bit loop with whole Fq2 elements per lane, two waves per SIMD
+    "mnt4_g2": _flags(2),
+    "mnt6_g1": _flags(3, "COLD_INLINE"),
+}
+assert list(GROUP_FLAGS) == GROUPS
 # scalar-field units (fr_ntt.hip: the FFT over Fr, its powers and product step), one per curve id
 FR_UNITS = {"alt_bn128": 0, "bls12_377": 1, "bw6_761": 2, "bls12_381": 3, "mnt4": 4, "mnt6": 5}
 ARCH = "gfx950"
@@ -99,13 +93,30 @@ def _run(cmd):
     return r
 
 
+def group_flags(g, extra=()):
+    """A group's flags with AMDMSM_EXTRA_FLAGS="-DAMDMSM_ACC_WAVES=4 ..." (experiment knobs, the same for every group)
+    appended: an experiment flag replaces the group's own setting of the same macro."""
+    names = {f.split("=")[0] for f in extra}
+    return [f for f in GROUP_FLAGS[g] if f.split("=")[0] not in names] + list(extra)
+
+
+MAX_BUILD_JOBS = 16
+
+
+def build_jobs(ntasks):
+    """Compilers run at once: MAX_JOBS where set, else the CPUs less one; never more than MAX_BUILD_JOBS -- a shared
+    machine reports many more CPUs than a job may use."""
+    want = os.environ.get("MAX_JOBS", "")
+    n = int(want) if want.isdigit() and int(want) > 0 else (os.cpu_count() or 2) - 1
+    return max(1, min(n, ntasks, MAX_BUILD_JOBS))
+
+
 def build(force=False, verbose=True, jobs=None):
     os.makedirs(OBJ, exist_ok=True)
     cc = hipcc()
     tasks = []
     objs = []
     groups = [g for g in os.environ.get("AMDMSM_GROUPS", ",".join(GROUPS)).split(",") if g]
-    # AMDMSM_EXTRA_FLAGS="-DAMDMSM_ACC_WAVES=4 ...": experiment knobs appended to every group TU
     extra = os.environ.get("AMDMSM_EXTRA_FLAGS", "").split()
     for g in groups:
         if g not in GROUPS:
@@ -113,11 +124,8 @@ def build(force=False, verbose=True, jobs=None):
         o = os.path.join(OBJ, f"group_{g}.o")
         objs.append(o)
         if force or _newer(o, DEVICE_DEPS):
-            # an experiment flag replaces the group's own setting of the same macro
-            names = {f.split("=")[0] for f in extra}
-            own = [f for f in GROUP_FLAGS.get(g, []) if f.split("=")[0] not in names]
             tasks.append([cc, *COMMON, "-c", os.path.join(CSRC, "msm_group.hip"),
-                          f"-DAMDMSM_GROUP={g}", f"-DAMDMSM_VT=vt_{g}", *own, *extra, "-o", o])
+                          f"-DAMDMSM_GROUP={g}", f"-DAMDMSM_VT=vt_{g}", *group_flags(g, extra), "-o", o])
     for c, cid in FR_UNITS.items():
         o = os.path.join(OBJ, f"fr_{c}.o")
         objs.append(o)
@@ -136,7 +144,7 @@ def build(force=False, verbose=True, jobs=None):
     if tasks:
         if verbose:
             print(f"[libff_amd.build] compiling {len(tasks)} translation unit(s) for {ARCH} ...", flush=True)
-        jobs = jobs or min(len(tasks), max(1, (os.cpu_count() or 2) - 1))
+        jobs = jobs or build_jobs(len(tasks))
         with concurrent.futures.ThreadPoolExecutor(max_workers=jobs) as ex:
             list(ex.map(_run, tasks))
     if tasks or not os.path.exists(SO_PATH) or no_ref != os.path.exists(SO_PATH + ".noref"):

@@ -214,28 +214,51 @@ size_t libff_log2(size_t n) {
     return r;
 }
 
+// One region of the MSM workspace: `unit` bytes for each of its units, from byte `off` on.  make_plan places the regions
+// (place) and is the only place that writes a unit; every user takes the pointer of unit i from ws_at.
+struct ws_region { size_t off = 0, unit = 0; };
+template <class T = uint32_t>
+T *ws_at(char *ws, const ws_region &r, size_t i = 0) {
+    return (T *)(ws + r.off + i * r.unit);
+}
 struct plan_t {
     int c = 0, W = 0;
     int D = 0;   // > 0: precomputed-table mode, D digits per scalar in one bucket set (W == 1)
     int G = 1;   // window groups (see ws_slot)
-    size_t queue_stride = 0, off_partial = 0;
     uint32_t B = 0, L = 0;
     uint32_t S = 0, T = 0;   // entries per accumulation lane, lanes per window
-    size_t off_counts = 0, off_lists = 0, off_buckets = 0, off_lvl0 = 0, off_lvl1 = 0, total = 0;
-    size_t off_pfirst = 0, off_plast = 0, off_cont = 0, off_queue = 0;
-    size_t off_coarse = 0, off_cursor = 0, off_tmp_payload = 0, off_tmp_key = 0, off_big = 0;
-    // bucket reduction as row / column sums + bit planes (vt->reduce_rowcol): scratch and serial lengths
+    size_t total = 0;
+    // unit = one window, of the K * W the workspace holds: window ends and lists, bucket accumulators, the two levels of
+    // the segment sums, first / last partial record and continued bucket of every lane, the sort's coarse counters,
+    // cursors, payloads and fine keys
+    ws_region counts, lists, buckets, lvl0, lvl1, pfirst, plast, cont, coarse, cursor, tmp_payload, tmp_key;
+    ws_region rc, planes, winsum;   // the same for vt->reduce_rowcol (rowcol): row / column sums, bit planes, window sum
+    ws_region big, endo;            // unit = one MSM of a batch: big-bin sort scratch; phi(P) = (beta x, y) of every base, compact affine
+    ws_region queue;                // unit = one window group: its fix-up queue
+    ws_region partial;              // unit = one Jacobian point: what the Horner chain of a window group hands to the next
+    // bucket reduction as row / column sums + bit planes (vt->reduce_rowcol): serial lengths
     bool rowcol = false;
     uint32_t q_row = 0, q_col = 0;
-    size_t off_rc = 0, off_planes = 0, off_winsum = 0, rc_points = 0;
-    int K = 1;                                  // MSMs the workspace holds side by side (amdmsm_msm_device_batch)
-    size_t big_stride = 0, endo_stride = 0;     // bytes per MSM of the big-bin sort scratch / the phi(P) records
-    size_t list_stride = 0;
+    int K = 1;               // MSMs the workspace holds side by side (amdmsm_msm_device_batch)
+    size_t list_stride = 0;  // words between two windows of `lists` (and of the sort's payloads and keys)
     bool glv = false;        // endomorphism split: the sorted columns are 2 * n_real half-length scalars
-    size_t off_endo = 0;     // phi(P) = (beta x, y) of every base, compact affine
 };
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// puts `count` units of `unit` bytes at *off and moves *off behind them, to the next multiple of 256
+void place(ws_region &r, size_t *off, size_t count, size_t unit) {
+    r.off = *off;
+    r.unit = unit;
+    *off = align_up(*off + count * unit, 256);
+}
+// the buffers of the sort of MSM j of the workspace (a single MSM: j = 0) -- its windows start at window j * W
+sort_bufs sort_bufs_of(const plan_t &p, char *ws, size_t j) {
+    const size_t w = j * (size_t)p.W;
+    uint32_t *lists = ws_at(ws, p.lists, w);
+    // the digits live in the lists' space
+    return sort_bufs{ws_at(ws, p.coarse, w), ws_at(ws, p.cursor, w), (int32_t *)lists, ws_at(ws, p.tmp_payload, w),
+                     ws_at(ws, p.tmp_key, w), ws_at(ws, p.counts, w), lists, p.list_stride, ws_at(ws, p.big, j)};
+}
 
 // Windows needed for signed radix-2^c digits of the half scalars of the endomorphism split,
 // |k| <= 2^lb: the recoded top digit must not carry out, i.e. 2^lb < 2^(cW-1) - 2^(c(W-1))
@@ -445,49 +468,31 @@ int make_plan(const group_vtable *vt, const plan_req &r, plan_t &p) {
     }
     p.K = batch;
     const size_t Wt = (size_t)p.W * (size_t)batch;   // windows the workspace holds
+    // The regions of the workspace, in the order they lie in it; the byte counts here are the only statement of a stride.
     size_t off = 0;
-    p.off_counts = off;
-    off = align_up(off + Wt * p.B * 4, 256);
-    p.off_lists = off;
-    off = align_up(off + Wt * p.list_stride * 4, 256);
+    place(p.counts, &off, Wt, p.B * 4);
+    place(p.lists, &off, Wt, p.list_stride * 4);
     const size_t zz_bytes = (size_t)vt->bucket_words * 4;   // (X, Y, ZZ, ZZZ) bucket accumulators (reduced-radix groups: 4 L limbs)
-    p.off_buckets = off;
-    off = align_up(off + Wt * p.B * zz_bytes, 256);
+    place(p.buckets, &off, Wt, p.B * zz_bytes);
     const size_t M = p.B / p.L;
-    p.off_lvl0 = off;
-    off = align_up(off + Wt * M * xyz_bytes, 256);
-    p.off_lvl1 = off;
-    off = align_up(off + Wt * (M / 2 + 1) * xyz_bytes, 256);   // first fold leaves at most M / 32 points
-    p.off_pfirst = off;
-    off = align_up(off + Wt * p.T * zz_bytes, 256);
-    p.off_plast = off;
-    off = align_up(off + Wt * p.T * zz_bytes, 256);
-    p.off_cont = off;
-    off = align_up(off + Wt * p.T * 4, 256);
+    place(p.lvl0, &off, Wt, M * xyz_bytes);
+    place(p.lvl1, &off, Wt, (M / 2 + 1) * xyz_bytes);   // first fold leaves at most M / 32 points
+    place(p.pfirst, &off, Wt, p.T * zz_bytes);
+    place(p.plast, &off, Wt, p.T * zz_bytes);
+    place(p.cont, &off, Wt, p.T * 4);
     p.G = G_req > 0 ? std::min(std::min(G_req, MAX_GROUPS), p.W) : 1;
-    p.off_queue = off;   // one fix-up queue per group, each sized for the largest group
-    p.queue_stride = align_up(fixup_queue_words((size_t)((p.W + p.G - 1) / p.G) * (size_t)batch * p.T) * 4, 256);
-    off = off + p.queue_stride * p.G;
-    p.off_partial = off;
-    off = align_up(off + (size_t)MAX_GROUPS * xyz_bytes, 256);
-    // two-level sort scratch
-    // (the coarse counters, the cursors of the coarse pass and the header of the big-bin scratch are cleared by ONE
-    // memset: cursors and scratch follow the counters directly)
-    p.off_coarse = off;
-    off = align_up(off + Wt * 1025 * 4, 256);
-    p.off_cursor = off;
-    off = align_up(off + Wt * 1024 * 4, 256);
-    p.off_big = off;
+    // one fix-up queue per group, each sized for the largest group
+    place(p.queue, &off, p.G, align_up(fixup_queue_words((size_t)((p.W + p.G - 1) / p.G) * (size_t)batch * p.T) * 4, 256));
+    place(p.partial, &off, MAX_GROUPS, xyz_bytes);
+    // two-level sort scratch.  The coarse counters, the cursors of the coarse pass and the header of the big-bin scratch
+    // are cleared by ONE memset from coarse.off on, so these three regions must stay adjacent and in this order.
+    place(p.coarse, &off, Wt, SORT_COARSE_WORDS * 4);
+    place(p.cursor, &off, Wt, SORT_CURSOR_WORDS * 4);
     // (big_words_min: a batch of MSMs of different lengths passes the largest need of any of its lengths)
-    p.big_stride = p.c <= 22 ? align_up(std::max(sort_geometry(n, p.c, p.W).big_words, big_words_min) * 4, 256) : 256;   // per MSM of a batch
-    off += p.big_stride * (size_t)batch;
-    p.off_tmp_payload = off;
-    off = align_up(off + Wt * p.list_stride * 4, 256);
-    p.off_tmp_key = off;
-    off = align_up(off + Wt * p.list_stride * 4, 256);   // 16-bit fine keys use half of it
-    p.off_endo = off;
-    p.endo_stride = glv ? align_up((n / 2) * (size_t)vt->el_words * 2 * 4, 256) : 0;   // per MSM of a batch
-    off += p.endo_stride * (size_t)batch;
+    place(p.big, &off, batch, p.c <= 22 ? align_up(std::max(sort_geometry(n, p.c, p.W).big_words, big_words_min) * 4, 256) : 256);
+    place(p.tmp_payload, &off, Wt, p.list_stride * 4);
+    place(p.tmp_key, &off, Wt, p.list_stride * 4);   // 16-bit fine keys use half of it
+    place(p.endo, &off, batch, glv ? align_up((n / 2) * (size_t)vt->el_words * 2 * 4, 256) : 0);
     // Bucket reduction as plain sums (row / column sums of the weight matrix, bit planes, one short
     // Horner per window) from c = 10 up; below that a window's few segments fold inside one wave of
     // k_reduce_segments.  AMDMSM_ROWCOL=0 keeps the segment kernels everywhere (A/B runs).
@@ -511,13 +516,9 @@ int make_plan(const group_vtable *vt, const plan_req &r, plan_t &p) {
         while (q < 64 && Wt * p.B * red_lanes * 2 / q > lane_budget) q <<= 1;
         p.q_row = qr_env > 0 ? (uint32_t)qr_env : q;
         p.q_col = qc_env > 0 ? (uint32_t)qc_env : q;
-        p.rc_points = R + 1 + C;
-        p.off_rc = off;
-        off = align_up(off + Wt * p.rc_points * xyz_bytes, 256);
-        p.off_planes = off;
-        off = align_up(off + Wt * p.c * xyz_bytes, 256);
-        p.off_winsum = off;
-        off = align_up(off + Wt * xyz_bytes, 256);
+        place(p.rc, &off, Wt, (R + 1 + C) * xyz_bytes);
+        place(p.planes, &off, Wt, p.c * xyz_bytes);
+        place(p.winsum, &off, Wt, xyz_bytes);
     }
     p.total = off;
     return AMDMSM_OK;
@@ -674,23 +675,19 @@ int short_limit_bits(const group_vtable *vt, const short_spec &ss) {
 // the fix-up of the buckets that span accumulation lanes (fix-up queue `queue`), then the bucket reduction -- row / column
 // sums and bit planes, or segment sums and the levels that fold them.  Returns the nw window sums Horner reads.
 uint32_t *enqueue_tail(const group_vtable *vt, const plan_t &p, char *ws, int w0, int nw, hipStream_t ts, int queue) {
-    const size_t zzw = (size_t)vt->bucket_words, xyzw = (size_t)vt->el_words * 3;   // words per XYZZ / Jacobian point
     const size_t w = (size_t)w0;
-    uint32_t *buckets = (uint32_t *)(ws + p.off_buckets) + w * p.B * zzw;
-    vt->accumulate_fixup(ts, (uint32_t *)(ws + p.off_counts) + w * p.B, buckets, (uint32_t *)(ws + p.off_pfirst) + w * p.T * zzw,
-                         (uint32_t *)(ws + p.off_plast) + w * p.T * zzw, (uint32_t *)(ws + p.off_cont) + w * p.T,
-                         (uint32_t *)(ws + p.off_queue + (size_t)queue * p.queue_stride), nw, p.B, p.S, p.T);
+    uint32_t *buckets = ws_at(ws, p.buckets, w);
+    vt->accumulate_fixup(ts, ws_at(ws, p.counts, w), buckets, ws_at(ws, p.pfirst, w), ws_at(ws, p.plast, w), ws_at(ws, p.cont, w),
+                         ws_at(ws, p.queue, (size_t)queue), nw, p.B, p.S, p.T);
     if (p.rowcol) {
-        uint32_t *winsum = (uint32_t *)(ws + p.off_winsum) + w * xyzw;
-        vt->reduce_rowcol(ts, buckets, nw, p.B, p.c, p.q_row, p.q_col, (uint32_t *)(ws + p.off_rc) + w * p.rc_points * xyzw,
-                          (uint32_t *)(ws + p.off_planes) + w * p.c * xyzw, winsum);
+        uint32_t *winsum = ws_at(ws, p.winsum, w);
+        vt->reduce_rowcol(ts, buckets, nw, p.B, p.c, p.q_row, p.q_col, ws_at(ws, p.rc, w), ws_at(ws, p.planes, w), winsum);
         return winsum;
     }
-    const size_t M0 = p.B / p.L, cap1 = M0 / 2 + 1;   // segments of a window, points a window keeps in lvl1
-    uint32_t *src = (uint32_t *)(ws + p.off_lvl0) + w * M0 * xyzw, *dst = (uint32_t *)(ws + p.off_lvl1) + w * cap1 * xyzw;
+    uint32_t *src = ws_at(ws, p.lvl0, w), *dst = ws_at(ws, p.lvl1, w);
     vt->reduce_segments(ts, buckets, nw, p.B, p.L, src);
     const uint32_t fold = (uint32_t)vt->reduce_fold;
-    uint32_t M = (uint32_t)M0;
+    uint32_t M = p.B / p.L;   // segments of a window
     M /= std::min<uint32_t>(M, fold);   // folded per wave inside reduce_segments
     while (M > 1) {
         if ((size_t)M * (64 / fold) <= 256) {   // the remaining levels in one launch
@@ -760,37 +757,30 @@ int msm_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_b
     rc = ensure_ws(ctx, sl, p.total);
     if (rc) return rc;
     char *ws = (char *)sl.ws;
-    uint32_t *counts = (uint32_t *)(ws + p.off_counts);
-    uint32_t *lists = (uint32_t *)(ws + p.off_lists);
-    uint32_t *buckets = (uint32_t *)(ws + p.off_buckets);
+    const sort_bufs sb = sort_bufs_of(p, ws, 0);
 
     record(ctx, sl, 0, st);
     // phi(P) of every base (endomorphism split): independent of the sort, so it runs beside it on
     // the slot's side stream when the bases are already on the device (no upload hook)
     // (d_endo_resident: the records already exist, kept with a registered base vector)
-    const uint32_t *endo_pts = !glv ? nullptr : (d_endo_resident ? d_endo_resident : (const uint32_t *)(ws + p.off_endo));
+    const uint32_t *endo_pts = !glv ? nullptr : (d_endo_resident ? d_endo_resident : ws_at(ws, p.endo));
     const bool endo_beside = glv && !d_endo_resident && !(hook && hook->fn);
     // the side stream also clears the bucket array and the queue heads while the sort runs (both
     // are first touched by the accumulation)
     HIP_TRY(ctx, hipEventRecord(sl.tail_done[0], st));
     if ((atomic_sort || p.c > 22) && !table_digits) {
-        HIP_TRY(ctx, hipMemsetAsync(counts, 0, (size_t)p.W * p.B * 4, st));
-        vt->count(st, d_scalars, n, mont, p.c, p.W, counts);
+        HIP_TRY(ctx, hipMemsetAsync(sb.ends, 0, (size_t)p.W * p.counts.unit, st));
+        vt->count(st, d_scalars, n, mont, p.c, p.W, sb.ends);
         record(ctx, sl, 1, st);
-        vt->scatter(st, d_scalars, n, mont, p.c, p.W, counts, lists, p.list_stride);
+        vt->scatter(st, d_scalars, n, mont, p.c, p.W, sb.ends, sb.lists, p.list_stride);
     } else {
-        HIP_TRY(ctx, hipMemsetAsync(ws + p.off_coarse, 0, p.off_big + 16 - p.off_coarse, st));   // counters + cursors + big-bin header
+        HIP_TRY(ctx, hipMemsetAsync(sb.coarse, 0, p.big.off + 16 - p.coarse.off, st));   // counters + cursors + big-bin header
         record(ctx, sl, 1, st);
         if (ss)
-            vt->sort_short(st, d_scalars, ss->kind, short_limit_bits(vt, *ss), ss->flag, n, mont, p.c, p.W,
-                           (uint32_t *)(ws + p.off_coarse), (uint32_t *)(ws + p.off_cursor), (int32_t *)lists,
-                           (uint32_t *)(ws + p.off_tmp_payload), (uint32_t *)(ws + p.off_tmp_key), counts, lists, p.list_stride,
-                           (uint32_t *)(ws + p.off_big));
+            vt->sort(st, sort_src::short_scalars(d_scalars, ss->kind, short_limit_bits(vt, *ss), ss->flag), n, mont, p.c, p.W, sb, 0);
         else
-        vt->sort(st, d_scalars, n, mont, p.c, table_digits ? table_digits : p.W, (uint32_t *)(ws + p.off_coarse),
-                 (uint32_t *)(ws + p.off_cursor), (int32_t *)lists, (uint32_t *)(ws + p.off_tmp_payload),
-                 (uint32_t *)(ws + p.off_tmp_key), counts, lists, p.list_stride, (uint32_t *)(ws + p.off_big),
-                 table_digits ? 1 : (glv ? 2 : 0), nullptr);
+            vt->sort(st, sort_src::own(d_scalars), n, mont, p.c, table_digits ? table_digits : p.W, sb,
+                     table_digits ? 1 : (glv ? 2 : 0));
     }
     // (measured at 2^20 points: beside the whole sort 0.29 ms for the phase, beside its LDS-bound
     // second half only 0.35, after it 0.30; the plain path's sort takes 0.24)
@@ -800,9 +790,9 @@ int msm_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_b
     // for the previous MSM's tail -- seen in a kernel trace: the accumulation then started only after that tail)
     hipStream_t side = overlap ? st : sl.side[0];
     if (!overlap) HIP_TRY(ctx, hipStreamWaitEvent(side, sl.tail_done[0], 0));
-    HIP_TRY(ctx, hipMemsetAsync(buckets, 0, (size_t)p.W * p.B * vt->bucket_words * 4, side));
-    for (int g = 0; g < p.G; ++g) HIP_TRY(ctx, hipMemsetAsync(ws + p.off_queue + g * p.queue_stride, 0, 8, side));
-    if (endo_beside) vt->endo_points(side, d_bases, n, (uint32_t *)(ws + p.off_endo));
+    HIP_TRY(ctx, hipMemsetAsync(ws_at(ws, p.buckets), 0, (size_t)p.W * p.buckets.unit, side));
+    for (int g = 0; g < p.G; ++g) HIP_TRY(ctx, hipMemsetAsync(ws_at(ws, p.queue, (size_t)g), 0, 8, side));
+    if (endo_beside) vt->endo_points(side, d_bases, n, ws_at(ws, p.endo));
     if (!overlap) HIP_TRY(ctx, hipEventRecord(sl.acc_done[0], side));
     if (hook && hook->fn) {
         hipEvent_t wait_for = nullptr;
@@ -811,10 +801,7 @@ int msm_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_b
         if (wait_for) HIP_TRY(ctx, hipStreamWaitEvent(st, wait_for, 0));
     }
     if (!overlap) HIP_TRY(ctx, hipStreamWaitEvent(st, sl.acc_done[0], 0));
-    if (glv && !d_endo_resident && !endo_beside) vt->endo_points(st, d_bases, n, (uint32_t *)(ws + p.off_endo));
-    const size_t zzw = (size_t)vt->bucket_words, xyzw = (size_t)vt->el_words * 3;   // words per XYZZ / Jacobian point
-    uint32_t *pfirst = (uint32_t *)(ws + p.off_pfirst), *plast = (uint32_t *)(ws + p.off_plast);
-    uint32_t *cont = (uint32_t *)(ws + p.off_cont), *partial = (uint32_t *)(ws + p.off_partial);
+    if (glv && !d_endo_resident && !endo_beside) vt->endo_points(st, d_bases, n, ws_at(ws, p.endo));
     // groups of windows, highest first: [w0, w0 + wg)
     int w_hi = p.W;
     for (int g = 0; g < p.G; ++g) {
@@ -826,9 +813,9 @@ int msm_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_b
         // moves to a side stream
         hipStream_t ts = last ? (overlap ? ctx->tail_stream : st) : sl.side[g];
         if (g == 0) record(ctx, sl, 2, st);
-        vt->accumulate(st, counts + (size_t)w0 * p.B, lists + (size_t)w0 * p.list_stride, p.list_stride, d_bases,
-                       buckets + (size_t)w0 * p.B * zzw, pfirst + (size_t)w0 * p.T * zzw, plast + (size_t)w0 * p.T * zzw,
-                       cont + (size_t)w0 * p.T, wg, p.B, p.S, p.T, endo_pts, n, overlap ? 1 : 0);
+        vt->accumulate(st, ws_at(ws, p.counts, w0), ws_at(ws, p.lists, w0), p.list_stride, d_bases, ws_at(ws, p.buckets, w0),
+                       ws_at(ws, p.pfirst, w0), ws_at(ws, p.plast, w0), ws_at(ws, p.cont, w0), wg, p.B, p.S, p.T, endo_pts, n,
+                       overlap ? 1 : 0);
         if (last) {
             record(ctx, sl, 3, st);
             if (overlap) {
@@ -843,8 +830,8 @@ int msm_device_impl(amdmsm_ctx *ctx, const group_vtable *vt, const uint32_t *d_b
         // Horner over this group's windows, continuing from the groups above
         if (g > 0) HIP_TRY(ctx, hipStreamWaitEvent(ts, sl.tail_done[g - 1], 0));
         if (last) record(ctx, sl, 4, ts);
-        vt->horner(ts, src, wg, p.c, last ? form : (int)AMDMSM_OUT_JACOBIAN, g > 0 ? partial + (size_t)(g - 1) * xyzw : nullptr,
-                   last ? d_out : partial + (size_t)g * xyzw);
+        vt->horner(ts, src, wg, p.c, last ? form : (int)AMDMSM_OUT_JACOBIAN, g > 0 ? ws_at(ws, p.partial, g - 1) : nullptr,
+                   last ? d_out : ws_at(ws, p.partial, g));
         if (!last) HIP_TRY(ctx, hipEventRecord(sl.tail_done[g], ts));
     }
     if (overlap) {
@@ -931,43 +918,32 @@ int msm_device_batch_items_impl(amdmsm_ctx *ctx, const group_vtable *vt, int k, 
     rc = ensure_ws(ctx, sl, p.total);
     if (rc) return rc;
     char *ws = (char *)sl.ws;
-    const size_t zzw = (size_t)vt->bucket_words;
     const size_t Wt = (size_t)p.W * (size_t)k;
-    uint32_t *counts = (uint32_t *)(ws + p.off_counts), *lists = (uint32_t *)(ws + p.off_lists);
-    uint32_t *buckets = (uint32_t *)(ws + p.off_buckets);
-    uint32_t *pfirst = (uint32_t *)(ws + p.off_pfirst), *plast = (uint32_t *)(ws + p.off_plast), *cont = (uint32_t *)(ws + p.off_cont);
     record(ctx, sl, 0, st);
-    HIP_TRY(ctx, hipMemsetAsync(ws + p.off_coarse, 0, p.off_big - p.off_coarse, st));   // counters + cursors
-    for (int j = 0; j < k; ++j) HIP_TRY(ctx, hipMemsetAsync(ws + p.off_big + (size_t)j * p.big_stride, 0, 16, st));
-    HIP_TRY(ctx, hipMemsetAsync(buckets, 0, Wt * p.B * vt->bucket_words * 4, st));
-    HIP_TRY(ctx, hipMemsetAsync(ws + p.off_queue, 0, 8, st));
+    HIP_TRY(ctx, hipMemsetAsync(ws_at(ws, p.coarse), 0, p.big.off - p.coarse.off, st));   // counters + cursors
+    for (int j = 0; j < k; ++j) HIP_TRY(ctx, hipMemsetAsync(ws_at(ws, p.big, (size_t)j), 0, 16, st));
+    HIP_TRY(ctx, hipMemsetAsync(ws_at(ws, p.buckets), 0, Wt * p.buckets.unit, st));
+    HIP_TRY(ctx, hipMemsetAsync(ws_at(ws, p.queue), 0, 8, st));
     record(ctx, sl, 1, st);
     bool first = true;
     for (int j = 0; j < k; ++j) {
         const size_t w0 = (size_t)j * p.W, n = it[j].n;
-        uint32_t *lists_j = lists + w0 * p.list_stride, *counts_j = counts + w0 * p.B;
+        const sort_bufs sb = sort_bufs_of(p, ws, (size_t)j);
         if (n == 0) {
             // no entries: every bucket of its windows ends at 0 and no lane continues a bucket (NO_BUCKET = ~0)
-            HIP_TRY(ctx, hipMemsetAsync(counts_j, 0, (size_t)p.W * p.B * 4, st));
-            HIP_TRY(ctx, hipMemsetAsync(cont + w0 * p.T, 0xff, (size_t)p.W * p.T * 4, st));
+            HIP_TRY(ctx, hipMemsetAsync(sb.ends, 0, (size_t)p.W * p.counts.unit, st));
+            HIP_TRY(ctx, hipMemsetAsync(ws_at(ws, p.cont, w0), 0xff, (size_t)p.W * p.cont.unit, st));
             continue;
         }
-        uint32_t *coarse_j = (uint32_t *)(ws + p.off_coarse) + w0 * 1025, *cursor_j = (uint32_t *)(ws + p.off_cursor) + w0 * 1024;
-        uint32_t *tmp_pay_j = (uint32_t *)(ws + p.off_tmp_payload) + w0 * p.list_stride;
-        uint32_t *tmp_key_j = (uint32_t *)(ws + p.off_tmp_key) + w0 * p.list_stride;
-        uint32_t *big_j = (uint32_t *)(ws + p.off_big + (size_t)j * p.big_stride);
-        if (it[j].scalars)
-            vt->sort(st, it[j].scalars, n, mont, p.c, p.W, coarse_j, cursor_j, (int32_t *)lists_j, tmp_pay_j, tmp_key_j, counts_j,
-                     lists_j, p.list_stride, big_j, glv ? 2 : 0, nullptr);
-        else
-            vt->sort_sel(st, d_shared, shared_n, it[j].index, it[j].offset, flags + j, n, mont, p.c, p.W, coarse_j, cursor_j,
-                         (int32_t *)lists_j, tmp_pay_j, tmp_key_j, counts_j, lists_j, p.list_stride, big_j, glv ? 2 : 0);
-        uint32_t *endo_j = glv ? (uint32_t *)(ws + p.off_endo + (size_t)j * p.endo_stride) : nullptr;
+        const sort_src src_j = it[j].scalars ? sort_src::own(it[j].scalars)
+                                             : sort_src::selected(d_shared, shared_n, it[j].index, it[j].offset, flags + j);
+        vt->sort(st, src_j, n, mont, p.c, p.W, sb, glv ? 2 : 0);
+        uint32_t *endo_j = glv ? ws_at(ws, p.endo, (size_t)j) : nullptr;
         if (glv) vt->endo_points(st, it[j].bases, n, endo_j);
         if (first) record(ctx, sl, 2, st);
         first = false;
-        vt->accumulate(st, counts_j, lists_j, p.list_stride, it[j].bases, buckets + w0 * p.B * zzw, pfirst + w0 * p.T * zzw,
-                       plast + w0 * p.T * zzw, cont + w0 * p.T, p.W, p.B, p.S, p.T, endo_j, n, 0);
+        vt->accumulate(st, sb.ends, sb.lists, p.list_stride, it[j].bases, ws_at(ws, p.buckets, w0), ws_at(ws, p.pfirst, w0),
+                       ws_at(ws, p.plast, w0), ws_at(ws, p.cont, w0), p.W, p.B, p.S, p.T, endo_j, n, 0);
     }
     record(ctx, sl, 3, st);
     const uint32_t *src = enqueue_tail(vt, p, ws, 0, (int)Wt, st, 0);
@@ -1297,7 +1273,7 @@ int amdmsm_plan_sort(int curve, int group, size_t n, int window_bits, int endomo
 
 int amdmsm_plan_sort_digit_grid(size_t items, unsigned block_min, unsigned workgroups, size_t out[3]) {
     if (!out || workgroups == 0) return AMDMSM_ERR_BAD_ARG;
-    // the launcher's own function (msm_group.hip sort_launch)
+    // the launcher's own function (msm_group.hip l_sort)
     const digit_grid g = sort_digit_grid(items, block_min, workgroups);
     out[0] = g.block;
     out[1] = g.blocks;
@@ -1320,7 +1296,7 @@ int amdmsm_plan_top_window(int curve, int group, size_t n, int window_bits, int 
     const int rc = make_plan(vt, req, p);
     if (rc) return rc;
     if (p.c > 22) return AMDMSM_ERR_UNSUPPORTED;
-    // the sort launcher's own value (msm_group.hip sort_launch asks the same function)
+    // the sort launcher's own value (msm_group.hip l_sort asks the same function)
     out[1] = vt->sort_top_window(glv ? 2 : 0, scalars_plain ? 0 : 1, p.c, p.W, glv ? 2 * n : n, &out[0]);
     out[2] = p.c;
     out[3] = p.W;

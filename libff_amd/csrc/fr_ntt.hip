@@ -229,9 +229,27 @@ void l_muladd(hipStream_t st, size_t n, const uint32_t* d_a, const uint32_t* d_b
 }
 
 const fr_vtable g_frvt = {
-    AMDMSM_FR_CURVE, N, FR::SQRT_S, FR::INV, FR::P, FR::R, FR::R2, FR::ROOT_OF_UNITY, l_powers, l_pass, l_muladd,
-    FRM_T, l_matrix_apply, l_matrix_naive, l_scan, l_scan_naive,
-    FR::MULT_GENERATOR, l_domain_sweep, l_domain_combine, l_domain_den, l_domain_divide,
+    .curve = AMDMSM_FR_CURVE,
+    .words = N,
+    .two_adicity = FR::SQRT_S,
+    .inv = FR::INV,
+    .modulus = FR::P,
+    .one = FR::R,
+    .r2 = FR::R2,
+    .root = FR::ROOT_OF_UNITY,
+    .generator = FR::MULT_GENERATOR,
+    .powers = l_powers,
+    .pass = l_pass,
+    .muladd = l_muladd,
+    .matrix_chunk = FRM_T,
+    .matrix_apply = l_matrix_apply,
+    .matrix_naive = l_matrix_naive,
+    .scan = l_scan,
+    .scan_naive = l_scan_naive,
+    .domain_sweep = l_domain_sweep,
+    .domain_combine = l_domain_combine,
+    .domain_den = l_domain_den,
+    .domain_divide = l_domain_divide,
 };
 
 }  // namespace

@@ -91,10 +91,13 @@ struct frd_combine {
     uint32_t half[FR_MAX_WORDS];   // 1 / 2, Montgomery
 };
 
+// Members by stage: constants of the field, the transform, the sparse matrix, scans, step domains.  fr_ntt.hip fills
+// the table by member name.
 struct fr_vtable {
     int curve, words, two_adicity;
     uint32_t inv;                                  // -r^-1 mod 2^32
     const uint32_t *modulus, *one, *r2, *root;     // r, R mod r, R^2 mod r, libff's Fr::root_of_unity (Montgomery)
+    const uint32_t* generator;                     // libff's Fr::multiplicative_generator (Montgomery): the step domains' coset
     // d_out[i] = first * base^i, i < n.  table: FR_POW_TABLE host records base^(2^b); first: a host record or null (1)
     void (*powers)(hipStream_t, const uint32_t* table, const uint32_t* first, int out_plain, size_t n, uint32_t* d_out);
     void (*pass)(hipStream_t, const fr_pass&);
@@ -111,10 +114,9 @@ struct fr_vtable {
     void (*scan)(hipStream_t, const frs_args&);
     // the same by one lane that walks the vector: AMDMSM_FR_SCAN_NAIVE=1
     void (*scan_naive)(hipStream_t, const frs_args&);
-    // step radix-2 domains (fr_domain.inc): libff's Fr::multiplicative_generator (Montgomery), the fold / merge / partial-sum
-    // sweep, row 0 of the inverse, d_den[k] -= c (c: a host record), and d_out[j] = d_in[j] * (j < B ? d_inv[j mod K] : tail)
-    // for j < m (tail: a host record; B = 0: tail throughout)
-    const uint32_t* generator;
+    // step radix-2 domains (fr_domain.inc): the fold / merge / partial-sum sweep, row 0 of the inverse, d_den[k] -= c
+    // (c: a host record), and d_out[j] = d_in[j] * (j < B ? d_inv[j mod K] : tail) for j < m (tail: a host record;
+    // B = 0: tail throughout)
     void (*domain_sweep)(hipStream_t, const frd_sweep&);
     void (*domain_combine)(hipStream_t, const frd_combine&);
     void (*domain_den)(hipStream_t, size_t n, uint32_t* d_den, const uint32_t* c);

@@ -25,6 +25,10 @@ struct sort_geom {
     uint32_t big_cap;     // most such bins one call can hold (bound: total entries / big_thresh)
     size_t big_words;     // words of scratch for them: header + list + per-bin cursors
 };
+// The most coarse bits a plan takes, and with them the words of one window's coarse counters (2^hb bins and their total)
+// and coarse-pass cursors (2^hb): the workspace holds both at this size whatever hb a call's length gives.
+constexpr int SORT_HB_MAX = 10;
+constexpr size_t SORT_COARSE_WORDS = ((size_t)1 << SORT_HB_MAX) + 1, SORT_CURSOR_WORDS = (size_t)1 << SORT_HB_MAX;
 inline sort_geom sort_geometry(size_t n, int c, int W) {
     sort_geom g;
     // coarse / fine split of the c-1 bucket-index bits: about half each, at most 10 coarse and 11
@@ -32,7 +36,7 @@ inline sort_geom sort_geometry(size_t n, int c, int W) {
     // c = 16, 8 coarse bits beat 10 at every size from 2^16 to 2^23 (2^20: 0.27 vs 0.29 ms,
     // 2^16: 0.07 vs 0.09); around 2^20 points 7 is better still (0.24 ms).  AMDMSM_SORT_HB overrides.
     static const int hb_env = getenv("AMDMSM_SORT_HB") ? atoi(getenv("AMDMSM_SORT_HB")) : 0;
-    g.hb = c / 2 < 10 ? c / 2 : 10;
+    g.hb = c / 2 < SORT_HB_MAX ? c / 2 : SORT_HB_MAX;
     if (c == 16 && n >= ((size_t)3 << 18) && n < ((size_t)3 << 19)) g.hb = 7;
     if (hb_env > 0) g.hb = hb_env;
     if (g.hb > c - 1) g.hb = c - 1;
@@ -122,7 +126,51 @@ AMDMSM_HD inline size_t fixup_queue_cap_long(size_t lanes) { return lanes / 32 +
 AMDMSM_HD inline size_t fixup_queue_cap_mid(size_t lanes) { return lanes / 3 + 2; }
 inline size_t fixup_queue_words(size_t lanes) { return 2 + 2 * (fixup_queue_cap_long(lanes) + fixup_queue_cap_mid(lanes)); }
 
+// The buffers of one two-level sort (group_vtable::sort), every pointer the start of window 0 of the call: a sub-range
+// of windows, or one MSM of a batch, is sorted by passing offset pointers and its window count.
+struct sort_bufs {
+    uint32_t* coarse;        // W * SORT_COARSE_WORDS words, zeroed
+    uint32_t* cursor;        // W * SORT_CURSOR_WORDS words, zeroed
+    int32_t* digits;         // W * stride words; may alias lists (the digits are dead once the coarse pass has run)
+    uint32_t* tmp_payload;   // W * stride words
+    uint32_t* tmp_key;       // W * stride 16-bit fine keys
+    uint32_t* ends;          // out: ends[w][b], W * 2^(c-1) words
+    uint32_t* lists;         // out: lists[w][...], W * stride words
+    size_t stride;           // words between two windows of digits / tmp_payload / tmp_key / lists
+    uint32_t* big;           // sort_geometry().big_words words, the first 4 zeroed (oversized coarse bins, sorted cooperatively)
+};
+// Where scalar i of a sort comes from.  OWN: record i of `scalars` (Fr records; mont: Montgomery residues).
+// SELECTED (amdmsm_*_batch_items): `scalars` is a vector of sel.shared_n scalars that several MSMs share, and base i
+// takes element sel.index[i] of it (index != null; any order, repeats allowed), else element sel.offset + i.  An element
+// at or past shared_n is not read: it counts as scalar 0 and sets *sel.flag (one word, cleared by the caller) to nonzero.
+// SHORT (amdmsm_*_short): W is sized for scalars below 2^shrt.limit_bits, and `scalars` holds elements of shrt.kind =
+// AMDMSM_SCALAR_*: 0 = Fr records, else the bytes of one packed little-endian unsigned integer (1, 2, 4, 8; the pointer
+// needs that alignment only).  A scalar that is not below the limit counts as 0 and sets *shrt.flag (one word, cleared by
+// the caller) to nonzero; limit_bits at the kind's full width tests nothing and the flag may be null.
+// The rules: the short form runs mode 0 only; the short form and selection exclude each other (one `form`); and in every
+// form sort_bufs::digits may alias sort_bufs::lists.
+struct sort_src {
+    enum form_t : int { OWN = 0, SELECTED = 1, SHORT = 2 };
+    struct selection { const uint32_t* index; size_t offset, shared_n; uint32_t* flag; };   // index null: slice
+    struct short_form { int kind, limit_bits; uint32_t* flag; };
+    const void* scalars;
+    form_t form;
+    selection sel;      // SELECTED
+    short_form shrt;    // SHORT
+    static sort_src own(const uint32_t* scalars) { return {scalars, OWN, {}, {}}; }
+    static sort_src selected(const uint32_t* shared, size_t shared_n, const uint32_t* index, size_t offset, uint32_t* flag) {
+        return {shared, SELECTED, {index, offset, shared_n, flag}, {}};
+    }
+    static sort_src short_scalars(const void* scalars, int kind, int limit_bits, uint32_t* flag) {
+        return {scalars, SHORT, {}, {kind, limit_bits, flag}};
+    }
+};
+
+// Members by stage: constants of the group; import / export / codecs; digits and sort; accumulate and fix-up; reduction
+// and Horner; fixed-base; point-vector entries (smv, seg, fold, fft); test hooks and probes.  msm_group.hip fills the
+// table by member name.
 struct group_vtable {
+    // ---- constants of the group ----------
     int curve, group;
     int fr_words;      // 32-bit words per scalar
     int el_words;      // 32-bit words per coordinate (Fq or Fq2)
@@ -132,46 +180,74 @@ struct group_vtable {
     int reduce_fold;   // segments / points one wave of reduce_segments / sum_butterfly folds (64 or 32)
     int bucket_words;  // words between two records of the bucket / partial accumulator arrays (>= 4 * el_words)
     const uint32_t* fr_one_mont;   // Fr::one() in Montgomery form (R mod r), fr_words words
+    const uint32_t* fr_modulus;    // the scalar-field modulus r, plain integer, fr_words words
+    // the group has the endomorphism phi below (0: MNT4 / MNT6, whose glv_* entries are placeholders and whose
+    // amdmsm_opts.endomorphism is ignored); the curve has a != 0 (the compressed-record decoders assume a = 0)
+    int has_endomorphism;
+    int coeff_a_nonzero;
     // endomorphism split k = k1 + k2 lambda (mod r), phi(x, y) = (beta x, y) = [lambda](x, y) on the
     // order-r subgroup (msm_group.hip glv_split): |k1|, |k2| <= 2^(glv_bound_log2_x1000 / 1000)
     int glv_bound_log2_x1000;
     int prime_order;               // the whole curve group has order r (cofactor 1): phi = [lambda] everywhere
     const uint32_t* glv_lambda;    // plain integer, fr_words words
-    // out[i] = phi(P_i) = (beta x_i, y_i), compact affine like the n bases
-    void (*endo_points)(hipStream_t, const uint32_t* bases_affine, size_t n, uint32_t* out);
-    // test hook: signed digits of both halves, out[(2 i + half) * W + w]
-    void (*glv_digits)(hipStream_t, const uint32_t* scalars, size_t n, int mont, int c, int W, int32_t* out);
 
+    // ---- import / export / codecs ----------
     // libff (X, Y, Z) records -> compact affine (x, y); (0, 0) = infinity.
     // form_special != 0 promises Z == 1 or zero (multi_exp_base_form_special).
     void (*import_bases)(hipStream_t, const uint32_t* src, size_t stride_words, int form_special,
                          size_t n, uint32_t* dst_affine);
+    // compact affine -> libff special-form records (x, y, 1) / (0, 1, 0)
+    void (*export_affine)(hipStream_t, const uint32_t* src_affine, size_t n, uint32_t* dst_xyz);
+    // synthetic bases: dst[i] = (first + i + 1) * G::one(), compact affine
+    void (*gen_bases_seq)(hipStream_t, unsigned long long first, size_t n, uint32_t* dst_affine);
+    // out[i] = phi(P_i) = (beta x_i, y_i), compact affine like the n bases
+    void (*endo_points)(hipStream_t, const uint32_t* bases_affine, size_t n, uint32_t* out);
     // table[i*D + j] = [2^(j*c)] P_i (compact affine), j < D; tmp: n*D affine-sized slots of scratch
     void (*precompute_table)(hipStream_t, const uint32_t* bases_affine, size_t n, int c, int D, uint32_t* tmp,
                              uint32_t* table);
+    // libff FFI wire format (big-endian plain affine, ffi_serialization.tcc) <-> engine layout;
+    // *status receives OR of: 1 out of range, 2 not on curve, 4 not in the safe subgroup
+    void (*ffi_decode_points)(hipStream_t, const uint32_t* src_be, size_t n, uint32_t* dst_affine, uint32_t* status);
+    void (*ffi_decode_scalars)(hipStream_t, const uint32_t* src_be, size_t n, uint32_t* dst_plain, uint32_t* status);
+    void (*ffi_encode_point)(hipStream_t, const uint32_t* src_xyz_affine, uint32_t* dst_be);
+    // libff on-disk base records (binary, Montgomery, uncompressed) -> compact affine
+    void (*disk_decode)(hipStream_t, const uint32_t* src, size_t n, uint32_t* dst_affine);
+    // the compressed form of the same records (X with two flag bits, Y by square root);
+    // *status |= 2 where X is not the abscissa of a curve point
+    void (*disk_decode_compressed)(hipStream_t, const uint32_t* src, size_t n, uint32_t* dst_affine, uint32_t* status);
+
+    // ---- digits and sort ----------
+    // stats[0] += #scalars equal to zero, stats[1] += #scalars equal to one (multi_exp_filter_one_zero's
+    // classification, multiexp.tcc:713-733); mont: the scalars are Montgomery residues
+    void (*scalar_stats)(hipStream_t, const uint32_t* scalars, size_t n, int mont, uint32_t* stats);
+    // Scalars known to be short (amdmsm_*_short), kind as for sort_src's short form (mont as for `sort`).
+    // *out_bits = max(*out_bits, bit length of the longest scalar); one word, cleared by the caller
+    void (*scalar_bits)(hipStream_t, const void* scalars, int kind, size_t n, int mont, uint32_t* out_bits);
+    // out[i] = the scalar base i selects, copied as it is stored (same selection and guard as sort_src's selecting form)
+    void (*gather_scalars)(hipStream_t, const uint32_t* shared, size_t shared_n, const uint32_t* index, size_t offset,
+                           uint32_t* flag, size_t n, uint32_t* out);
     // histogram of signed radix-2^c digits: counts[w * B + (|d| - 1)]++
     void (*count)(hipStream_t, const uint32_t* scalars, size_t n, int mont, int c, int W, uint32_t* counts);
     // cursor[] holds exclusive bucket starts on entry, bucket ends on exit
     void (*scatter)(hipStream_t, const uint32_t* scalars, size_t n, int mont, int c, int W, uint32_t* cursor,
                     uint32_t* lists, size_t list_stride);
-    // stats[0] += #scalars equal to zero, stats[1] += #scalars equal to one (multi_exp_filter_one_zero's
-    // classification, multiexp.tcc:713-733); mont: the scalars are Montgomery residues
-    void (*scalar_stats)(hipStream_t, const uint32_t* scalars, size_t n, int mont, uint32_t* stats);
-    // LDS-staged two-level sort (same result as count + scatter): ends[w][b] and lists[w][...].
-    // coarse: W*(2^hb+1) words zeroed, cursor: W*2^hb words zeroed, digits/tmp_payload/lists:
-    // W*stride words each (digits may alias lists), tmp_key: W*stride 16-bit fine keys; big: sort_geometry().big_words words, the
-    // first 4 zeroed (oversized coarse bins, sorted cooperatively); needs c <= 22
-    void (*sort)(hipStream_t, const uint32_t* scalars, size_t n, int mont, int c, int W, uint32_t* coarse,
-                 uint32_t* cursor, int32_t* digits, uint32_t* tmp_payload, uint32_t* tmp_key, uint32_t* ends,
-                 uint32_t* lists, size_t stride, uint32_t* big, int mode, hipEvent_t after_coarse);
-    // after_coarse (may be null): recorded on the stream once the bandwidth-heavy first half (digit
-    // extraction, coarse partition) has been enqueued -- work queued behind it on another stream
-    // overlaps the LDS-bound fine pass
+    // LDS-staged two-level sort (same result as count + scatter) of the n scalars of `src` into ends[w][b] and
+    // lists[w][...] of `bufs`; needs c <= 22
     // mode 2: endomorphism split -- scalar i yields digit columns i (k1) and n + i (k2), so every
     // per-column array is sized for 2n columns (stride >= 2n) and payloads >= n name phi(P_(e - n))
     // mode 1 (flat): the W digits of scalar i become entries i*W .. i*W+W-1 of ONE list over one
     // bucket set (their payload indexes a precompute_table); then stride >= n*W, coarse / cursor /
     // ends are those of a single window and big is sized by sort_geometry(n*W, c, 1)
+    void (*sort)(hipStream_t, const sort_src& src, size_t n, int mont, int c, int W, const sort_bufs& bufs, int mode);
+    // The top window of the sort that `sort` runs for (mode, mont, c, W) over `columns` digit columns per window (every
+    // form but the short one, whose windows are sized by the data): returns the fine bits dropped there (sort_top_shift)
+    // -- the very value the launcher passes to its kernels -- and, in *tb (may be null), the bound on that window's index
+    // bits it rests on.  The bound covers every input the entry points admit: the halves of the split obey theirs for any
+    // scalar of fr_words words; Montgomery scalars come out of the conversion below r; plain scalars without the split may
+    // be any integer of fr_words words (k >= r is documented input), so there only the word length bounds the top window.
+    int (*sort_top_window)(int mode, int mont, int c, int W, size_t columns, int* tb);
+
+    // ---- accumulate and fix-up ----------
     // segmented bucket sums: lane t of window w owns list entries [t*S, (t+1)*S); buckets[]
     // must be zero-filled; part_first / part_last: W*T points, cont_bucket: W*T words.
     // Every array argument is the start of window 0 of the call, so a sub-range of windows is
@@ -191,6 +267,8 @@ struct group_vtable {
     void (*accumulate_fixup)(hipStream_t, const uint32_t* ends, uint32_t* buckets, uint32_t* part_first,
                              const uint32_t* part_last, const uint32_t* cont_bucket, uint32_t* queue, int W,
                              uint32_t B, uint32_t S, uint32_t T);
+
+    // ---- reduction and Horner ----------
     // M = B/L segments per window, G = min(M, reduce_fold):
     // out[w][g] = sum over segments s in [g*G, (g+1)*G) of sum_j (s*L + j + 1) * bucket[w][s*L + j]
     void (*reduce_segments)(hipStream_t, const uint32_t* buckets, int W, uint32_t B, uint32_t L, uint32_t* out);
@@ -213,22 +291,8 @@ struct group_vtable {
     void (*horner_batch)(hipStream_t, const uint32_t* window_sums, int k, int W, int c, int form, uint32_t* const* outs);
     // sum of k engine-Jacobian points
     void (*sum_points)(hipStream_t, const uint32_t* pts, int k, int form, uint32_t* out);
-    // synthetic bases: dst[i] = (first + i + 1) * G::one(), compact affine
-    void (*gen_bases_seq)(hipStream_t, unsigned long long first, size_t n, uint32_t* dst_affine);
-    // compact affine -> libff special-form records (x, y, 1) / (0, 1, 0)
-    void (*export_affine)(hipStream_t, const uint32_t* src_affine, size_t n, uint32_t* dst_xyz);
 
-    // libff FFI wire format (big-endian plain affine, ffi_serialization.tcc) <-> engine layout;
-    // *status receives OR of: 1 out of range, 2 not on curve, 4 not in the safe subgroup
-    void (*ffi_decode_points)(hipStream_t, const uint32_t* src_be, size_t n, uint32_t* dst_affine, uint32_t* status);
-    void (*ffi_decode_scalars)(hipStream_t, const uint32_t* src_be, size_t n, uint32_t* dst_plain, uint32_t* status);
-    void (*ffi_encode_point)(hipStream_t, const uint32_t* src_xyz_affine, uint32_t* dst_be);
-
-    // libff on-disk base records (binary, Montgomery, uncompressed) -> compact affine
-    void (*disk_decode)(hipStream_t, const uint32_t* src, size_t n, uint32_t* dst_affine);
-    // the compressed form of the same records (X with two flag bits, Y by square root);
-    // *status |= 2 where X is not the abscissa of a curve point
-    void (*disk_decode_compressed)(hipStream_t, const uint32_t* src, size_t n, uint32_t* dst_affine, uint32_t* status);
+    // ---- fixed-base ----------
     // fixed-base batch exponentiation: out[i] = (coeff *) scalars[i] * g via a window table
     // (get_window_table / windowed_exp / batch_exp[_with_coeff], multiexp.tcc:809-947);
     // gouter: outerc points, table: outerc * 2^window points (scratch: must be zero-filled), table_aff: as many compact
@@ -237,47 +301,7 @@ struct group_vtable {
                            size_t n, int mont, const uint32_t* coeff, int form, uint32_t* gouter, uint32_t* table,
                            uint32_t* table_aff, int build_table, uint32_t* out);
 
-    // ---- test hooks (parity of the primitives against the oracle) ----------
-    // coordinate-field op over arrays: 0 mul 1 sqr 2 add 3 sub 4 neg 5 inverse
-    void (*field_op)(hipStream_t, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n);
-    // group op over arrays of libff-layout records (Jacobian groups: same formulas as
-    // libff; bw6_761: converted through affine): 0 add 1 mixed_add 2 dbl; out in `form`
-    void (*group_op)(hipStream_t, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n, int form);
-    // signed digits of each scalar: out[i * W + w]
-    void (*digits)(hipStream_t, const uint32_t* scalars, size_t n, int mont, int c, int W, int32_t* out);
-    // throughput probes: 2*iters dependent Fq products / iters mixed additions per lane
-    // (inline_variant selects the fully inlined product where the TU was built with it)
-    void (*mul_bench)(hipStream_t, uint32_t* inout, size_t nthreads, int iters, int inline_variant);
-    void (*madd_bench)(hipStream_t, const uint32_t* pts_affine, uint32_t* out_xyz, size_t nthreads, int iters,
-                       int inline_variant);
-
-    // the group has the endomorphism phi above (0: MNT4 / MNT6, whose glv_* entries are placeholders and whose
-    // amdmsm_opts.endomorphism is ignored); the curve has a != 0 (the compressed-record decoders assume a = 0)
-    int has_endomorphism;
-    int coeff_a_nonzero;
-
-    // `sort` with the scalar of base i taken from a vector of shared_n scalars that several MSMs share: element
-    // index[i] of it (index != null; any order, repeats allowed), else element offset + i.  Lists, payloads and every
-    // scratch argument are those of `sort` for n bases.  An element at or past shared_n is not read: it counts as
-    // scalar 0 and sets *flag (one word, cleared by the caller) to nonzero.
-    void (*sort_sel)(hipStream_t, const uint32_t* shared, size_t shared_n, const uint32_t* index, size_t offset,
-                     uint32_t* flag, size_t n, int mont, int c, int W, uint32_t* coarse, uint32_t* cursor, int32_t* digits,
-                     uint32_t* tmp_payload, uint32_t* tmp_key, uint32_t* ends, uint32_t* lists, size_t stride, uint32_t* big,
-                     int mode);
-    // out[i] = the scalar base i selects, copied as it is stored (same selection and guard as sort_sel)
-    void (*gather_scalars)(hipStream_t, const uint32_t* shared, size_t shared_n, const uint32_t* index, size_t offset,
-                           uint32_t* flag, size_t n, uint32_t* out);
-
-    // Scalars known to be short (amdmsm_*_short).  kind = AMDMSM_SCALAR_*: 0 = Fr records (mont as for `sort`), else the
-    // bytes of one packed little-endian unsigned integer (1, 2, 4, 8; the pointer needs that alignment only).
-    // *out_bits = max(*out_bits, bit length of the longest scalar); one word, cleared by the caller
-    void (*scalar_bits)(hipStream_t, const void* scalars, int kind, size_t n, int mont, uint32_t* out_bits);
-    // `sort` (mode 0) with W sized for scalars below 2^limit_bits.  A scalar that is not counts as 0 and sets *flag (one
-    // word, cleared by the caller) to nonzero; limit_bits at the kind's full width tests nothing and flag may be null.
-    void (*sort_short)(hipStream_t, const void* scalars, int kind, int limit_bits, uint32_t* flag, size_t n, int mont, int c, int W,
-                       uint32_t* coarse, uint32_t* cursor, int32_t* digits, uint32_t* tmp_payload, uint32_t* tmp_key,
-                       uint32_t* ends, uint32_t* lists, size_t stride, uint32_t* big);
-
+    // ---- point-vector entries (smv, seg, fold, fft) ----------
     // Element-wise scalar multiplication out[i] = k_i * P_i (amdmsm_scalar_mul_vec), one lane per element.
     // smv_table: table[j * n + i] = (j + 1) * P_i as compact affine records, j < smv_entries ((0, 0) = infinity); tmp: as
     // many records of scratch.  smv_ladder: signed fixed-window ladder over that table; scalars as for `sort` (a plain
@@ -302,24 +326,6 @@ struct group_vtable {
                            size_t n_slices, uint32_t* sums);
     void (*seg_fold)(hipStream_t, const uint32_t* sums, const uint32_t* seg_first, size_t m, uint32_t* winsum);
     void (*seg_horner)(hipStream_t, const uint32_t* winsum, size_t m, int form, uint32_t* out);
-
-    // ---- probes of the field and point layers (tests/test_gpu_field_probe.py) ----------
-    // One library function (FPROBE_*) per element on the cold element type (impl 0) or the fully inlined one (impl 1):
-    // operands a, b, c, d (null where the op takes fewer) and out are n elements of el_words words, taken and stored as
-    // they are; flag (may be null): one word per element, the boolean the op returns (else 0).
-    void (*field_probe)(hipStream_t, int impl, int op, const uint32_t* a, const uint32_t* b, const uint32_t* c,
-                        const uint32_t* d, uint32_t* out, uint32_t* flag, size_t n);
-    // One extended-Jacobian function (XPROBE_*) per lane: acc and out are n (X, Y, ZZ, ZZZ) records of 4 * el_words
-    // words; pt: n compact affine records, or n more (X, Y, ZZ, ZZZ) records for XPROBE_ADD (null where unused)
-    void (*xyzz_probe)(hipStream_t, int impl, int op, const uint32_t* acc, const uint32_t* pt, uint32_t* out, size_t n);
-
-    // The top window of the sort that `sort` / `sort_sel` run for (mode, mont, c, W) over `columns` digit columns per
-    // window: returns the fine bits dropped there (sort_top_shift) -- the very value the launcher passes to its kernels --
-    // and, in *tb (may be null), the bound on that window's index bits it rests on.  The bound covers every input the
-    // entry points admit: the halves of the split obey theirs for any scalar of fr_words words; Montgomery scalars come
-    // out of the conversion below r; plain scalars without the split may be any integer of fr_words words (k >= r is
-    // documented input), so there only the word length bounds the top window.
-    int (*sort_top_window)(int mode, int mont, int c, int W, size_t columns, int* tb);
 
     // Fold of k point vectors by k shared scalars, out[i] = sum_j s_j * P_j[i] (amdmsm_fold_vec), k <= FOLD_MAX_K.
     // fold_digits: the signed 4-bit digits of the k scalars -- HOST memory, k records of fr_words words, passed to the
@@ -346,7 +352,32 @@ struct group_vtable {
     void (*fft_gather)(hipStream_t, const uint32_t* in_affine, size_t b0, size_t cn, int rsh, uint32_t* dst_affine);
     void (*fft_butterfly)(hipStream_t, const uint32_t* table, size_t cn, const uint32_t* in_affine, size_t b0, int rsh,
                           const uint32_t* twiddles, int mont, size_t half, uint32_t* out);
-    const uint32_t* fr_modulus;    // the scalar-field modulus r, plain integer, fr_words words
+
+    // ---- test hooks (parity of the primitives against the oracle) ----------
+    // coordinate-field op over arrays: 0 mul 1 sqr 2 add 3 sub 4 neg 5 inverse
+    void (*field_op)(hipStream_t, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n);
+    // group op over arrays of libff-layout records (Jacobian groups: same formulas as
+    // libff; bw6_761: converted through affine): 0 add 1 mixed_add 2 dbl; out in `form`
+    void (*group_op)(hipStream_t, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n, int form);
+    // signed digits of each scalar: out[i * W + w]
+    void (*digits)(hipStream_t, const uint32_t* scalars, size_t n, int mont, int c, int W, int32_t* out);
+    // signed digits of both halves of the endomorphism split, out[(2 i + half) * W + w]
+    void (*glv_digits)(hipStream_t, const uint32_t* scalars, size_t n, int mont, int c, int W, int32_t* out);
+    // throughput probes: 2*iters dependent Fq products / iters mixed additions per lane
+    // (inline_variant selects the fully inlined product where the TU was built with it)
+    void (*mul_bench)(hipStream_t, uint32_t* inout, size_t nthreads, int iters, int inline_variant);
+    void (*madd_bench)(hipStream_t, const uint32_t* pts_affine, uint32_t* out_xyz, size_t nthreads, int iters,
+                       int inline_variant);
+
+    // ---- probes of the field and point layers (tests/test_gpu_field_probe.py) ----------
+    // One library function (FPROBE_*) per element on the cold element type (impl 0) or the fully inlined one (impl 1):
+    // operands a, b, c, d (null where the op takes fewer) and out are n elements of el_words words, taken and stored as
+    // they are; flag (may be null): one word per element, the boolean the op returns (else 0).
+    void (*field_probe)(hipStream_t, int impl, int op, const uint32_t* a, const uint32_t* b, const uint32_t* c,
+                        const uint32_t* d, uint32_t* out, uint32_t* flag, size_t n);
+    // One extended-Jacobian function (XPROBE_*) per lane: acc and out are n (X, Y, ZZ, ZZZ) records of 4 * el_words
+    // words; pt: n compact affine records, or n more (X, Y, ZZ, ZZZ) records for XPROBE_ADD (null where unused)
+    void (*xyzz_probe)(hipStream_t, int impl, int op, const uint32_t* acc, const uint32_t* pt, uint32_t* out, size_t n);
 };
 constexpr int FOLD_MAX_K = 8;
 constexpr size_t FOLD_DIGIT_BYTES = 2048;   // 2 FOLD_MAX_K rows of at most 100 bytes

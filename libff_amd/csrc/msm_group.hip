@@ -82,9 +82,10 @@ static_assert(GP::COEFF_A == 0, "the reduced-radix and lane-pair accumulation lo
 #ifndef AMDMSM_ACC_WAVES
 #define AMDMSM_ACC_WAVES 1
 #endif
-// Overlap mode (engine.cpp amdmsm_ctx::bulk_stream): AMDMSM_OVERLAP_OK marks a group whose tail kernels are built to
-// fit beside an accumulation that leaves one workgroup per CU free -- AMDMSM_TAIL_WAVES waves per SIMD as their
-// register budget (4 -> 128 VGPRs, what three accumulation waves of 128 leave of a SIMD's 512)
+// Overlap mode (engine.cpp amdmsm_ctx::bulk_stream): AMDMSM_OVERLAP_OK marks a group whose accumulation may be launched
+// one workgroup per CU short of full occupancy (group_vtable::accumulate_overlap_ok, where ACC_OVERLAP_LDS is nonzero
+// too).  It says nothing about the tail kernels' registers any more: no group caps them, and AMDMSM_TAIL_WAVES -- their
+// minimum waves per SIMD -- stays at 1 unless an experiment build sets it.
 #ifndef AMDMSM_OVERLAP_OK
 #define AMDMSM_OVERLAP_OK 0
 #endif
@@ -684,11 +685,7 @@ __global__ void __launch_bounds__(SORT_TPB) k_sort_digits(const uint32_t* __rest
 // redirected; digit columns and payloads stay indexed by the base i.  An element at or past shared_n is never
 // dereferenced: it counts as scalar 0 and raises *flag, which the engine turns into AMDMSM_ERR_BAD_ARG.
 // Every lane still loads one whole scalar with 16-byte (10-word fields: 8-byte) loads, as the streaming form does.
-struct scalar_sel {
-    const uint32_t* index;   // null: slice
-    size_t offset, shared_n;
-    uint32_t* flag;
-};
+using scalar_sel = sort_src::selection;
 AMDMSM_DEV void load_scalar_sel(uint32_t (&s)[FRW], const uint32_t* shared, const scalar_sel& sel, size_t i, int mont) {
     const size_t idx = sel.index ? (size_t)sel.index[i] : sel.offset + i;
     if (idx >= sel.shared_n) {
@@ -1147,9 +1144,8 @@ __global__ void __launch_bounds__(NT, NT == SORT_TPB ? (PER < 16 ? SORT_WAVES_2W
         return;
     }
     const uint32_t nch = (m + chunk_cap - 1) / chunk_cap;
-    const bool single = false;   // (one-chunk bins took the path above)
     uint32_t* ch = reinterpret_cast<uint32_t*>(st_fine + chunk_cap);   // [nch][nfine]
-    const bool split_hist = !single && (size_t)nch * nfine <= perchunk_words;
+    const bool split_hist = (size_t)nch * nfine <= perchunk_words;   // (nch >= 2: one-chunk bins took the path above)
     if (split_hist) {
         for (uint32_t j = threadIdx.x; j < nch * nfine; j += NT) ch[j] = 0;
         __syncthreads();
@@ -1177,18 +1173,14 @@ __global__ void __launch_bounds__(NT, NT == SORT_TPB ? (PER < 16 ? SORT_WAVES_2W
     for (uint32_t c0 = 0; c0 < m; c0 += chunk_cap, ++cidx) {
         const uint32_t cm = (m - c0 < chunk_cap) ? m - c0 : chunk_cap;
         const uint32_t* hist_c = split_hist ? ch + cidx * nfine : chist;   // this chunk's histogram
-        if (single) {
-            for (uint32_t j = threadIdx.x; j < nfine; j += NT) cstart[j] = ccur[j] = fstart[j];
-        } else {
-            if (!split_hist) {
-                for (uint32_t j = threadIdx.x; j < nfine; j += NT) chist[j] = 0;
-                __syncthreads();
-                for (uint32_t k = threadIdx.x; k < cm; k += NT) atomicAdd(&chist[key[c0 + k] & fmask], 1u);
-                __syncthreads();
-            }
-            block_exclusive_scan<NT>(hist_c, cstart, nfine, tmp);
-            for (uint32_t j = threadIdx.x; j < nfine; j += NT) ccur[j] = cstart[j];
+        if (!split_hist) {
+            for (uint32_t j = threadIdx.x; j < nfine; j += NT) chist[j] = 0;
+            __syncthreads();
+            for (uint32_t k = threadIdx.x; k < cm; k += NT) atomicAdd(&chist[key[c0 + k] & fmask], 1u);
+            __syncthreads();
         }
+        block_exclusive_scan<NT>(hist_c, cstart, nfine, tmp);
+        for (uint32_t j = threadIdx.x; j < nfine; j += NT) ccur[j] = cstart[j];
         __syncthreads();
         for (uint32_t k = threadIdx.x; k < cm; k += NT) {
             const uint32_t f = key[c0 + k] & fmask;
@@ -3903,11 +3895,6 @@ void l_scatter(hipStream_t st, const uint32_t* scalars, size_t n, int mont, int 
     if (!n) return;
     hipLaunchKernelGGL(k_scatter, dim3(blocks_for(n)), dim3(TPB), 0, st, scalars, n, mont, c, W, cursor, lists, list_stride);
 }
-// the short-scalar form of the digit pass (group_vtable::sort_short); scalars then points at elements of that kind
-struct short_src {
-    int kind, limit_bits;
-    uint32_t* flag;
-};
 template <int WB>
 size_t packed_items(const void* p, size_t n) { return packed_split<WB>(p, n).items(); }
 // group_vtable::sort_top_window; flat lists have one window
@@ -3949,13 +3936,12 @@ uint32_t digit_pass_workgroups(const void* kernel, size_t lds) {
     a = answer{dev, kernel, lds, (uint32_t)cus * (uint32_t)per_cu};
     return a.wgs;
 }
-// digits / lists may alias (digits are dead once k_sort_coarse has run)
-// sel != null: the selecting form of the digit pass (group_vtable::sort_sel); everything behind it is the same
-void sort_launch(hipStream_t st, const uint32_t* scalars, size_t n, int mont, int c, int W, uint32_t* coarse,
-                 uint32_t* cursor, int32_t* digits, uint32_t* tmp_payload, uint32_t* tmp_key, uint32_t* ends, uint32_t* lists,
-                 size_t stride, uint32_t* big, int mode, hipEvent_t after_coarse, const scalar_sel* sel,
-                 const short_src* ss = nullptr) {
+// group_vtable::sort.  The form of src picks the digit pass; everything behind it is the same
+void l_sort(hipStream_t st, const sort_src& src, size_t n, int mont, int c, int W, const sort_bufs& b, int mode) {
     if (!n) return;
+    const uint32_t* scalars = (const uint32_t*)src.scalars;
+    const sort_src::short_form* ss = src.form == sort_src::SHORT ? &src.shrt : nullptr;
+    const scalar_sel* sel = src.form == sort_src::SELECTED ? &src.sel : nullptr;
     // mode 1 (flat): one list of n*W entries (entry i*W + j = digit j of scalar i), one bucket set
     // mode 2 (endomorphism split): 2n columns of W digits
     const bool flat = mode == 1;
@@ -3983,7 +3969,7 @@ void sort_launch(hipStream_t st, const uint32_t* scalars, size_t n, int mont, in
         const digit_grid dg = sort_digit_grid(items, K ? 256u : (uint32_t)SORT_TPB,                                         \
                                               digit_pass_workgroups((const void*)k_sort_digits_short<K>, lds));             \
         hipLaunchKernelGGL(k_sort_digits_short<K>, dim3(dg.grid), dim3(SORT_TPB), lds, st, (const void*)scalars, n, mont, c, W, hb, \
-                           dg.block, digits, stride, coarse, ss->limit_bits, ss->flag);                                   \
+                           dg.block, b.digits, b.stride, b.coarse, ss->limit_bits, ss->flag);                                   \
     } while (0)
         if (k == 1) AMDMSM_LAUNCH_SHORT(1);
         else if (k == 2) AMDMSM_LAUNCH_SHORT(2);
@@ -3993,22 +3979,21 @@ void sort_launch(hipStream_t st, const uint32_t* scalars, size_t n, int mont, in
 #undef AMDMSM_LAUNCH_SHORT
     } else if (sel) {
         const digit_grid dg = sort_digit_grid(n, SORT_TPB, digit_pass_workgroups((const void*)k_sort_digits_sel, lds));
-        hipLaunchKernelGGL(k_sort_digits_sel, dim3(dg.grid), dim3(SORT_TPB), lds, st, scalars, n, mont, c, W, hb, digits, stride,
-                           coarse, mode, sel->index, sel->offset, sel->shared_n, sel->flag, dtop);
+        hipLaunchKernelGGL(k_sort_digits_sel, dim3(dg.grid), dim3(SORT_TPB), lds, st, scalars, n, mont, c, W, hb, b.digits, b.stride,
+                           b.coarse, mode, sel->index, sel->offset, sel->shared_n, sel->flag, dtop);
     } else {
         const digit_grid dg = sort_digit_grid(n, SORT_TPB, digit_pass_workgroups((const void*)k_sort_digits, lds));
-        hipLaunchKernelGGL(k_sort_digits, dim3(dg.grid), dim3(SORT_TPB), lds, st, scalars, n, mont, c, W, hb, digits, stride,
-                           coarse, mode, dtop);
+        hipLaunchKernelGGL(k_sort_digits, dim3(dg.grid), dim3(SORT_TPB), lds, st, scalars, n, mont, c, W, hb, b.digits, b.stride,
+                           b.coarse, mode, dtop);
     }
-    sort_key_t* tmp_key16 = reinterpret_cast<sort_key_t*>(tmp_key);   // W * stride fine keys
+    sort_key_t* tmp_key16 = reinterpret_cast<sort_key_t*>(b.tmp_key);   // W * stride fine keys
     const dim3 coarse_grid((unsigned)((ne + SORT_TILE - 1) / SORT_TILE), We);
     if (c <= 17)   // the bucket index has c - 1 bits
-        hipLaunchKernelGGL(k_sort_coarse<unsigned short>, coarse_grid, dim3(SORT_TPB), 0, st, digits, ne, stride, c, hb, coarse,
-                           cursor, tmp_payload, tmp_key16, dtop);
+        hipLaunchKernelGGL(k_sort_coarse<unsigned short>, coarse_grid, dim3(SORT_TPB), 0, st, b.digits, ne, b.stride, c, hb, b.coarse,
+                           b.cursor, b.tmp_payload, tmp_key16, dtop);
     else
-        hipLaunchKernelGGL(k_sort_coarse<uint32_t>, coarse_grid, dim3(SORT_TPB), 0, st, digits, ne, stride, c, hb, coarse,
-                           cursor, tmp_payload, tmp_key16, dtop);
-    if (after_coarse) (void)hipEventRecord(after_coarse, st);
+        hipLaunchKernelGGL(k_sort_coarse<uint32_t>, coarse_grid, dim3(SORT_TPB), 0, st, b.digits, ne, b.stride, c, hb, b.coarse,
+                           b.cursor, b.tmp_payload, tmp_key16, dtop);
     // per-chunk histograms of a bin of up to 16 chunks, where they fit beside the staging area (<= 32 KiB)
     static const bool split_hist = !(getenv("AMDMSM_SORT_SPLIT_HIST") && atoi(getenv("AMDMSM_SORT_SPLIT_HIST")) == 0);
     uint32_t perchunk_words = 0;
@@ -4035,8 +4020,8 @@ void sort_launch(hipStream_t st, const uint32_t* scalars, size_t n, int mont, in
     }();
     (void)reported;
 #define AMDMSM_LAUNCH_FINE(NT, PER)                                                                                          \
-    hipLaunchKernelGGL((k_sort_fine<NT, PER>), dim3(nbin, We), dim3(NT), fine_lds, st, tmp_payload, tmp_key16, coarse, stride, c, \
-                       hb, sg.chunk_cap, sg.big_thresh, sg.big_cap, perchunk_words, big, ends, lists, dtop)
+    hipLaunchKernelGGL((k_sort_fine<NT, PER>), dim3(nbin, We), dim3(NT), fine_lds, st, b.tmp_payload, tmp_key16, b.coarse, b.stride, c, \
+                       hb, sg.chunk_cap, sg.big_thresh, sg.big_cap, perchunk_words, b.big, b.ends, b.lists, dtop)
     if (sg.chunk_cap <= 4096)
         AMDMSM_LAUNCH_FINE(256, 16);
     else if (sg.chunk_cap <= 8192)
@@ -4046,30 +4031,10 @@ void sort_launch(hipStream_t st, const uint32_t* scalars, size_t n, int mont, in
     else
         AMDMSM_LAUNCH_FINE(SORT_TPB, 16);
 #undef AMDMSM_LAUNCH_FINE
-    hipLaunchKernelGGL(k_sort_big_hist, dim3(512), dim3(SORT_TPB), 0, st, tmp_key16, coarse, stride, c, hb, big, ends, wtop, dtop);
-    hipLaunchKernelGGL(k_sort_big_scan, dim3(256), dim3(SORT_TPB), 0, st, coarse, c, hb, sg.big_cap, big, ends, wtop, dtop);
-    hipLaunchKernelGGL(k_sort_big_scatter, dim3(512), dim3(SORT_TPB), big_lds, st, tmp_payload, tmp_key16, coarse, stride, c,
-                       hb, sg.big_cap, big, lists, wtop, dtop);
-}
-void l_sort(hipStream_t st, const uint32_t* scalars, size_t n, int mont, int c, int W, uint32_t* coarse,
-            uint32_t* cursor, int32_t* digits, uint32_t* tmp_payload, uint32_t* tmp_key, uint32_t* ends, uint32_t* lists,
-            size_t stride, uint32_t* big, int mode, hipEvent_t after_coarse) {
-    sort_launch(st, scalars, n, mont, c, W, coarse, cursor, digits, tmp_payload, tmp_key, ends, lists, stride, big, mode,
-                after_coarse, nullptr);
-}
-void l_sort_sel(hipStream_t st, const uint32_t* shared, size_t shared_n, const uint32_t* index, size_t offset, uint32_t* flag,
-                size_t n, int mont, int c, int W, uint32_t* coarse, uint32_t* cursor, int32_t* digits, uint32_t* tmp_payload,
-                uint32_t* tmp_key, uint32_t* ends, uint32_t* lists, size_t stride, uint32_t* big, int mode) {
-    const scalar_sel sel{index, offset, shared_n, flag};
-    sort_launch(st, shared, n, mont, c, W, coarse, cursor, digits, tmp_payload, tmp_key, ends, lists, stride, big, mode,
-                nullptr, &sel);
-}
-void l_sort_short(hipStream_t st, const void* scalars, int kind, int limit_bits, uint32_t* flag, size_t n, int mont, int c, int W,
-                  uint32_t* coarse, uint32_t* cursor, int32_t* digits, uint32_t* tmp_payload, uint32_t* tmp_key, uint32_t* ends,
-                  uint32_t* lists, size_t stride, uint32_t* big) {
-    const short_src ss{kind, limit_bits, flag};
-    sort_launch(st, (const uint32_t*)scalars, n, mont, c, W, coarse, cursor, digits, tmp_payload, tmp_key, ends, lists, stride, big, 0,
-                nullptr, nullptr, &ss);
+    hipLaunchKernelGGL(k_sort_big_hist, dim3(512), dim3(SORT_TPB), 0, st, tmp_key16, b.coarse, b.stride, c, hb, b.big, b.ends, wtop, dtop);
+    hipLaunchKernelGGL(k_sort_big_scan, dim3(256), dim3(SORT_TPB), 0, st, b.coarse, c, hb, sg.big_cap, b.big, b.ends, wtop, dtop);
+    hipLaunchKernelGGL(k_sort_big_scatter, dim3(512), dim3(SORT_TPB), big_lds, st, b.tmp_payload, tmp_key16, b.coarse, b.stride, c,
+                       hb, sg.big_cap, b.big, b.lists, wtop, dtop);
 }
 void l_scalar_bits(hipStream_t st, const void* scalars, int kind, size_t n, int mont, uint32_t* out) {
     if (!n) return;
@@ -4390,17 +4355,37 @@ void l_fft_butterfly(hipStream_t st, const uint32_t* table, size_t cn, const uin
 }
 
 const group_vtable g_vt = {
-    GP::CURVE, GP::GROUP, FRW, EW, FQ::N, FR::BITS, GP::LIBFF_PROJECTIVE ? 1 : 0, (int)RED_FOLD, ZZS, FR::R,
-    GLV::BOUND_LOG2_X1000, GP::SUBGROUP_CHECK == 0 ? 1 : 0, GLV::LAMBDA, l_endo_points, l_glv_digits,
-    l_import_bases, l_precompute_table, l_count, l_scatter, l_scalar_stats, l_sort, l_accumulate, l_accumulate_resident_lanes, (AMDMSM_OVERLAP_OK && ACC_OVERLAP_LDS) ? 1 : 0, l_accumulate_fixup, l_reduce_segments, l_sum_butterfly, l_sum_block, l_reduce_rowcol, l_horner, l_horner_batch, l_sum_points,
-    l_gen_bases_seq, l_export_affine, l_ffi_decode_points, l_ffi_decode_scalars, l_ffi_encode_point, l_disk_decode, l_disk_decode_compressed, l_fixed_base_exp, l_field_op, l_group_op, l_digits, l_mul_bench, l_madd_bench,
-    GP::HAS_ENDO ? 1 : 0, GP::COEFF_A != 0 ? 1 : 0, l_sort_sel, l_gather_scalars, l_scalar_bits, l_sort_short,
-    SMV_T, l_smv_table, l_smv_ladder,
-    SMV_DIGITS, SMV_DS, l_seg_digits, l_seg_accumulate, l_seg_fold, l_seg_horner,
-    l_field_probe, l_xyzz_probe,
-    l_sort_top_window,
-    SMV_DS, l_fold_digits, l_fold_ladder,
-    l_fft_gather, l_fft_butterfly, FR::P,
+    // constants of the group
+    .curve = GP::CURVE, .group = GP::GROUP, .fr_words = FRW, .el_words = EW, .fq_words = FQ::N, .fr_bits = FR::BITS,
+    .projective = GP::LIBFF_PROJECTIVE ? 1 : 0, .reduce_fold = (int)RED_FOLD, .bucket_words = ZZS,
+    .fr_one_mont = FR::R, .fr_modulus = FR::P,
+    .has_endomorphism = GP::HAS_ENDO ? 1 : 0, .coeff_a_nonzero = GP::COEFF_A != 0 ? 1 : 0,
+    .glv_bound_log2_x1000 = GLV::BOUND_LOG2_X1000, .prime_order = GP::SUBGROUP_CHECK == 0 ? 1 : 0, .glv_lambda = GLV::LAMBDA,
+    // import / export / codecs
+    .import_bases = l_import_bases, .export_affine = l_export_affine, .gen_bases_seq = l_gen_bases_seq,
+    .endo_points = l_endo_points, .precompute_table = l_precompute_table,
+    .ffi_decode_points = l_ffi_decode_points, .ffi_decode_scalars = l_ffi_decode_scalars, .ffi_encode_point = l_ffi_encode_point,
+    .disk_decode = l_disk_decode, .disk_decode_compressed = l_disk_decode_compressed,
+    // digits and sort
+    .scalar_stats = l_scalar_stats, .scalar_bits = l_scalar_bits, .gather_scalars = l_gather_scalars,
+    .count = l_count, .scatter = l_scatter, .sort = l_sort, .sort_top_window = l_sort_top_window,
+    // accumulate and fix-up
+    .accumulate = l_accumulate, .accumulate_resident_lanes = l_accumulate_resident_lanes,
+    .accumulate_overlap_ok = (AMDMSM_OVERLAP_OK && ACC_OVERLAP_LDS) ? 1 : 0, .accumulate_fixup = l_accumulate_fixup,
+    // reduction and Horner
+    .reduce_segments = l_reduce_segments, .sum_butterfly = l_sum_butterfly, .sum_block = l_sum_block,
+    .reduce_rowcol = l_reduce_rowcol, .horner = l_horner, .horner_batch = l_horner_batch, .sum_points = l_sum_points,
+    // fixed-base
+    .fixed_base_exp = l_fixed_base_exp,
+    // point-vector entries
+    .smv_entries = SMV_T, .smv_table = l_smv_table, .smv_ladder = l_smv_ladder,
+    .seg_windows = SMV_DIGITS, .seg_digit_stride = SMV_DS, .seg_digits = l_seg_digits, .seg_accumulate = l_seg_accumulate,
+    .seg_fold = l_seg_fold, .seg_horner = l_seg_horner,
+    .fold_digit_stride = SMV_DS, .fold_digits = l_fold_digits, .fold_ladder = l_fold_ladder,
+    .fft_gather = l_fft_gather, .fft_butterfly = l_fft_butterfly,
+    // test hooks and probes
+    .field_op = l_field_op, .group_op = l_group_op, .digits = l_digits, .glv_digits = l_glv_digits,
+    .mul_bench = l_mul_bench, .madd_bench = l_madd_bench, .field_probe = l_field_probe, .xyzz_probe = l_xyzz_probe,
 };
 
 }  // namespace
