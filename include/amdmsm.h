@@ -332,6 +332,16 @@ int amdmsm_fr_powers_device(amdmsm_ctx *ctx, int curve, const void *base, size_t
    (one record in host memory) may be NULL: 0 and 1.  d_out may be any of the inputs.  Enqueued, not synchronised */
 int amdmsm_fr_muladd_device(amdmsm_ctx *ctx, int curve, size_t n, const void *d_a, const void *d_b, const void *d_c,
                             const void *k, const amdmsm_opts *opts, void *d_out);
+/* d_out[i] = sum over j < k of s_j * v_j[i], i < n: a linear combination of 1 <= k <= 4 resident vectors with scalars
+   from the host -- the key vectors (beta At + alpha Bt + Ct) / delta of a generator, the blinding terms of a witness
+   map.  d_v: k device vectors, listed in host memory; scalars: k packed records in host memory; vectors and scalars in
+   the form opts->scalars_plain says, n <= 2^28.  d_out may be any one of the v_j as a whole (a vector may also be listed
+   twice); any other overlap with d_out is refused.  One lane per record, one launch; enqueued, not synchronised.
+   AMDMSM_ERR_BAD_ARG, before anything is launched and before the context is looked at, for k out of range, a scalar not
+   below r, a null scalars or d_v, and with n > 0 a null or misaligned vector; n = 0 succeeds and writes nothing.  With
+   timing enabled: [1] the kernel */
+int amdmsm_fr_lincomb_device(amdmsm_ctx *ctx, int curve, size_t n, int k, const void *const *d_v, const void *scalars,
+                             const amdmsm_opts *opts, void *d_out);
 
 /* Scans and batch inversion over a vector of Fr records -- the operations that carry a value from one record to the
  * next: prefix products (the z vector of a grand product), prefix sums, Horner evaluation and synthetic division by
@@ -457,6 +467,29 @@ int amdmsm_fr_domain_divide_by_z(amdmsm_ctx *ctx, int curve, size_t m, const voi
                                  const amdmsm_opts *opts, void *out);
 int amdmsm_fr_domain_divide_by_z_device(amdmsm_ctx *ctx, int curve, size_t m, const void *d_values, const void *coset,
                                         const amdmsm_opts *opts, void *d_out);
+/* The Lagrange vector of the domain of m points at a point t -- what libfqfft's evaluate_all_lagrange_polynomials(t)
+ * answers, the u of libsnark's r1cs_to_qap_instance_map_with_evaluation, and the weights that evaluate a polynomial held
+ * in evaluation form, A(t) = sum over j of L_j(t) A(x_j):
+ *     out[j] = L_j(t) = product over k != j of (t - x_k) / (x_j - x_k),   j < m,
+ * on the points x_j above, in their order; for t = x_k the unit vector e_k.  Restated from that property, not checked
+ * against libfqfft's code: the point order is the contract.
+ *   t   one record in host memory in the form opts->scalars_plain says, as the coset of amdmsm_fr_domain_fft; any
+ *       value below r, 0 and the points of the domain included.  The results are in the same form
+ * With Z(t) != 0 one sweep writes the m denominators 1 / L_j(t) -- (t / x_j - 1) times m / Z(t) on a basic domain; on a
+ * step domain times B (rho^(j mod K) - w^S) / Z(t) below B, rho = w^(2 S), K = B / S, and times -2 S w^S / Z(t) from B
+ * on -- from the cached powers of w and K factors built as those of the division by Z, and the batch inversion above
+ * inverts them in place: one field inversion on the device and one, of Z(t), on the host, whatever m (DESIGN section
+ * 24).  With Z(t) = 0 the same sweep compares x_j with t and writes the unit vector; nothing is inverted.
+ * The device entry is enqueued on opts->stream (or the context's) and not synchronised, d_out aligned as the vectors of
+ * amdmsm_fr_fft_device; the host entry runs, downloads and synchronises.  Workspace from the context's slots.
+ * Refused before anything is launched or written and before the context is looked at, amdmsm_last_error naming the
+ * argument: AMDMSM_ERR_UNSUPPORTED for an unknown curve and the domains left out; AMDMSM_ERR_TOO_LARGE for m > 2^28;
+ * AMDMSM_ERR_BAD_ARG for an m that is no domain size (the message names the size amdmsm_fr_domain chooses), m < 2, a
+ * null t or output, a t not below r, a misaligned d_out, a wrong opts->struct_size.
+ * With timing enabled (amdmsm_get_timings): [0] the tables, [1] the kernels, [2] the download (host entry),
+ * [AMDMSM_PH_TOTAL] the call. */
+int amdmsm_fr_domain_lagrange_device(amdmsm_ctx *ctx, int curve, size_t m, const void *t, const amdmsm_opts *opts, void *d_out);
+int amdmsm_fr_domain_lagrange(amdmsm_ctx *ctx, int curve, size_t m, const void *t, const amdmsm_opts *opts, void *out);
 
 /* Sparse matrix times Fr vector -- the rows <A_i, z>, <B_i, z>, <C_i, z> of a constraint system on a resident
  * assignment, the vectors the transforms above start from -- and any other sparse linear map over Fr:
@@ -510,6 +543,20 @@ int amdmsm_fr_matrix_free(amdmsm_ctx *ctx, uint64_t mat);
 #define AMDMSM_FR_MATRIX_PLAN_WORDS 16
 int amdmsm_plan_fr_matrix(int curve, size_t n_rows, size_t n_cols, const uint64_t *offsets, const uint32_t *cols,
                           const void *coeffs, int coeffs_plain, size_t out[AMDMSM_FR_MATRIX_PLAN_WORDS]);
+/* The transposed map: the arguments are the CSR arrays of a matrix M exactly as amdmsm_fr_matrix_load takes them, the
+ * handle is that of its transpose -- n_cols rows and n_rows columns, so that
+ *     amdmsm_fr_matrix_apply*(mat, u, n_x >= n_rows, out, n_out >= n_cols):  out[c] = sum over the entries (i, c) of M of coeff * u[i]
+ * which with u the Lagrange vector of a domain at t gives At, Bt, Ct of r1cs_to_qap_instance_map_with_evaluation (the
+ * input-consistency terms At[i] = u[num_constraints + i] are rows of M the caller adds).  Validation, codes and messages
+ * are those of the plain load and name rows and entries of M as given.  A stable counting sort on the host then gives
+ * the CSR of the transpose -- within a row the entries in ascending row of M -- through an index per entry, the
+ * coefficients are read where the caller has them; zero coefficients are dropped, and from there the handle is an
+ * ordinary one in every respect, AMDMSM_FR_MATRIX_NAIVE=1 included.  The plan twin reports what amdmsm_plan_fr_matrix
+ * reports for the transpose. */
+int amdmsm_fr_matrix_load_transposed(amdmsm_ctx *ctx, int curve, size_t n_rows, size_t n_cols, const uint64_t *offsets,
+                                     const uint32_t *cols, const void *coeffs, int coeffs_plain, uint64_t *mat);
+int amdmsm_plan_fr_matrix_transposed(int curve, size_t n_rows, size_t n_cols, const uint64_t *offsets, const uint32_t *cols,
+                                     const void *coeffs, int coeffs_plain, size_t out[AMDMSM_FR_MATRIX_PLAN_WORDS]);
 
 /* Segmented MSM: m sums in one call, out[j] = sum of scalars[i] * base(i) over offsets[j] <= i < offsets[j + 1] -- the
  * shape of k proofs verified as a batch (sum of input_i * IC_i per proof), of row or column commitments, of the cross

@@ -4199,11 +4199,13 @@ bool fr_below_modulus(const fr_vtable *f, const uint32_t *w) {
 }
 
 // What plan and load share: the argument rules and the layout.  Nothing is allocated on the device before it returns 0.
+// tr: the layout is that of the transpose, which is left there; the rules and what they name are those of M as given.
 int frm_prepare(amdmsm_ctx *ctx, const fr_vtable *f, size_t n_rows, size_t n_cols, const uint64_t *offsets, const uint32_t *cols,
-                const void *coeffs, int coeffs_plain, frm_layout &L) {
+                const void *coeffs, int coeffs_plain, frm_layout &L, frm_transposed *tr = nullptr) {
     std::string err;
     const int bad = frm_validate(n_rows, n_cols, offsets, cols, coeffs != nullptr, err);
     if (bad) return fail(ctx, bad == 2 ? AMDMSM_ERR_TOO_LARGE : AMDMSM_ERR_BAD_ARG, err);
+    if (tr) frm_transpose(n_rows, n_cols, offsets, cols, *tr);
     // 1 and r - 1 in the form the coefficients come in
     const fr_rec one = coeffs_plain ? fr_small(1) : fr_from_words(f, f->one), minus_one = fr_r_minus(f, one), zero;
     const size_t rec = (size_t)f->words * 4;
@@ -4217,9 +4219,21 @@ int frm_prepare(amdmsm_ctx *ctx, const fr_vtable *f, size_t n_rows, size_t n_col
         if (!memcmp(w, zero.v, rec)) return FRM_ZERO;
         return FRM_GEN;
     };
-    if (!frm_build(n_rows, offsets, cols, cls_of, frm_env("AMDMSM_FR_MATRIX_WAVE_ROW"), frm_env("AMDMSM_FR_MATRIX_SPLIT_ROW"), L,
-                   bad_entry))
-        return fail(ctx, AMDMSM_ERR_BAD_ARG, "entry " + std::to_string(bad_entry) + ": coefficient >= r");
+    const uint32_t want_wave = frm_env("AMDMSM_FR_MATRIX_WAVE_ROW"), want_split = frm_env("AMDMSM_FR_MATRIX_SPLIT_ROW");
+    bool ok;
+    if (tr) {
+        ok = frm_build(n_cols, tr->offsets.data(), tr->rows.data(), [&](uint64_t k) { return cls_of(tr->src[k]); }, want_wave,
+                       want_split, L, bad_entry);
+        // the entry a plain load would have named: the first in M's order
+        for (uint64_t k = 0; !ok && k < L.nnz; ++k)
+            if (cls_of(k) == FRM_BAD) {
+                bad_entry = k;
+                break;
+            }
+    } else {
+        ok = frm_build(n_rows, offsets, cols, cls_of, want_wave, want_split, L, bad_entry);
+    }
+    if (!ok) return fail(ctx, AMDMSM_ERR_BAD_ARG, "entry " + std::to_string(bad_entry) + ": coefficient >= r");
     return AMDMSM_OK;
 }
 
@@ -4314,17 +4328,15 @@ int frm_run(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, fr_matrix *m, c
     return AMDMSM_OK;
 }
 
-}   // namespace
-
-extern "C" {
-
-int amdmsm_plan_fr_matrix(int curve, size_t n_rows, size_t n_cols, const uint64_t *offsets, const uint32_t *cols, const void *coeffs,
-                          int coeffs_plain, size_t out[AMDMSM_FR_MATRIX_PLAN_WORDS]) {
+// plan and load of a matrix or, with `transposed`, of its transpose: the handle then has n_cols rows and n_rows columns
+int frm_plan(int curve, size_t n_rows, size_t n_cols, const uint64_t *offsets, const uint32_t *cols, const void *coeffs,
+             int coeffs_plain, bool transposed, size_t *out) {
     const fr_vtable *f = find_frvt(curve);
     if (!f) return AMDMSM_ERR_UNSUPPORTED;
     if (!out) return AMDMSM_ERR_BAD_ARG;
     frm_layout L;
-    const int rc = frm_prepare(nullptr, f, n_rows, n_cols, offsets, cols, coeffs, coeffs_plain, L);
+    frm_transposed tr;
+    const int rc = frm_prepare(nullptr, f, n_rows, n_cols, offsets, cols, coeffs, coeffs_plain, L, transposed ? &tr : nullptr);
     if (rc) return rc;
     const bool naive = frm_naive_env();
     out[0] = L.nnz;
@@ -4338,7 +4350,7 @@ int amdmsm_plan_fr_matrix(int curve, size_t n_rows, size_t n_cols, const uint64_
     out[8] = L.t_wave;
     out[9] = L.t_split;
     out[10] = L.longest;
-    out[11] = frm_device_bytes(f, L, n_rows, naive);
+    out[11] = frm_device_bytes(f, L, transposed ? n_cols : n_rows, naive);
     out[12] = naive ? 1 : 1 + (L.comb.empty() ? 0 : 1);
     out[13] = f->matrix_chunk;
     out[14] = L.desc.size();
@@ -4346,21 +4358,27 @@ int amdmsm_plan_fr_matrix(int curve, size_t n_rows, size_t n_cols, const uint64_
     return AMDMSM_OK;
 }
 
-int amdmsm_fr_matrix_load(amdmsm_ctx *ctx, int curve, size_t n_rows, size_t n_cols, const uint64_t *offsets, const uint32_t *cols,
-                          const void *coeffs, int coeffs_plain, uint64_t *mat) {
+int frm_load(amdmsm_ctx *ctx, int curve, size_t n_rows, size_t n_cols, const uint64_t *offsets, const uint32_t *cols,
+             const void *coeffs, int coeffs_plain, bool transposed, uint64_t *mat) {
     if (mat) *mat = 0;   // no handle is ever 0
     const fr_vtable *f = find_frvt(curve);
     if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
     if (!mat) return fail(ctx, AMDMSM_ERR_BAD_ARG, "mat: null pointer");
     frm_layout L;
-    int rc = frm_prepare(ctx, f, n_rows, n_cols, offsets, cols, coeffs, coeffs_plain, L);
+    frm_transposed tr;
+    int rc = frm_prepare(ctx, f, n_rows, n_cols, offsets, cols, coeffs, coeffs_plain, L, transposed ? &tr : nullptr);
     if (rc) return rc;
     FR_ENTER(ctx);
+    if (transposed) {   // from here on the matrix is the transpose
+        std::swap(n_rows, n_cols);
+        offsets = tr.offsets.data();
+        cols = tr.rows.data();
+    }
     const size_t rec = (size_t)f->words * 4, N = (size_t)f->words;
     const fr_rec r2 = fr_from_words(f, f->r2);
-    const auto mont = [&](uint64_t k, uint32_t *dst) {   // the caller's coefficient k as a Montgomery residue
+    const auto mont = [&](uint64_t k, uint32_t *dst) {   // coefficient k of the matrix as a Montgomery residue
         fr_rec c;
-        memcpy(c.v, (const char *)coeffs + k * rec, rec);
+        memcpy(c.v, (const char *)coeffs + (transposed ? tr.src[k] : k) * rec, rec);
         if (coeffs_plain) c = fr_mul(f, c, r2);
         memcpy(dst, c.v, rec);
     };
@@ -4398,6 +4416,28 @@ int amdmsm_fr_matrix_load(amdmsm_ctx *ctx, int curve, size_t n_rows, size_t n_co
     ctx->fr_mats.push_back(m);
     *mat = m->id;
     return AMDMSM_OK;
+}
+
+}   // namespace
+
+extern "C" {
+
+int amdmsm_plan_fr_matrix(int curve, size_t n_rows, size_t n_cols, const uint64_t *offsets, const uint32_t *cols, const void *coeffs,
+                          int coeffs_plain, size_t out[AMDMSM_FR_MATRIX_PLAN_WORDS]) {
+    return frm_plan(curve, n_rows, n_cols, offsets, cols, coeffs, coeffs_plain, false, out);
+}
+int amdmsm_plan_fr_matrix_transposed(int curve, size_t n_rows, size_t n_cols, const uint64_t *offsets, const uint32_t *cols,
+                                     const void *coeffs, int coeffs_plain, size_t out[AMDMSM_FR_MATRIX_PLAN_WORDS]) {
+    return frm_plan(curve, n_rows, n_cols, offsets, cols, coeffs, coeffs_plain, true, out);
+}
+
+int amdmsm_fr_matrix_load(amdmsm_ctx *ctx, int curve, size_t n_rows, size_t n_cols, const uint64_t *offsets, const uint32_t *cols,
+                          const void *coeffs, int coeffs_plain, uint64_t *mat) {
+    return frm_load(ctx, curve, n_rows, n_cols, offsets, cols, coeffs, coeffs_plain, false, mat);
+}
+int amdmsm_fr_matrix_load_transposed(amdmsm_ctx *ctx, int curve, size_t n_rows, size_t n_cols, const uint64_t *offsets,
+                                     const uint32_t *cols, const void *coeffs, int coeffs_plain, uint64_t *mat) {
+    return frm_load(ctx, curve, n_rows, n_cols, offsets, cols, coeffs, coeffs_plain, true, mat);
 }
 
 int amdmsm_fr_matrix_free(amdmsm_ctx *ctx, uint64_t mat) {
@@ -5010,6 +5050,106 @@ int frdiv_run(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, const frdiv_c
     return AMDMSM_OK;
 }
 
+// ---- the Lagrange vector of a domain at a point: out[j] = L_j(t) ---------------------------------------------
+// With Z = Z(t) != 0 the denominators are
+//     basic:           1 / L_j = (t / x_j - 1) m / Z
+//     step, j < B:     1 / L_j = (t / x_j - 1) B (rho^(j mod K) - w^S) / Z,   rho = w^(2 S) of order K
+//     step, j >= B:    1 / L_j = (t / x_j - 1) (-2 S w^S) / Z
+// one sweep writes them and the batch inversion of section 20 inverts them in place.  The K factors below B are built as
+// frdiv_run builds its own: powers of rho, then a subtraction.  The inversion takes and leaves Montgomery residues; for
+// plain results the factors carry one more R, so that what it leaves is the plain integer.  Z = 0: t is a point of the
+// domain and the sweep writes the unit vector.
+struct frlag_call {
+    frdom d;
+    size_t rec = 0, K = 0, off_scan = 0, ws_bytes = 0;
+    bool plain = false, unit = false;
+    fr_rec w, t, rho, first, sub, tail;   // kden[k] = first rho^k - sub
+    frs_call inv;
+};
+int frlag_check(amdmsm_ctx *ctx, const fr_vtable *f, size_t m, const void *t, const amdmsm_opts *opts, const void *out, bool device,
+                frlag_call &c) {
+    std::string why;
+    int rc = frdom_exact(f, m, c.d, why);
+    if (rc) return fail(ctx, rc, why);
+    c.rec = (size_t)f->words * 4;
+    if (!t) return fail(ctx, AMDMSM_ERR_BAD_ARG, "t: null pointer");
+    if (!out) return fail(ctx, AMDMSM_ERR_BAD_ARG, "output: null pointer");
+    if (device) {
+        rc = fr_check_aligned(ctx, f, "d_out", {out});
+        if (rc) return rc;
+    }
+    if (!fr_below_modulus(f, (const uint32_t *)t)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "t: not below r");
+    c.plain = opts && opts->scalars_plain;
+    const frdom &d = c.d;
+    const fr_rec one = fr_one(f), r2 = fr_from_words(f, f->r2);
+    c.t = fr_read(f, t, c.plain);
+    c.w = fr_root_host(f, d.log_w);
+    const fr_rec ws = fr_pow_host(f, c.w, d.S);
+    fr_rec z = fr_sub_host(f, fr_pow_host(f, c.t, d.B), one);
+    if (d.step) z = fr_mul(f, z, fr_sub_host(f, fr_pow_host(f, c.t, d.S), ws));
+    c.unit = fr_is_zero(f, z);
+    if (c.unit) {
+        c.tail = c.plain ? fr_small(1) : one;
+        return AMDMSM_OK;
+    }
+    const fr_rec zi = fr_inv_host(f, z);
+    if (!d.step) {
+        c.tail = fr_mul(f, fr_mont_small(f, (uint32_t)d.m), zi);
+    } else {
+        c.K = d.B >> d.log_s;
+        c.rho = fr_mul(f, ws, ws);
+        c.first = fr_mul(f, fr_mont_small(f, (uint32_t)d.B), zi);
+        c.sub = fr_mul(f, c.first, ws);
+        c.tail = fr_neg_host(f, fr_mul(f, fr_mul(f, fr_mont_small(f, (uint32_t)(2 * d.S)), ws), zi));
+    }
+    if (c.plain) {
+        c.first = fr_mul(f, c.first, r2);
+        c.sub = fr_mul(f, c.sub, r2);
+        c.tail = fr_mul(f, c.tail, r2);
+    }
+    c.inv.rec = c.rec;
+    c.inv.invert = true;
+    c.inv.naive = frs_naive_env();
+    c.inv.has_a = 1;
+    frs_make_layout(m, 0, c.rec, true, c.inv.naive, c.inv.L);
+    c.off_scan = align_up(c.K * c.rec, 256);
+    c.ws_bytes = c.off_scan + c.inv.L.ws_bytes;
+    return AMDMSM_OK;
+}
+// phase 0: the powers of w, from the context's cache or built now, and the K factors; phase 1: the sweep and the inversion
+int frlag_run(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, const frlag_call &c, uint32_t *d_out, char *ws) {
+    const frdom &d = c.d;
+    fr_tw_entry *tw = nullptr;
+    frfft_params pw;
+    pw.omega = c.w;
+    const int rc = frfft_twiddles(ctx, f, st, (size_t)1 << d.log_w, pw, tw);
+    if (rc) return rc;
+    uint32_t *kden = (uint32_t *)ws;
+    if (d.step && !c.unit) {
+        f->powers(st, fr_pow_table(f, c.rho, 0).data(), c.first.v, 0, c.K, kden);
+        f->domain_den(st, c.K, kden, c.sub.v);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    call_mark(ctx, st, 1);
+    frd_lagrange a = {};
+    a.tw = (const uint32_t *)tw->buf.p;
+    a.kden = kden;
+    a.out = d_out;
+    a.m = d.m;
+    a.log_b = d.log_b;
+    a.log_s = d.log_s;
+    a.log_o = d.log_w;
+    a.step = d.step ? 1 : 0;
+    a.unit = c.unit ? 1 : 0;
+    memcpy(a.t, c.t.v, sizeof(a.t));
+    memcpy(a.tail, c.tail.v, sizeof(a.tail));
+    f->domain_lagrange(st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(tw->ev, st));
+    if (c.unit) return AMDMSM_OK;
+    return frs_run(ctx, f, st, c.inv, d.m, d_out, nullptr, d_out, nullptr, ws + c.off_scan);
+}
+
 }   // namespace
 
 extern "C" {
@@ -5168,6 +5308,68 @@ int amdmsm_fr_domain_divide_by_z(amdmsm_ctx *ctx, int curve, size_t m, const voi
     const size_t vec = align_up(m * c.rec, 256);
     return fr_call(ctx, st, vec, std::max<size_t>(c.ws_bytes, 256), {{values, 0, m * c.rec}}, {{out, 0, m * c.rec}},
                    [&](char *v, char *ws) { return frdiv_run(ctx, f, st, c, (const uint32_t *)v, (uint32_t *)v, ws); });
+}
+
+int amdmsm_fr_domain_lagrange_device(amdmsm_ctx *ctx, int curve, size_t m, const void *t, const amdmsm_opts *opts, void *d_out) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
+    CHECK_OPTS(ctx, opts);
+    frlag_call c;
+    const int rc = frlag_check(ctx, f, m, t, opts, d_out, true, c);
+    if (rc) return rc;
+    FR_ENTER(ctx);
+    hipStream_t st = stream_of(ctx, opts);
+    return fr_call(ctx, st, 0, std::max<size_t>(c.ws_bytes, 256), {}, {},
+                   [&](char *, char *ws) { return frlag_run(ctx, f, st, c, (uint32_t *)d_out, ws); });
+}
+
+int amdmsm_fr_domain_lagrange(amdmsm_ctx *ctx, int curve, size_t m, const void *t, const amdmsm_opts *opts, void *out) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
+    CHECK_OPTS(ctx, opts);
+    frlag_call c;
+    const int rc = frlag_check(ctx, f, m, t, opts, out, false, c);
+    if (rc) return rc;
+    FR_ENTER(ctx);
+    hipStream_t st = ctx->stream;
+    // one staged vector, written by the sweep and inverted in place; nothing goes up
+    const size_t vec = align_up(m * c.rec, 256);
+    return fr_call(ctx, st, vec, std::max<size_t>(c.ws_bytes, 256), {}, {{out, 0, m * c.rec}},
+                   [&](char *v, char *ws) { return frlag_run(ctx, f, st, c, (uint32_t *)v, ws); });
+}
+
+int amdmsm_fr_lincomb_device(amdmsm_ctx *ctx, int curve, size_t n, int k, const void *const *d_v, const void *scalars,
+                             const amdmsm_opts *opts, void *d_out) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
+    CHECK_OPTS(ctx, opts);
+    if (k < 1 || k > FR_LINCOMB_MAX) return fail(ctx, AMDMSM_ERR_BAD_ARG, "k = " + std::to_string(k) + ": 1 .. " + std::to_string(FR_LINCOMB_MAX));
+    if (n > FRS_MAX_N) return fail(ctx, AMDMSM_ERR_TOO_LARGE, "n = " + std::to_string(n) + ": at most 2^28 records");
+    if (!d_v) return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_v: null pointer");
+    if (!scalars) return fail(ctx, AMDMSM_ERR_BAD_ARG, "scalars: null pointer");
+    const size_t rec = (size_t)f->words * 4, bytes = n * rec;
+    if (n && !d_out) return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_out: null pointer");
+    for (int j = 0; j < k; ++j) {
+        const std::string name = "d_v[" + std::to_string(j) + "]";
+        if (n && !d_v[j]) return fail(ctx, AMDMSM_ERR_BAD_ARG, name + ": null pointer");
+        int rc = n ? fr_check_aligned(ctx, f, "d_v / d_out", {d_v[j], d_out}) : AMDMSM_OK;
+        if (!rc) rc = fr_check_apart(ctx, name.c_str(), d_v[j], bytes, "d_out", d_out, bytes);
+        if (rc) return rc;
+        if (!fr_below_modulus(f, (const uint32_t *)((const char *)scalars + j * rec)))
+            return fail(ctx, AMDMSM_ERR_BAD_ARG, "scalars[" + std::to_string(j) + "]: not below r");
+    }
+    FR_ENTER(ctx);
+    if (!n) return AMDMSM_OK;
+    const bool plain = opts && opts->scalars_plain;
+    uint32_t s[FR_LINCOMB_MAX * FR_MAX_WORDS] = {};
+    for (int j = 0; j < k; ++j) memcpy(s + (size_t)j * f->words, fr_read(f, (const char *)scalars + j * rec, plain).v, rec);
+    hipStream_t st = stream_of(ctx, opts);
+    return fr_call(ctx, st, 0, 256, {}, {}, [&](char *, char *) -> int {
+        call_mark(ctx, st, 1);
+        f->lincomb(st, n, k, (const uint32_t *const *)d_v, s, (uint32_t *)d_out);
+        HIP_TRY(ctx, hipGetLastError());
+        return AMDMSM_OK;
+    });
 }
 
 }  // extern "C"

@@ -174,6 +174,45 @@ __global__ void __launch_bounds__(TPB) k_frd_divide(size_t m, size_t B, size_t k
     }
 }
 
+// The Lagrange vector at t, DESIGN section 24.  x_j = w^e with w the root of order O = 2^log_o and e = j (basic), 2 j
+// (step, j < B) or 1 + 2 K (j - B) (step, the tail: sigma = w^(2 K)); the table holds w^i for i < O / 2 and w^(O / 2) is
+// -1, so w^i is tw[i] or -tw[i - O / 2].  Record j is the denominator
+//     1 / L_j(t) = (t / x_j - 1) f_j,   f_j = kden[j mod K] (step, j < B) or tail,
+// which the batch inversion turns into L_j(t); with Z(t) = 0 (UNIT) it is the vector itself, 1 where x_j = t.
+// Every index comes from log_b, log_s, log_o and the launch geometry, none from a record.
+AMDMSM_DEV void frd_root_power(F& x, const uint32_t* tw, size_t i, size_t half) {
+    const bool neg = i >= half;
+    rec_load(x, tw, neg ? i - half : i);
+    fp_cneg(x, x, neg);
+}
+template <bool UNIT>
+__global__ void __launch_bounds__(TPB) k_frd_lagrange(const frd_lagrange a) {
+    const size_t O = (size_t)1 << a.log_o, half = O >> 1;
+    const size_t B = a.step ? (size_t)1 << a.log_b : 0, kmask = a.step ? (B >> a.log_s) - 1 : 0;
+    F t, tail, one;
+    rec_copy(t, a.t);
+    rec_copy(tail, a.tail);
+    fp_set_one(one);
+    for (size_t j = (size_t)blockIdx.x * TPB + threadIdx.x; j < a.m; j += (size_t)gridDim.x * TPB) {
+        const size_t e = !a.step ? j : (j < B ? 2 * j : 1 + ((j - B) << (a.log_o - a.log_s)));
+        F x;
+        if constexpr (UNIT) {
+            frd_root_power(x, a.tw, e, half);
+            const bool hit = fp_eq(x, t);
+            fp_set_zero(x);
+            rec_store(a.out, j, hit ? tail : x);
+        } else {
+            frd_root_power(x, a.tw, (O - e) & (O - 1), half);   // 1 / x_j
+            F f = tail;
+            if (j < B) rec_load(f, a.kden, j & kmask);
+            fp_mul(x, x, t);
+            fp_sub(x, x, one);
+            fp_mul(x, x, f);
+            rec_store(a.out, j, x);
+        }
+    }
+}
+
 // ---- launchers ------------------------------------------------------------------------------------------------------
 void l_domain_sweep(hipStream_t st, const frd_sweep& a) {
     const uint32_t per = (uint32_t)(TPB >> a.log_w) * a.iters;
@@ -198,4 +237,10 @@ void l_domain_divide(hipStream_t st, size_t m, size_t B, size_t K, const uint32_
     const size_t blocks = (m + TPB - 1) / TPB;
     hipLaunchKernelGGL(k_frd_divide, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(TPB), 0, st, m, B, K ? K - 1 : 0, d_in,
                        d_inv, tl, d_out);
+}
+void l_domain_lagrange(hipStream_t st, const frd_lagrange& a) {
+    const size_t blocks = (a.m + TPB - 1) / TPB;
+    const dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096));
+    if (a.unit) hipLaunchKernelGGL(k_frd_lagrange<true>, grid, dim3(TPB), 0, st, a);
+    else hipLaunchKernelGGL(k_frd_lagrange<false>, grid, dim3(TPB), 0, st, a);
 }

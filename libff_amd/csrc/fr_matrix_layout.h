@@ -1,5 +1,5 @@
 // CSR -> resident form of a sparse matrix over Fr (amdmsm_fr_matrix_load): validation, classification, binning, the
-// row permutation and the offsets of the side arrays.  Pure index arithmetic on host arrays -- no HIP, no field
+// row permutation and the offsets of the side arrays; and the CSR of the transpose (amdmsm_fr_matrix_load_transposed).  Pure index arithmetic on host arrays -- no HIP, no field
 // arithmetic: the caller says what class a coefficient is -- so that the stand-alone checker tools/fr_matrix_layout_check.cpp
 // builds the same layouts under the host compiler's sanitizers.  DESIGN section 19 describes the form.
 //
@@ -92,6 +92,29 @@ inline int frm_validate(size_t n_rows, size_t n_cols, const uint64_t *offsets, c
             return err = "entry " + std::to_string(k) + ": column " + std::to_string(cols[k]) + " >= n_cols = " +
                          std::to_string(n_cols), 1;
     return 0;
+}
+
+// The CSR of the transpose of a validated matrix M (amdmsm_fr_matrix_load_transposed), by a stable counting sort on the
+// column: n_cols rows whose entries go in ascending row of M, those of one row of M in the order given.  src[k]: the
+// entry of M behind entry k of the transpose -- the coefficients stay where the caller has them.
+struct frm_transposed {
+    std::vector<uint64_t> offsets;
+    std::vector<uint32_t> rows, src;
+};
+inline void frm_transpose(size_t n_rows, size_t n_cols, const uint64_t *offsets, const uint32_t *cols, frm_transposed &t) {
+    const uint64_t nnz = n_rows ? offsets[n_rows] : 0;
+    t.offsets.assign(n_cols + 1, 0);
+    for (uint64_t k = 0; k < nnz; ++k) ++t.offsets[(size_t)cols[k] + 1];
+    for (size_t c = 0; c < n_cols; ++c) t.offsets[c + 1] += t.offsets[c];
+    t.rows.resize(nnz);
+    t.src.resize(nnz);
+    std::vector<uint64_t> at(t.offsets.begin(), t.offsets.end() - 1);
+    for (size_t i = 0; i < n_rows; ++i)
+        for (uint64_t k = offsets[i]; k < offsets[i + 1]; ++k) {
+            const uint64_t p = at[cols[k]]++;
+            t.rows[p] = (uint32_t)i;
+            t.src[p] = (uint32_t)k;   // nnz <= 2^31
+        }
 }
 
 // The layout of a validated matrix.  cls_of(k): the class of the caller's entry k -- FRM_GEN, FRM_PLUS, FRM_MINUS,

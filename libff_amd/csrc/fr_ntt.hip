@@ -191,6 +191,32 @@ __global__ void __launch_bounds__(TPB) k_fr_muladd(size_t n, const uint32_t* a, 
     }
 }
 
+// ---- out[i] = sum over j < k of s_j v_j[i] -------------------------------------------------------------------------------
+// The scalars are Montgomery residues whatever the vectors are: the Montgomery product of s R and a plain v is the
+// plain s v, of s R and v R it is s v R.  A lane reads its record of every vector before it writes, so out may be any
+// one of them.
+struct fr_lincomb_args {
+    const uint32_t* v[FR_LINCOMB_MAX];
+    uint32_t s[FR_LINCOMB_MAX][N];
+};
+__global__ void __launch_bounds__(TPB) k_fr_lincomb(size_t n, int k, const fr_lincomb_args a, uint32_t* out) {
+    const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    F acc;
+    fp_set_zero(acc);
+#pragma unroll
+    for (int j = 0; j < FR_LINCOMB_MAX; ++j) {
+        if (j < k) {
+            F x, s;
+            rec_copy(s, a.s[j]);
+            rec_load(x, a.v[j], i);
+            fp_mul(x, x, s);
+            fp_add(acc, acc, x);
+        }
+    }
+    rec_store(out, i, acc);
+}
+
 // ---- sparse matrix times vector ---------------------------------------------------------------------------------------
 #include "fr_matrix.inc"
 
@@ -228,6 +254,16 @@ void l_muladd(hipStream_t st, size_t n, const uint32_t* d_a, const uint32_t* d_b
                        k ? 1 : 0, plain, d_out);
 }
 
+void l_lincomb(hipStream_t st, size_t n, int k, const uint32_t* const* d_v, const uint32_t* scalars, uint32_t* d_out) {
+    if (!n) return;
+    fr_lincomb_args a = {};
+    for (int j = 0; j < k; ++j) {
+        a.v[j] = d_v[j];
+        for (int w = 0; w < N; ++w) a.s[j][w] = scalars[(size_t)j * N + w];
+    }
+    hipLaunchKernelGGL(k_fr_lincomb, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, st, n, k, a, d_out);
+}
+
 const fr_vtable g_frvt = {
     .curve = AMDMSM_FR_CURVE,
     .words = N,
@@ -241,6 +277,7 @@ const fr_vtable g_frvt = {
     .powers = l_powers,
     .pass = l_pass,
     .muladd = l_muladd,
+    .lincomb = l_lincomb,
     .matrix_chunk = FRM_T,
     .matrix_apply = l_matrix_apply,
     .matrix_naive = l_matrix_naive,
@@ -250,6 +287,7 @@ const fr_vtable g_frvt = {
     .domain_combine = l_domain_combine,
     .domain_den = l_domain_den,
     .domain_divide = l_domain_divide,
+    .domain_lagrange = l_domain_lagrange,
 };
 
 }  // namespace

@@ -15,6 +15,7 @@ constexpr int FR_MAX_WORDS = 12;
 constexpr int FR_LDS_LOG2 = 10;        // records of one LDS tile (log2), every field: 32 / 40 / 48 KiB
 constexpr int FR_TILE_MIN = 4, FR_TILE_MAX = 8, FR_TILE_DEFAULT = 8;   // butterfly stages per global pass
 constexpr int FR_POW_TABLE = 17;       // base^(2^b), b = 0 .. 16: what k_fr_powers is given
+constexpr int FR_LINCOMB_MAX = 4;      // vectors of one linear combination (k_fr_lincomb)
 
 // one global pass of the transform (k_fr_fft_pass): log_r in-LDS stages on tiles of 2^log_c neighbouring columns
 struct fr_pass {
@@ -90,6 +91,17 @@ struct frd_combine {
     int log_b, log_s, plain;
     uint32_t half[FR_MAX_WORDS];   // 1 / 2, Montgomery
 };
+// the Lagrange vector of a domain at a point t (k_frd_lagrange): m denominators 1 / L_j(t) for the batch inversion, or
+// with `unit` (Z(t) = 0) the unit vector itself.  A basic domain has step = 0, log_o = log2 m and no K-table
+struct frd_lagrange {
+    const uint32_t* tw;          // the 2^(log_o - 1) powers of the root of order 2^log_o, Montgomery
+    const uint32_t* kden;        // step: the K factors of the records below B
+    uint32_t* out;               // m records
+    size_t m;
+    int log_b, log_s, log_o, step, unit;
+    uint32_t t[FR_MAX_WORDS];    // Montgomery
+    uint32_t tail[FR_MAX_WORDS]; // the factor from B on (basic: of every record); unit: what a 1 is in the caller's form
+};
 
 // Members by stage: constants of the field, the transform, the sparse matrix, scans, step domains.  fr_ntt.hip fills
 // the table by member name.
@@ -104,6 +116,9 @@ struct fr_vtable {
     // d_out[i] = (a_i * b_i - c_i) * k; d_c, k: null for 0 and 1.  k: a host record
     void (*muladd)(hipStream_t, size_t n, const uint32_t* d_a, const uint32_t* d_b, const uint32_t* d_c, const uint32_t* k,
                    int plain, uint32_t* d_out);
+    // d_out[i] = sum over j < k of s_j * v_j[i], 1 <= k <= FR_LINCOMB_MAX.  d_v: k device vectors in host memory, any of
+    // them d_out; scalars: k packed host records.  Records keep the form they come in
+    void (*lincomb)(hipStream_t, size_t n, int k, const uint32_t* const* d_v, const uint32_t* scalars, uint32_t* d_out);
     // sparse matrix times vector: general products summed unreduced, matrix_chunk of them to one Montgomery reduction
     uint32_t matrix_chunk;
     void (*matrix_apply)(hipStream_t, const frm_args&);
@@ -122,6 +137,8 @@ struct fr_vtable {
     void (*domain_den)(hipStream_t, size_t n, uint32_t* d_den, const uint32_t* c);
     void (*domain_divide)(hipStream_t, size_t m, size_t B, size_t K, const uint32_t* d_in, const uint32_t* d_inv, const uint32_t* tail,
                           uint32_t* d_out);
+    // record j of the domain's Lagrange vector at t, as its denominator or, on a point of the domain, as it is
+    void (*domain_lagrange)(hipStream_t, const frd_lagrange&);
 };
 
 const fr_vtable* frvt_alt_bn128() __attribute__((weak));

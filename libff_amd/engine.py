@@ -75,6 +75,8 @@ EXPORTED_SYMBOLS = [
     "amdmsm_fr_domain", "amdmsm_fr_domain_element", "amdmsm_fr_domain_vanishing", "amdmsm_fr_domain_z_terms",
     "amdmsm_fr_multiplicative_generator", "amdmsm_fr_domain_fft", "amdmsm_fr_domain_fft_device",
     "amdmsm_fr_domain_divide_by_z", "amdmsm_fr_domain_divide_by_z_device",
+    "amdmsm_fr_domain_lagrange", "amdmsm_fr_domain_lagrange_device",
+    "amdmsm_fr_matrix_load_transposed", "amdmsm_plan_fr_matrix_transposed", "amdmsm_fr_lincomb_device",
 ]
 SEG_SHARED_BASES = 1            # include/amdmsm.h AMDMSM_SEG_SHARED_BASES
 SEG_LONG_NEVER = 2 ** 64 - 1    # long_from = SIZE_MAX: no segment takes the single-MSM route
@@ -330,12 +332,22 @@ def plan_fr_matrix(curve, offsets, cols, coeffs, n_cols, plain=False):
     entries per coefficient class, rows per length class with the thresholds between them, the longest row, device
     bytes, launches of one apply and the field's chain length.  Validates exactly what the load validates and raises
     ``AmdMsmError`` with the code."""
+    return _plan_fr_matrix("amdmsm_plan_fr_matrix", curve, offsets, cols, coeffs, n_cols, plain)
+
+
+def plan_fr_matrix_transposed(curve, offsets, cols, coeffs, n_cols, plain=False):
+    """What ``Engine.fr_matrix_load_transposed`` would build from the CSR arrays of M (``amdmsm_plan_fr_matrix_transposed``):
+    ``plan_fr_matrix`` of the transpose, with the validation and the codes of the plain plan."""
+    return _plan_fr_matrix("amdmsm_plan_fr_matrix_transposed", curve, offsets, cols, coeffs, n_cols, plain)
+
+
+def _plan_fr_matrix(entry, curve, offsets, cols, coeffs, n_cols, plain):
     offsets, cols, coeffs, n_rows, ptr = _csr_arrays(curve, offsets, cols, coeffs)
     out = (ctypes.c_size_t * FR_MATRIX_PLAN_WORDS)()
-    rc = load_library().amdmsm_plan_fr_matrix(curve, ctypes.c_size_t(n_rows), ctypes.c_size_t(n_cols), ptr(offsets), ptr(cols),
-                                              ptr(coeffs), int(plain), out)
+    rc = getattr(load_library(), entry)(curve, ctypes.c_size_t(n_rows), ctypes.c_size_t(n_cols), ptr(offsets), ptr(cols),
+                                        ptr(coeffs), int(plain), out)
     if rc:
-        raise AmdMsmError(f"amdmsm_plan_fr_matrix: {rc}")
+        raise AmdMsmError(f"{entry}: {rc}")
     return {"nnz": out[0], "general": out[1], "plus_one": out[2], "minus_one": out[3], "zero": out[4],
             "rows_lane": out[5], "rows_wave": out[6], "rows_split": out[7], "wave_row": out[8], "split_row": out[9],
             "longest_row": out[10], "device_bytes": out[11], "launches": out[12], "chunk": out[13], "wave_jobs": out[14],
@@ -1151,6 +1163,17 @@ class Engine:
         self._check(rc, "amdmsm_fr_matrix_load")
         return FrMatrix(self, h.value, curve, n_rows, int(n_cols))
 
+    def fr_matrix_load_transposed(self, curve, offsets, cols, coeffs, n_cols, plain=False):
+        """Keep the transpose of a CSR matrix M on the device (``amdmsm_fr_matrix_load_transposed``): the arguments are
+        those of ``fr_matrix_load`` for M, the ``FrMatrix`` has ``n_cols`` rows and M's rows as columns --
+        ``fr_matrix_apply(mat, u)[c]`` is the sum of ``coeff * u[i]`` over the entries (i, c) of M."""
+        offsets, cols, coeffs, n_rows, ptr = _csr_arrays(curve, offsets, cols, coeffs)
+        h = ctypes.c_uint64(0)
+        rc = self.lib.amdmsm_fr_matrix_load_transposed(self.h, curve, ctypes.c_size_t(n_rows), ctypes.c_size_t(n_cols),
+                                                       ptr(offsets), ptr(cols), ptr(coeffs), int(plain), ctypes.byref(h))
+        self._check(rc, "amdmsm_fr_matrix_load_transposed")
+        return FrMatrix(self, h.value, curve, int(n_cols), n_rows)
+
     def fr_matrix_apply(self, mat, x, n_out=None, plain=False):
         """``out[i] = sum_k coeffs[k] x[cols[k]]`` over row i (``amdmsm_fr_matrix_apply``): ``x`` (n_x >= n_cols, fr_limbs)
         uint64 records in the form ``plain`` says, the result -- ``n_out`` records, the rows and zeros behind them --
@@ -1277,6 +1300,42 @@ class Engine:
         self._check(self.lib.amdmsm_fr_domain_divide_by_z_device(self.h, curve, ctypes.c_size_t(m), _opt_dev(d_values), _opt_ptr(g),
                                                                  ctypes.byref(o), _opt_dev(d_out)),
                     "amdmsm_fr_domain_divide_by_z_device")
+
+    def fr_domain_lagrange(self, curve, m, t, plain=False):
+        """The Lagrange vector of the domain of ``m`` points at ``t`` (an int; ``amdmsm_fr_domain_lagrange``):
+        ``out[j] = L_j(t)``, (m, fr_limbs) uint64 records in the form ``plain`` says -- libfqfft's
+        ``evaluate_all_lagrange_polynomials(t)``; the unit vector where ``t`` is a point of the domain."""
+        limbs = _fr_limbs(curve)
+        out = np.zeros((m, limbs), dtype=np.uint64)
+        tt = _fr_host_record(t, limbs, fr_modulus(curve, G1), plain)
+        o = self._opts(scalars_plain=plain)
+        rc = self.lib.amdmsm_fr_domain_lagrange(self.h, curve, ctypes.c_size_t(m), _opt_ptr(tt), ctypes.byref(o), _np_ptr(out))
+        self._check(rc, "amdmsm_fr_domain_lagrange")
+        return out
+
+    def fr_domain_lagrange_device(self, curve, m, t, d_out, plain=False, stream=None):
+        """``fr_domain_lagrange`` into ``m`` device-resident records (``amdmsm_fr_domain_lagrange_device``); enqueued on
+        ``stream``, not synchronised."""
+        tt = _fr_host_record(t, _fr_limbs(curve), fr_modulus(curve, G1), plain)
+        o = self._opts(scalars_plain=plain, stream=stream)
+        self._check(self.lib.amdmsm_fr_domain_lagrange_device(self.h, curve, ctypes.c_size_t(m), _opt_ptr(tt), ctypes.byref(o),
+                                                              _opt_dev(d_out)), "amdmsm_fr_domain_lagrange_device")
+
+    def fr_lincomb_device(self, curve, n, d_vectors, scalars, d_out, plain=False, stream=None):
+        """``d_out[i] = sum_j scalars[j] * d_vectors[j][i]`` over ``n`` device-resident records
+        (``amdmsm_fr_lincomb_device``): 1 to 4 device pointers, as many ``scalars`` (ints, or a (k, fr_limbs) uint64 array
+        taken as it stands); ``d_out`` may be one of the vectors; enqueued on ``stream``, not synchronised."""
+        limbs, r = _fr_limbs(curve), fr_modulus(curve, G1)
+        k = len(d_vectors)
+        if isinstance(scalars, np.ndarray):
+            s = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, limbs)
+        else:
+            s = np.array([_fr_record(x, limbs, r, plain) for x in scalars], dtype=np.uint64).reshape(-1, limbs)
+        assert s.shape[0] == k, "one scalar per vector"
+        ptrs = (ctypes.c_void_p * max(k, 1))(*[_opt_dev(x) for x in d_vectors])
+        o = self._opts(scalars_plain=plain, stream=stream)
+        self._check(self.lib.amdmsm_fr_lincomb_device(self.h, curve, ctypes.c_size_t(n), k, ptrs, _np_ptr(s) if s.size else None,
+                                                      ctypes.byref(o), _opt_dev(d_out)), "amdmsm_fr_lincomb_device")
 
     def batch_exp_timings(self):
         """device times (ms) of the last batch_exp: inputs H2D, window table (0 = reused), exponentiations, results D2H"""

@@ -1,7 +1,7 @@
 // Stand-alone check of libff_amd/csrc/fr_matrix_layout.h, the host code that turns a CSR matrix into the resident form
 // of amdmsm_fr_matrix_load: builds layouts for a handful of small matrices, walks them the way k_frm_apply does -- wave
 // job by wave job, step by step, lane by lane, every array a heap block of its exact size -- over a small prime, and
-// compares with the plain CSR sum.  Meant for the host compiler's sanitizers (tests/test_fr_matrix_cpu.py):
+// compares with the plain CSR sum; the transposition in front of amdmsm_fr_matrix_load_transposed likewise.  Meant for the host compiler's sanitizers (tests/test_fr_matrix_cpu.py):
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -I libff_amd/csrc tools/fr_matrix_layout_check.cpp -o check && ./check
 // No HIP, no GPU.  Exit status 0 and "ok" when every matrix agrees.
 #include <cstdint>
@@ -44,6 +44,13 @@ uint64_t pick_coeff() {
     }
 }
 
+template <class T>
+std::unique_ptr<T[]> exact_copy(const std::vector<T> &v) {   // a heap block of exactly v.size() elements
+    std::unique_ptr<T[]> p(new T[v.size()]);
+    if (!v.empty()) memcpy(p.get(), v.data(), v.size() * sizeof(T));
+    return p;
+}
+
 csr make(size_t n_cols, const std::vector<size_t> &lens, bool nonzero = false) {
     csr m;
     m.n_rows = lens.size();
@@ -59,6 +66,31 @@ csr make(size_t n_cols, const std::vector<size_t> &lens, bool nonzero = false) {
         m.offsets.push_back(m.cols.size());
     }
     return m;
+}
+
+// the transpose through frm_transpose, its arrays read from heap blocks of exact size; 1 where it is not the transpose
+int transposed(const char *name, const csr &m, csr &t) {
+    auto offsets = exact_copy(m.offsets), coeffs = exact_copy(m.coeffs);
+    auto cols = exact_copy(m.cols);
+    frm_transposed tr;
+    frm_transpose(m.n_rows, m.n_cols, m.n_rows ? offsets.get() : nullptr, cols.get(), tr);
+    t = csr();
+    t.n_rows = m.n_cols;
+    t.n_cols = m.n_rows;
+    t.offsets = tr.offsets;
+    t.cols = tr.rows;
+    for (uint32_t k : tr.src) t.coeffs.push_back(coeffs[k]);
+    // every entry of M once, under its column, rows ascending and the entries of one row in the order given
+    int wrong = t.offsets.size() != m.n_cols + 1 || t.cols.size() != m.cols.size() || tr.src.size() != m.cols.size();
+    std::vector<char> seen(m.cols.size(), 0);
+    for (size_t c = 0; !wrong && c < m.n_cols; ++c)
+        for (uint64_t k = t.offsets[c]; k < t.offsets[c + 1]; ++k) {
+            const uint32_t src = tr.src[k], row = tr.rows[k];
+            wrong += src >= m.cols.size() || seen[src]++ || m.cols[src] != c || src < m.offsets[row] || src >= m.offsets[row + 1];
+            if (k > t.offsets[c]) wrong += tr.src[k - 1] >= src;
+        }
+    if (wrong) printf("%s: not the transpose\n", name);
+    return wrong ? 1 : 0;
 }
 
 template <class T>
@@ -184,6 +216,18 @@ int main() {
         bad += check("mixed, t_wave 1", make(97, lens), 1, 64, 300);
     }
     bad += check("one long row", make(11, {70000}), 0, 0, 1);
+    {   // amdmsm_fr_matrix_load_transposed: the transpose, and its layout walked like any other
+        std::vector<size_t> lens;
+        for (size_t i = 0; i < 3000; ++i) lens.push_back(1 + rnd() % 4);
+        csr wide = make(40, lens), t;
+        for (size_t i = 0; i < wide.n_rows; ++i) wide.cols[wide.offsets[i]] = 0;   // one column in every row
+        bad += transposed("transposed, a full column", wide, t) || check("transposed, a full column", t, 4, 256, 64);
+        bad += transposed("transposed, rows 0..3", make(7, {0, 1, 2, 3, 3, 2, 1, 0, 2}), t) || check("transposed, rows 0..3", t, 0, 0, 7);
+        bad += transposed("transposed, no rows", make(5, {}), t) || check("transposed, no rows", t, 0, 0, 5);
+        csr none = make(1, {0, 0, 0});
+        none.n_cols = 0;
+        bad += transposed("transposed, no columns", none, t) || check("transposed, no columns", t, 0, 0, 0);
+    }
     {   // the refusals of the index rules
         std::string err;
         const uint64_t off_bad0[] = {1, 2}, off_dec[] = {0, 2, 1}, off_ok[] = {0, 1};
