@@ -774,6 +774,32 @@ int amdmsm_batch_exp(amdmsm_ctx *ctx, int curve, int group, size_t scalar_size, 
  * window and g -- was still resident), [2] the exponentiations (batch_exp's loop, :874-912), [3] results back */
 int amdmsm_get_batch_exp_timings(amdmsm_ctx *ctx, float ms[4]);
 
+/* amdmsm_batch_exp on device-resident scalars, the results left in HBM: d_out_xyz[i] = d_scalars[i] * g (or (coeff *
+ * d_scalars[i]) * g), what a key generator calls on the Fr vectors amdmsm_fr_lincomb_device left on the device.
+ * scalar_size, window, g_xyz (host) and coeff (host Fr record or NULL) mean what they mean in amdmsm_batch_exp;
+ * opts->scalars_plain speaks of d_scalars and of coeff.  opts->out_form: AMDMSM_OUT_LIBFF (opts == NULL) gives the
+ * records amdmsm_batch_exp writes, word for word; AMDMSM_OUT_AFFINE special form, by the batch normalisation of
+ * amdmsm_scalar_mul_vec_device; AMDMSM_OUT_JACOBIAN is refused.  amdmsm_import_bases_device (form normal, or special
+ * after AMDMSM_OUT_AFFINE) turns the results into compact affine records for the MSM entries and the writers below.
+ * Enqueued on opts->stream (or the context's) and not synchronised; g_xyz and coeff are consumed before the call
+ * returns.  n = 0 succeeds, writes nothing and still builds or keeps the table.
+ * The context's resident window table is shared with amdmsm_batch_exp under the same rule -- same curve, group,
+ * scalar_size, window and g: a table built by either entry serves the other, and a call on another stream than the
+ * one that built or last read it waits for that call on the device (an event, as for a workspace slot).  One table.
+ * Refused before anything is launched or written: AMDMSM_ERR_UNSUPPORTED for (MNT6, G2), before the context is looked
+ * at; AMDMSM_ERR_BAD_ARG for window outside 1..22, scalar_size outside 1..8 * fr_bytes, a null g, a wrong
+ * opts->struct_size, and with n > 0 a null device pointer, d_scalars off 16 bytes (8 for the 10-word fields) or
+ * d_out_xyz off the record alignment, d_out_xyz overlapping d_scalars.
+ * amdmsm_get_batch_exp_timings after this entry waits for the call: [0] upload of g / coeff, [1] table (0 when
+ * reused), [2] exponentiations, [3] normalisation (0 for AMDMSM_OUT_LIBFF).  The normalisation of AMDMSM_OUT_AFFINE
+ * takes a workspace slot, as amdmsm_scalar_mul_vec_device does: on a context with amdmsm_set_timing on it takes a timing
+ * ticket too, so amdmsm_get_timings, amdmsm_last_timing_ticket and amdmsm_last_slot then speak of this call and no
+ * longer of the MSM before it (all of the slot's time stands under its last phase). */
+int amdmsm_batch_exp_device(amdmsm_ctx *ctx, int curve, int group, size_t scalar_size, size_t window,
+                            const void *g_xyz /* host */, const void *d_scalars, size_t n,
+                            const void *coeff /* host Fr record or NULL */, void *d_out_xyz,
+                            const amdmsm_opts *opts);
+
 /* ---- device-resident entry points (all pointers are HBM addresses) ---- */
 int amdmsm_import_bases_device(amdmsm_ctx *ctx, int curve, int group, const void *d_src_xyz,
                                size_t stride_bytes, int base_form, size_t n, void *d_dst_affine,
@@ -785,6 +811,35 @@ int amdmsm_export_affine_device(amdmsm_ctx *ctx, int curve, int group, const voi
  * *status != 0: some compressed X is not on the curve.  Synchronises. */
 int amdmsm_disk_decode_device(amdmsm_ctx *ctx, int curve, int group, const void *d_records, size_t n,
                               int compressed, void *d_dst_affine, unsigned *status);
+/* The inverse: group_write<encoding_binary, form_montgomery, compression_{off,on}> (curve_serialization.tcc:78-133) of
+ * n compact affine points in HBM -> n on-disk records in HBM, 2 * coordinate bytes each (compressed: one coordinate).
+ * Uncompressed: X || Y, every Fq component the Montgomery residue with its bytes reversed, Fq2 as c0 then c1; zero is
+ * written (0, one), what the reference writes after to_affine_coordinates.  Compressed (the a = 0 curves;
+ * AMDMSM_ERR_UNSUPPORTED for MNT4 / MNT6): X with two flags in the top bits of the first byte -- bit 0 the low bit of
+ * Y's (Y.c0's) Montgomery representation, bit 1 zero, which is written as X = 0 with that flag alone.
+ * Enqueued on `stream` (NULL: the context's) and not synchronised; n = 0 succeeds.  AMDMSM_ERR_BAD_ARG for a null or
+ * misaligned vector with n > 0 (the record alignment: 16 bytes, 8 for the 10-word fields) and for d_records overlapping
+ * the source. */
+int amdmsm_disk_encode_device(amdmsm_ctx *ctx, int curve, int group, const void *d_src_affine, size_t n,
+                              int compressed, void *d_records, void *stream);
+/* The same records, written out: n compact affine points in HBM leave through `write` (or into a file) in the format
+ * amdmsm_multi_exp_stream[_compressed][_file] and -- for a table of amdmsm_precompute_bases_device --
+ * amdmsm_multi_exp_stream_with_precompute[_file] read.  chunk_points records at a time (0: 2^20, the readers' default):
+ * chunk k is encoded on the device and copied into one of two pinned staging buffers while chunk k - 1 is handed to
+ * `write`, which sees the records in order, one call per chunk, and returns the bytes it took.  A callback that takes
+ * fewer bytes than offered ends the call with AMDMSM_ERR_BAD_ARG ("record stream ended early"); the context stays
+ * usable.  The points have to be complete on the context's stream; the call returns when everything is written.
+ * amdmsm_write_points_file opens `path` without truncating it (creating it where absent) and writes from offset_bytes
+ * on: the bytes in front and those behind the records are left as they are.  A file that cannot be opened or written
+ * is AMDMSM_ERR_BAD_ARG ("cannot open <path>", "cannot write <path>"), as for the _file readers.
+ * amdmsm_plan_write_points (no context): out[0] = chunks of such a call, and for chunk k below that number out[1] =
+ * its first record, out[2] = its records, out[3] = its staging buffer. */
+typedef size_t (*amdmsm_write_fn)(void *write_ctx, const void *src, size_t bytes); /* returns bytes taken */
+int amdmsm_write_points_stream(amdmsm_ctx *ctx, int curve, int group, const void *d_points_affine, size_t n,
+                               int compressed, amdmsm_write_fn write, void *write_ctx, size_t chunk_points);
+int amdmsm_write_points_file(amdmsm_ctx *ctx, int curve, int group, const void *d_points_affine, size_t n,
+                             int compressed, const char *path, size_t offset_bytes, size_t chunk_points);
+int amdmsm_plan_write_points(size_t n, size_t chunk_points, size_t k, size_t out[4]);
 int amdmsm_msm_device(amdmsm_ctx *ctx, int curve, int group, const void *d_bases_affine,
                       const void *d_scalars, size_t n, void *d_out_xyz, const amdmsm_opts *opts);
 /* k (<= 8) MSMs of the same group and length in one call: d_bases_affine[j] / d_scalars[j] / d_out_xyz[j] as for

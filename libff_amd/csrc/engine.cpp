@@ -6,6 +6,7 @@
 #include "engine_internal.h"
 #include "group_vtable.h"
 #include "fr_vtable.h"
+#include "write_plan.h"
 
 #include <hip/hip_runtime.h>
 
@@ -15,6 +16,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -83,6 +85,16 @@ struct fb_state {
     int curve = 0, group = 0;
     size_t scalar_size = 0, window = 0;
     unsigned char g[3 * 24 * 2 * 4] = {};   // the generator the resident table was built from
+    // amdmsm_batch_exp_device runs on the caller's stream and does not wait: `used` is recorded behind the last such call
+    // -- the table it built or read, the coefficient slot of `small` -- and every later call of either entry makes its own
+    // stream wait for it, as a workspace slot's `done` does.  h_up: UP_BLOCKS pinned copies of (g, coeff), taken in
+    // turn: the entry copies its host arguments there before it returns; uploaded[b], behind the copy out of block b,
+    // is what the call that takes block b next waits for on the host -- UP_BLOCKS calls later, not the next one.
+    static constexpr unsigned UP_BLOCKS = 4;
+    hipEvent_t used = nullptr, uploaded[UP_BLOCKS] = {};
+    bool used_valid = false, uploaded_valid[UP_BLOCKS] = {};
+    unsigned up_next = 0;
+    void *h_up = nullptr;
 };
 
 // staging of the streaming entries (multi_exp_stream*), kept between calls
@@ -163,6 +175,8 @@ struct amdmsm_ctx {
     size_t call_marks = 0;
     long long call_ticket = -1;
     float aux_ms[4] = {};
+    // the last batch_exp was amdmsm_batch_exp_device, which does not wait: its times are read off aux_ev when asked for
+    bool aux_pending = false, aux_reused = false, aux_normalised = false;
     fr_tw_entry fr_tw[4];                         // a prover alternates omega and omega^-1; a step domain has two transforms each way
     uint64_t fr_clock = 0;
     std::vector<fr_matrix *> fr_mats;
@@ -1181,6 +1195,11 @@ void amdmsm_ctx_destroy(amdmsm_ctx *ctx) {
             if (e) (void)hipEventDestroy(e);
         }
         for (auto &e : ctx->call_ev) (void)hipEventDestroy(e);
+        if (ctx->fb.used) (void)hipEventDestroy(ctx->fb.used);
+        for (hipEvent_t e : ctx->fb.uploaded) {
+            if (e) (void)hipEventDestroy(e);
+        }
+        if (ctx->fb.h_up) (void)hipHostFree(ctx->fb.h_up);
         for (auto &t : ctx->fr_tw) {
             if (t.buf.p) (void)hipFree(t.buf.p);
             if (t.ev) (void)hipEventDestroy(t.ev);
@@ -2811,6 +2830,130 @@ int stream_file_impl(amdmsm_ctx *ctx, int curve, int group, const char *path, si
     close(f.fd);
     return rc;
 }
+
+// A device vector of point records or of on-disk records: the kernels move the records 16 bytes at a time, 8 for the
+// 10-word fields (rec_align); two vectors of one call may not share a byte
+int dev_check_aligned(amdmsm_ctx *ctx, const char *what, const void *p, size_t align) {
+    if ((uintptr_t)p & (align - 1)) return fail(ctx, AMDMSM_ERR_BAD_ARG, std::string(what) + ": not aligned to " + std::to_string(align) + " bytes");
+    return AMDMSM_OK;
+}
+bool dev_ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// what the three encoding entries refuse before they look at the context: a group the library does not carry, and
+// compressed records of an a != 0 curve (the decoder's rule and message)
+int encode_refuse(amdmsm_ctx *ctx, int curve, int group, int compressed) {
+    const group_vtable *vt = find_vt(curve, group);
+    if (!vt) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve/group");
+    if (compressed && vt->coeff_a_nonzero) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "compressed records: a != 0 curve");
+    return AMDMSM_OK;
+}
+// ... and what they ask of the resident source vector (the caller has the context's lock)
+int encode_check_source(amdmsm_ctx *ctx, const group_vtable *vt, const void *d_points_affine, size_t n) {
+    if (n && !d_points_affine) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null pointer");
+    return n ? dev_check_aligned(ctx, "d_points_affine", d_points_affine, rec_align(vt)) : AMDMSM_OK;
+}
+void encode_launch(const group_vtable *vt, hipStream_t st, const void *d_src, size_t n, bool compressed, void *d_dst) {
+    if (compressed) vt->disk_encode_compressed(st, (const uint32_t *)d_src, n, (uint32_t *)d_dst);
+    else vt->disk_encode(st, (const uint32_t *)d_src, n, (uint32_t *)d_dst);
+}
+
+// The writer twin of stream_impl: n compact affine records in HBM leave as libff's on-disk records through `write`,
+// write_plan.h's chunks one after the other.  Chunk k is encoded on the device and copied into pinned staging buffer
+// k % 2 on stream k % 2 (the staging buffers, device buffers and streams of the readers); while that runs the host
+// hands chunk k - 1 to `write`, one call per chunk, in order.  The source has to be complete on the context's stream.
+// A callback that takes fewer bytes than offered ends the call, as a reader that delivers too few ends stream_impl.
+int write_impl(amdmsm_ctx *ctx, int curve, int group, const void *d_points_affine, size_t n, bool compressed,
+               amdmsm_write_fn write, void *write_ctx, size_t chunk_points) {
+    int rc = encode_refuse(ctx, curve, group, compressed);
+    if (rc) return rc;
+    if (!ctx || !write) return AMDMSM_ERR_BAD_ARG;
+    const group_vtable *vt = find_vt(curve, group);
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    dev_guard guard(ctx->device);
+    rc = encode_check_source(ctx, vt, d_points_affine, n);
+    if (rc) return rc;
+    const size_t aff_bytes = (size_t)vt->el_words * 8, rec_bytes = compressed ? aff_bytes / 2 : aff_bytes;
+    const write_plan plan = write_plan_of(n, chunk_points);
+    if (!plan.nchunks) return AMDMSM_OK;
+    constexpr int NB = stream_state::NB;
+    static_assert(NB == WRITE_BUFFERS, "the plan's buffers are the readers' staging buffers");
+    stream_state &ss = ctx->ss;
+    auto finish = [&](int rc_) {
+        for (int b = 0; b < NB; ++b) {
+            if (ss.streams[b]) (void)hipStreamSynchronize(ss.streams[b]);   // nothing of this call may still write the staging
+        }
+        return rc_;
+    };
+#define TRY_W(expr)                                                                                   \
+    do {                                                                                              \
+        hipError_t e_ = (expr);                                                                       \
+        if (e_ != hipSuccess) return finish(fail(ctx, AMDMSM_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_))); \
+    } while (0)
+    const size_t stage_bytes = plan.chunk_points * rec_bytes;
+    for (int b = 0; b < NB && (size_t)b < plan.nchunks; ++b) {
+        if (ss.h_bytes[b] < stage_bytes) {
+            (void)hipDeviceSynchronize();
+            if (ss.h_stage[b]) (void)hipHostFree(ss.h_stage[b]);
+            ss.h_stage[b] = nullptr;
+            ss.h_bytes[b] = 0;
+            TRY_W(hipHostMalloc(&ss.h_stage[b], stage_bytes, hipHostMallocDefault));
+            ss.h_bytes[b] = stage_bytes;
+        }
+        rc = ensure_buf(ctx, ss.d_raw[b], stage_bytes);
+        if (rc) return finish(rc);
+        if (!ss.streams[b]) TRY_W(hipStreamCreateWithFlags(&ss.streams[b], hipStreamNonBlocking));
+    }
+    // the two streams do not wait for the context's stream by themselves
+    TRY_W(hipEventRecord(ctx->bases_ready, ctx->stream));
+    for (int b = 0; b < NB && (size_t)b < plan.nchunks; ++b) TRY_W(hipStreamWaitEvent(ss.streams[b], ctx->bases_ready, 0));
+    auto hand_over = [&](size_t k) {   // chunk k, whose copy is enqueued on its stream, to the callback
+        const write_chunk c = write_plan_chunk(plan, k);
+        TRY_W(hipStreamSynchronize(ss.streams[c.buffer]));
+        const size_t bytes = c.count * rec_bytes;
+        if (write(write_ctx, ss.h_stage[c.buffer], bytes) != bytes) return finish(fail(ctx, AMDMSM_ERR_BAD_ARG, "record stream ended early"));
+        return (int)AMDMSM_OK;
+    };
+    for (size_t k = 0; k < plan.nchunks; ++k) {
+        const write_chunk c = write_plan_chunk(plan, k);   // buffer c.buffer is free: chunk k - 2 has been handed over
+        hipStream_t st = ss.streams[c.buffer];
+        encode_launch(vt, st, (const char *)d_points_affine + c.first * aff_bytes, c.count, compressed, ss.d_raw[c.buffer].p);
+        TRY_W(hipGetLastError());
+        TRY_W(hipMemcpyAsync(ss.h_stage[c.buffer], ss.d_raw[c.buffer].p, c.count * rec_bytes, hipMemcpyDeviceToHost, st));
+        if (k) {
+            rc = hand_over(k - 1);
+            if (rc) return rc;
+        }
+    }
+    rc = hand_over(plan.nchunks - 1);
+    if (rc) return rc;
+    return finish(AMDMSM_OK);
+#undef TRY_W
+}
+
+// the callback of amdmsm_write_points_file: pwrite at the file's running offset, whatever number of calls that takes
+struct file_dst {
+    int fd = -1;
+    size_t pos = 0;
+    bool failed = false;
+};
+size_t file_writer(void *ctxp, const void *src, size_t bytes) {
+    file_dst &f = *(file_dst *)ctxp;
+    size_t done = 0;
+    while (done < bytes) {
+        const ssize_t w = pwrite(f.fd, (const char *)src + done, bytes - done, (off_t)(f.pos + done));
+        if (w < 0 && errno == EINTR) continue;
+        if (w <= 0) {
+            f.failed = true;
+            break;
+        }
+        done += (size_t)w;
+    }
+    f.pos += done;
+    return done;
+}
 }  // namespace
 
 extern "C" {
@@ -2870,6 +3013,66 @@ int amdmsm_disk_decode_device(amdmsm_ctx *ctx, int curve, int group, const void 
     return AMDMSM_OK;
 }
 
+// group_write<encoding_binary, form_montgomery, Comp> over n compact affine points in HBM (curve_serialization.tcc:
+// 78-133), the inverse of amdmsm_disk_decode_device: n records out, enqueued on `stream` and not waited for.
+int amdmsm_disk_encode_device(amdmsm_ctx *ctx, int curve, int group, const void *d_src_affine, size_t n, int compressed,
+                              void *d_records, void *stream) {
+    int rc = encode_refuse(ctx, curve, group, compressed);
+    if (rc) return rc;
+    GET_VT(ctx, curve, group);
+    rc = encode_check_source(ctx, vt, d_src_affine, n);
+    if (rc || !n) return rc;
+    if (!d_records) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null pointer");
+    rc = dev_check_aligned(ctx, "d_records", d_records, rec_align(vt));
+    if (rc) return rc;
+    const size_t aff_bytes = (size_t)vt->el_words * 8;
+    if (dev_ranges_overlap(d_src_affine, n * aff_bytes, d_records, n * (compressed ? aff_bytes / 2 : aff_bytes)))
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_records overlaps d_src_affine");
+    encode_launch(vt, stream ? (hipStream_t)stream : ctx->stream, d_src_affine, n, compressed != 0, d_records);
+    HIP_TRY(ctx, hipGetLastError());
+    return AMDMSM_OK;
+}
+
+int amdmsm_plan_write_points(size_t n, size_t chunk_points, size_t k, size_t out[4]) {
+    if (!out) return AMDMSM_ERR_BAD_ARG;
+    const write_plan p = write_plan_of(n, chunk_points);
+    out[0] = p.nchunks;
+    out[1] = out[2] = out[3] = 0;
+    if (k >= p.nchunks) return AMDMSM_OK;
+    const write_chunk c = write_plan_chunk(p, k);
+    out[1] = c.first;
+    out[2] = c.count;
+    out[3] = (size_t)c.buffer;
+    return AMDMSM_OK;
+}
+
+int amdmsm_write_points_stream(amdmsm_ctx *ctx, int curve, int group, const void *d_points_affine, size_t n, int compressed,
+                               amdmsm_write_fn write, void *write_ctx, size_t chunk_points) {
+    return write_impl(ctx, curve, group, d_points_affine, n, compressed != 0, write, write_ctx, chunk_points);
+}
+
+// the file is opened without truncation and created where absent; the bytes in front of offset_bytes and behind the
+// records stay as they are (the readers' offset_bytes, mirrored)
+int amdmsm_write_points_file(amdmsm_ctx *ctx, int curve, int group, const void *d_points_affine, size_t n, int compressed,
+                             const char *path, size_t offset_bytes, size_t chunk_points) {
+    int rc = encode_refuse(ctx, curve, group, compressed);
+    if (rc) return rc;
+    if (!ctx || !path) return AMDMSM_ERR_BAD_ARG;
+    {   // a refused call creates no file
+        std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+        rc = encode_check_source(ctx, find_vt(curve, group), d_points_affine, n);
+        if (rc) return rc;
+    }
+    file_dst f;
+    f.fd = open(path, O_WRONLY | O_CREAT, 0644);
+    if (f.fd < 0) return fail(ctx, AMDMSM_ERR_BAD_ARG, std::string("cannot open ") + path);
+    f.pos = offset_bytes;
+    rc = write_impl(ctx, curve, group, d_points_affine, n, compressed != 0, file_writer, &f, chunk_points);
+    if (close(f.fd) != 0) f.failed = true;
+    if (f.failed) return fail(ctx, AMDMSM_ERR_BAD_ARG, std::string("cannot write ") + path);
+    return rc;
+}
+
 // multi_exp_stream_with_precompute (multiexp_stream.hpp:29-42, multiexp_stream.tcc:193-223): the
 // stream holds, per base, the num_digits = ceil(Fr::num_bits / c) multiples [2^(jc)]P; every
 // (scalar digit, multiple) pair lands in ONE bucket set and no doublings are needed.  Like the
@@ -2922,6 +3125,9 @@ int amdmsm_batch_exp(amdmsm_ctx *ctx, int curve, int group, size_t scalar_size, 
     if (rc == AMDMSM_OK) rc = ensure_buf(ctx, fb.out, n ? n * xyz_bytes : 16);
     if (rc) return rc;
     char *d_g = (char *)fb.small.p, *d_cf = d_g + xyz_bytes, *d_go = d_cf + xyz_bytes;
+    // a call of amdmsm_batch_exp_device on another stream may still read the table and the coefficient slot
+    if (fb.used_valid) HIP_TRY(ctx, hipStreamWaitEvent(st, fb.used, 0));
+    ctx->aux_pending = false;
     HIP_TRY(ctx, hipEventRecord(ctx->aux_ev[0], st));
     if (!same_table) {
         HIP_TRY(ctx, hipMemcpyAsync(d_g, g_xyz, xyz_bytes, hipMemcpyHostToDevice, st));
@@ -2946,6 +3152,7 @@ int amdmsm_batch_exp(amdmsm_ctx *ctx, int curve, int group, size_t scalar_size, 
     HIP_TRY(ctx, hipEventRecord(ctx->aux_ev[4], st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&ctx->aux_ms[i], ctx->aux_ev[i], ctx->aux_ev[i + 1]);
+    if (same_table) ctx->aux_ms[1] = 0;   // two adjacent events: nothing was built
     fb.valid = true;
     fb.curve = curve;
     fb.group = group;
@@ -2956,10 +3163,20 @@ int amdmsm_batch_exp(amdmsm_ctx *ctx, int curve, int group, size_t scalar_size, 
 }
 
 // device times of the last amdmsm_batch_exp of this context: ms[0] inputs host -> device, ms[1] window table
-// (0 when the resident table was reused), ms[2] the exponentiations (k_fb_exp), ms[3] results device -> host
+// (0 when the resident table was reused), ms[2] the exponentiations (k_fb_exp), ms[3] results device -> host.
+// After amdmsm_batch_exp_device, which returns with its work enqueued: the call is waited for here, ms[0] is the upload
+// of g / coeff and ms[3] the normalisation (0 for AMDMSM_OUT_LIBFF).
 int amdmsm_get_batch_exp_timings(amdmsm_ctx *ctx, float ms[4]) {
     if (!ctx || !ms) return AMDMSM_ERR_BAD_ARG;
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    if (ctx->aux_pending) {
+        dev_guard guard(ctx->device);
+        HIP_TRY(ctx, hipEventSynchronize(ctx->aux_ev[4]));
+        for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&ctx->aux_ms[i], ctx->aux_ev[i], ctx->aux_ev[i + 1]);
+        if (ctx->aux_reused) ctx->aux_ms[1] = 0;
+        if (!ctx->aux_normalised) ctx->aux_ms[3] = 0;
+        ctx->aux_pending = false;
+    }
     for (int i = 0; i < 4; ++i) ms[i] = ctx->aux_ms[i];
     return AMDMSM_OK;
 }
@@ -3157,6 +3374,116 @@ int amdmsm_scalar_mul_vec(amdmsm_ctx *ctx, int curve, int group, const void *poi
         return smv_chunk(ctx, vt, st, (const uint32_t *)ctx->hb_aff.p, (const uint32_t *)ctx->hb_sc.p, m, (uint32_t *)ctx->fb.out.p, vo,
                          sl, first);
     });
+}
+
+// amdmsm_batch_exp on device-resident scalars, the results left in HBM: what a key generator whose Fr vectors are
+// already there (amdmsm_fr_lincomb_device) calls instead of a download, the host entry and an upload.  The resident
+// window table (fb_state) is the host entry's, under its reuse rule, and the kernels are its kernels; the results in
+// special form come from vec_finish, the batch normalisation of the point-vector entries, its scratch a workspace slot.
+// Enqueued on the caller's stream and not waited for: g and coeff are copied into pinned memory before the call returns.
+int amdmsm_batch_exp_device(amdmsm_ctx *ctx, int curve, int group, size_t scalar_size, size_t window, const void *g_xyz,
+                            const void *d_scalars, size_t n, const void *coeff, void *d_out_xyz, const amdmsm_opts *opts) {
+    SMV_REFUSE_UNKNOWN(ctx, curve, group);
+    if (window < 1 || window > 22 || scalar_size < 1 || scalar_size > (size_t)find_vt(curve, group)->fr_words * 32)
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "window / scalar_size");
+    GET_VT(ctx, curve, group);
+    CHECK_OPTS(ctx, opts);
+    const vec_opts vo = vec_opts_of(opts);
+    if (vo.form != AMDMSM_OUT_LIBFF && vo.form != AMDMSM_OUT_AFFINE)
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "out_form: AMDMSM_OUT_LIBFF or AMDMSM_OUT_AFFINE");
+    if (!g_xyz || (n && (!d_scalars || !d_out_xyz))) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null pointer");
+    const size_t xyz_bytes = (size_t)vt->el_words * 12, aff_bytes = (size_t)vt->el_words * 8, fr_bytes = (size_t)vt->fr_words * 4;
+    if (n) {
+        int rc = dev_check_aligned(ctx, "d_scalars", d_scalars, vt->fr_words % 4 ? 8 : 16);
+        if (rc == AMDMSM_OK) rc = dev_check_aligned(ctx, "d_out_xyz", d_out_xyz, rec_align(vt));
+        if (rc) return rc;
+        if (dev_ranges_overlap(d_scalars, n * fr_bytes, d_out_xyz, n * xyz_bytes))
+            return fail(ctx, AMDMSM_ERR_BAD_ARG, "d_out_xyz overlaps d_scalars");
+    }
+    const size_t outerc = (scalar_size + window - 1) / window;
+    const size_t entries = outerc << window;
+    hipStream_t st = stream_of(ctx, opts);
+    fb_state &fb = ctx->fb;
+    const bool same_table = fb.valid && fb.curve == curve && fb.group == group && fb.scalar_size == scalar_size &&
+                            fb.window == window && memcmp(fb.g, g_xyz, xyz_bytes) == 0;
+    int rc = ensure_buf(ctx, fb.small, 2 * xyz_bytes + outerc * xyz_bytes + 64);
+    if (rc == AMDMSM_OK && !same_table) {
+        fb.valid = false;
+        rc = ensure_buf(ctx, fb.table, entries * xyz_bytes);
+        if (rc == AMDMSM_OK) rc = ensure_buf(ctx, fb.table_aff, entries * aff_bytes);
+    }
+    if (rc) return rc;
+    if (!fb.used) HIP_TRY(ctx, hipEventCreateWithFlags(&fb.used, hipEventDisableTiming));
+    for (hipEvent_t &e : fb.uploaded) {
+        if (!e) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    if (!fb.h_up) HIP_TRY(ctx, hipHostMalloc(&fb.h_up, fb_state::UP_BLOCKS * 2 * sizeof(fb.g), hipHostMallocDefault));
+    char *d_g = (char *)fb.small.p, *d_cf = d_g + xyz_bytes, *d_go = d_cf + xyz_bytes;
+    // the last call of this entry, on whatever stream: it may still read the table and the coefficient slot
+    if (fb.used_valid) HIP_TRY(ctx, hipStreamWaitEvent(st, fb.used, 0));
+    // From the first launch on, whatever way the call ends, `used` stands behind what it has enqueued: a call that fails
+    // half way leaves kernels that read the table, and the next call on another stream has to wait for them too.
+    struct used_guard {
+        fb_state &fb;
+        hipStream_t st;
+        ~used_guard() {
+            if (hipEventRecord(fb.used, st) == hipSuccess) fb.used_valid = true;
+        }
+    } mark_used{fb, st};
+    ctx->aux_pending = false;
+    HIP_TRY(ctx, hipEventRecord(ctx->aux_ev[0], st));
+    if (!same_table || coeff) {
+        const unsigned blk = fb.up_next++ % fb_state::UP_BLOCKS;
+        char *h_g = (char *)fb.h_up + (size_t)blk * 2 * sizeof(fb.g), *h_cf = h_g + sizeof(fb.g);
+        if (fb.uploaded_valid[blk]) HIP_TRY(ctx, hipEventSynchronize(fb.uploaded[blk]));   // the copy out of this block, UP_BLOCKS uploads ago
+        if (!same_table) {
+            memcpy(h_g, g_xyz, xyz_bytes);
+            HIP_TRY(ctx, hipMemcpyAsync(d_g, h_g, xyz_bytes, hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemsetAsync(fb.table.p, 0, entries * xyz_bytes, st));   // rows shorter than 2^window: infinity beyond
+        }
+        if (coeff) {
+            memcpy(h_cf, coeff, fr_bytes);
+            HIP_TRY(ctx, hipMemcpyAsync(d_cf, h_cf, fr_bytes, hipMemcpyHostToDevice, st));
+        }
+        HIP_TRY(ctx, hipEventRecord(fb.uploaded[blk], st));
+        fb.uploaded_valid[blk] = true;
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->aux_ev[1], st));
+    if (!same_table) {
+        vt->fixed_base_exp(st, (const uint32_t *)d_g, (int)scalar_size, (int)window, nullptr, 0, 0, nullptr, AMDMSM_OUT_LIBFF,
+                           (uint32_t *)d_go, (uint32_t *)fb.table.p, (uint32_t *)fb.table_aff.p, 1, nullptr);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->aux_ev[2], st));
+    if (n) {
+        vt->fixed_base_exp(st, (const uint32_t *)d_g, (int)scalar_size, (int)window, (const uint32_t *)d_scalars, n, vo.mont,
+                           coeff ? (const uint32_t *)d_cf : nullptr, AMDMSM_OUT_LIBFF, (uint32_t *)d_go, (uint32_t *)fb.table.p,
+                           (uint32_t *)fb.table_aff.p, 0, (uint32_t *)d_out_xyz);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->aux_ev[3], st));
+    const bool normalise = n && vo.form == AMDMSM_OUT_AFFINE;
+    if (normalise) {
+        ws_slot *sl = nullptr;
+        rc = slot_begin(ctx, st, n * aff_bytes, sl);
+        if (rc) return rc;
+        for (int i = 0; i < 5; ++i) record(ctx, *sl, i, st);   // a timed context: the whole slot time is normalisation
+        vec_finish(vt, st, vo, (uint32_t *)d_out_xyz, n, (uint32_t *)sl->ws);
+        HIP_TRY(ctx, hipGetLastError());
+        rc = slot_end(ctx, st, *sl);
+        if (rc) return rc;
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->aux_ev[4], st));
+    ctx->aux_pending = true;
+    ctx->aux_reused = same_table;
+    ctx->aux_normalised = normalise;
+    fb.valid = true;
+    fb.curve = curve;
+    fb.group = group;
+    fb.scalar_size = scalar_size;
+    fb.window = window;
+    memcpy(fb.g, g_xyz, xyz_bytes);
+    return AMDMSM_OK;
 }
 
 }  // extern "C"

@@ -215,6 +215,10 @@ struct group_vtable {
     // the compressed form of the same records (X with two flag bits, Y by square root);
     // *status |= 2 where X is not the abscissa of a curve point
     void (*disk_decode_compressed)(hipStream_t, const uint32_t* src, size_t n, uint32_t* dst_affine, uint32_t* status);
+    // compact affine -> the same on-disk records, n * 2 * el_words words; the compact zero (0, 0) is written as (0, one)
+    void (*disk_encode)(hipStream_t, const uint32_t* src_affine, size_t n, uint32_t* dst);
+    // ... and their compressed form, n * el_words words: X with the two flag bits, zero as X = 0 with flag 2 (a = 0 curves)
+    void (*disk_encode_compressed)(hipStream_t, const uint32_t* src_affine, size_t n, uint32_t* dst);
 
     // ---- digits and sort ----------
     // stats[0] += #scalars equal to zero, stats[1] += #scalars equal to one (multi_exp_filter_one_zero's

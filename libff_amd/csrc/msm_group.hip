@@ -2786,6 +2786,52 @@ __global__ void __launch_bounds__(64) k_disk_decode_compressed(const uint32_t* _
     store_aff(dst + i * AFFW, a);
 }
 
+// The writers of the same two record forms (group_write<encoding_binary, form_montgomery, compression_{off,on}>,
+// curve_serialization.tcc:78-133), the inverses of the two decoders above: compact affine records in, one lane per
+// record, the lanes of a wave on consecutive records and the grid striding over the vector.  Every index comes from n and
+// the launch geometry.  flags: or-ed into the top two bits of the component's highest limb -- the first byte written.
+template <bool I>
+AMDMSM_DEV void store_be_raw(uint32_t* __restrict__ dst, const Fp<FQ, I>& a, uint32_t flags) {
+    Fp<FQ, I> t;
+#pragma unroll
+    for (int j = 0; j < FQ::N; ++j) t.v[j] = bswap32(a.v[FQ::N - 1 - j]);
+    t.v[0] = bswap32(a.v[FQ::N - 1] | (flags << 30));
+    fp_store(dst, t);
+}
+template <bool I>
+AMDMSM_DEV void store_coord_disk(uint32_t* dst, const Fp<FQ, I>& a, uint32_t flags) { store_be_raw(dst, a, flags); }
+template <int NR, bool I>
+AMDMSM_DEV void store_coord_disk(uint32_t* dst, const Fp2<FQ, NR, I>& a, uint32_t flags) {
+    store_be_raw(dst, a.c0, flags);
+    store_be_raw(dst + FQ::N, a.c1, 0u);
+}
+
+// X || Y; the compact zero (0, 0) leaves as (0, one), what the reference writes after to_affine_coordinates on zero
+__global__ void __launch_bounds__(TPB) k_disk_encode(const uint32_t* __restrict__ src, size_t n, uint32_t* __restrict__ dst) {
+    const size_t step = (size_t)gridDim.x * TPB;
+    for (size_t i = gtid(); i < n; i += step) {
+        Aff<E> a;
+        load_aff(a, src + i * AFFW);
+        if (el_is_zero(a.x) && el_is_zero(a.y)) el_one(a.y);
+        store_coord_disk(dst + i * AFFW, a.x, 0u);
+        store_coord_disk(dst + i * AFFW + EW, a.y, 0u);
+    }
+}
+
+// X only, flag bit 0 = the low bit of Y's (Y.c0's) Montgomery word 0, flag bit 1 = zero, which is written as X = 0 with
+// that flag alone (curve_serialization.tcc:103-133 on G::zero()).  For the a = 0 curves, as the decoder.
+__global__ void __launch_bounds__(TPB) k_disk_encode_compressed(const uint32_t* __restrict__ src, size_t n,
+                                                                uint32_t* __restrict__ dst) {
+    const size_t step = (size_t)gridDim.x * TPB;
+    for (size_t i = gtid(); i < n; i += step) {
+        Aff<E> a;
+        load_aff(a, src + i * AFFW);
+        const bool zero = el_is_zero(a.x) && el_is_zero(a.y);
+        const uint32_t flags = zero ? 2u : (coord_c0(a.y).v[0] & 1u);
+        store_coord_disk(dst + i * EW, a.x, flags);
+    }
+}
+
 // ------------------------------------------------- fixed-base exponentiation
 // batch_exp / batch_exp_with_coeff (multiexp.tcc:874-947): res[i] = v[i] * g through a window
 // table powers_of_g[outer][inner] = inner * 2^(outer*window) * g (get_window_table,
@@ -4210,6 +4256,18 @@ void l_disk_decode_compressed(hipStream_t st, const uint32_t* src, size_t n, uin
     if (!n) return;
     hipLaunchKernelGGL(k_disk_decode_compressed, dim3(blocks_for(n, 64)), dim3(64), 0, st, src, n, dst, status);
 }
+// the encoders stride: at most DISK_ENCODE_BLOCKS workgroups, each lane taking records TPB * grid apart
+constexpr size_t DISK_ENCODE_BLOCKS = 8192;
+void l_disk_encode(hipStream_t st, const uint32_t* src, size_t n, uint32_t* dst) {
+    if (!n) return;
+    const unsigned blocks = (unsigned)std::min<size_t>((n + TPB - 1) / TPB, DISK_ENCODE_BLOCKS);
+    hipLaunchKernelGGL(k_disk_encode, dim3(blocks), dim3(TPB), 0, st, src, n, dst);
+}
+void l_disk_encode_compressed(hipStream_t st, const uint32_t* src, size_t n, uint32_t* dst) {
+    if (!n) return;
+    const unsigned blocks = (unsigned)std::min<size_t>((n + TPB - 1) / TPB, DISK_ENCODE_BLOCKS);
+    hipLaunchKernelGGL(k_disk_encode_compressed, dim3(blocks), dim3(TPB), 0, st, src, n, dst);
+}
 // table: outerc * 2^window Jacobian points of scratch, gouter: outerc points, table_aff: outerc * 2^window
 // compact affine records (what k_fb_exp reads).  build_table = 0: table_aff already holds the table of this
 // (g, scalar_size, window) -- the caller keeps it between calls.
@@ -4366,6 +4424,7 @@ const group_vtable g_vt = {
     .endo_points = l_endo_points, .precompute_table = l_precompute_table,
     .ffi_decode_points = l_ffi_decode_points, .ffi_decode_scalars = l_ffi_decode_scalars, .ffi_encode_point = l_ffi_encode_point,
     .disk_decode = l_disk_decode, .disk_decode_compressed = l_disk_decode_compressed,
+    .disk_encode = l_disk_encode, .disk_encode_compressed = l_disk_encode_compressed,
     // digits and sort
     .scalar_stats = l_scalar_stats, .scalar_bits = l_scalar_bits, .gather_scalars = l_gather_scalars,
     .count = l_count, .scatter = l_scatter, .sort = l_sort, .sort_top_window = l_sort_top_window,

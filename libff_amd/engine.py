@@ -77,6 +77,8 @@ EXPORTED_SYMBOLS = [
     "amdmsm_fr_domain_divide_by_z", "amdmsm_fr_domain_divide_by_z_device",
     "amdmsm_fr_domain_lagrange", "amdmsm_fr_domain_lagrange_device",
     "amdmsm_fr_matrix_load_transposed", "amdmsm_plan_fr_matrix_transposed", "amdmsm_fr_lincomb_device",
+    "amdmsm_batch_exp_device", "amdmsm_disk_encode_device", "amdmsm_write_points_stream", "amdmsm_write_points_file",
+    "amdmsm_plan_write_points",
 ]
 SEG_SHARED_BASES = 1            # include/amdmsm.h AMDMSM_SEG_SHARED_BASES
 SEG_LONG_NEVER = 2 ** 64 - 1    # long_from = SIZE_MAX: no segment takes the single-MSM route
@@ -592,6 +594,23 @@ def _fr_array(curve, a):
 
 # include/amdmsm.h amdmsm_read_fn: size_t read(void *read_ctx, void *dst, size_t bytes)
 _READ_FN = ctypes.CFUNCTYPE(ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
+# include/amdmsm.h amdmsm_write_fn: size_t write(void *write_ctx, const void *src, size_t bytes)
+_WRITE_FN = ctypes.CFUNCTYPE(ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
+
+
+def plan_write_points(n, chunk_points=0):
+    """The chunks of ``Engine.write_points_stream`` / ``write_points_file`` over ``n`` records
+    (``amdmsm_plan_write_points``, no device): a list of ``(first record, records, staging buffer)``."""
+    lib, out, chunks = load_library(), (ctypes.c_size_t * 4)(), []
+    k = 0
+    while True:
+        rc = lib.amdmsm_plan_write_points(ctypes.c_size_t(n), ctypes.c_size_t(chunk_points), ctypes.c_size_t(k), out)
+        if rc:
+            raise AmdMsmError(f"amdmsm_plan_write_points: {rc}")
+        if k >= out[0]:
+            return chunks
+        chunks.append((int(out[1]), int(out[2]), int(out[3])))
+        k += 1
 
 
 def _records(a, stride_bytes, g_bytes):
@@ -884,6 +903,79 @@ class Engine:
         finally:
             for p in (d_rec, d_aff, d_xyz):
                 self.free(p)
+
+    def disk_encode_device(self, curve, group, d_points_affine, n, d_records, compressed=False, stream=None):
+        """group_write<encoding_binary, form_montgomery, compression_{off,on}> of ``n`` compact affine points in HBM
+        (``amdmsm_disk_encode_device``): ``n`` records to ``d_records``; enqueued on ``stream``, not synchronised."""
+        self._check(self.lib.amdmsm_disk_encode_device(self.h, curve, group, _opt_dev(d_points_affine), ctypes.c_size_t(n),
+                                                       int(compressed), _opt_dev(d_records), _vp(stream)),
+                    "amdmsm_disk_encode_device")
+
+    def disk_encode(self, curve, group, points_xyz, compressed=False, base_form=multi_exp_base_form_normal):
+        """The twin of ``disk_decode``: (n, 3 * coordinate limbs) libff records in ``base_form`` -> their on-disk records
+        as a uint8 array, encoded on the device."""
+        pts = np.ascontiguousarray(points_xyz, dtype=np.uint64)
+        s = sizes(curve, group)
+        n = pts.shape[0] if pts.ndim == 2 else 0
+        rec = s["affine_bytes"] // 2 if compressed else s["affine_bytes"]
+        out = np.zeros(n * rec, dtype=np.uint8)
+        d_xyz, d_aff, d_rec = self.malloc(max(16, pts.nbytes)), self.malloc(max(16, n * s["affine_bytes"])), \
+            self.malloc(max(16, n * rec))
+        try:
+            if n:
+                assert pts.shape[1] * 8 == s["g_bytes"], "points must be (n, 3*coord_limbs) uint64"
+                self.h2d(d_xyz, pts)
+                self.import_bases_device(curve, group, d_xyz, s["g_bytes"], base_form, n, d_aff)
+            self.disk_encode_device(curve, group, d_aff, n, d_rec, compressed)
+            self.synchronize()
+            if n:
+                self.d2h(out, d_rec)
+            return out
+        finally:
+            for p in (d_xyz, d_aff, d_rec):
+                self.free(p)
+
+    def write_points_file(self, curve, group, d_points_affine, n, path, offset_bytes=0, compressed=False, chunk_points=0):
+        """``n`` compact affine points in HBM into ``path`` as libff's on-disk records (``amdmsm_write_points_file``), from
+        ``offset_bytes`` on; the file is not truncated.  What ``multi_exp_stream_file`` and its siblings read."""
+        self._check(self.lib.amdmsm_write_points_file(self.h, curve, group, _opt_dev(d_points_affine), ctypes.c_size_t(n),
+                                                      int(compressed), os.fsencode(path), ctypes.c_size_t(offset_bytes),
+                                                      ctypes.c_size_t(chunk_points)), "amdmsm_write_points_file")
+
+    def write_points_stream(self, curve, group, d_points_affine, n, writer, compressed=False, chunk_points=0):
+        """The same records through ``writer.write(bytes)`` (``amdmsm_write_points_stream``): one call per chunk of
+        ``chunk_points`` records, in order.  A ``write`` that returns a number below the length it was given ends the
+        call (AmdMsmError); one that returns None has taken everything.  An exception raised by ``writer`` ends the call
+        and is raised again after it."""
+        raised = []
+
+        def write(_ctx, src, nbytes):
+            try:
+                took = writer.write(ctypes.string_at(src, nbytes))
+                return int(nbytes) if took is None else max(0, min(int(took), int(nbytes)))
+            except BaseException as e:   # an exception cannot cross the C frames: end the call, raise afterwards
+                raised.append(e)
+                return 0
+
+        cb = _WRITE_FN(write)   # referenced from this frame for as long as the library may call it
+        rc = self.lib.amdmsm_write_points_stream(self.h, curve, group, _opt_dev(d_points_affine), ctypes.c_size_t(n),
+                                                 int(compressed), cb, None, ctypes.c_size_t(chunk_points))
+        del cb
+        if raised:
+            raise raised[0]
+        self._check(rc, "amdmsm_write_points_stream")
+
+    def batch_exp_device(self, curve, group, scalar_size, window, g, d_scalars, n, d_out_xyz, coeff=None,
+                         scalars_plain=False, out_form=OUT_LIBFF, stream=None):
+        """``batch_exp`` on ``n`` device-resident scalars, the results left at ``d_out_xyz`` (``amdmsm_batch_exp_device``);
+        ``g`` and ``coeff`` are host arrays.  Shares the resident window table with ``batch_exp``; enqueued on
+        ``stream``, not synchronised (``batch_exp_timings`` waits for it)."""
+        g = None if g is None else np.ascontiguousarray(g, dtype=np.uint64)
+        cf = None if coeff is None else np.ascontiguousarray(coeff, dtype=np.uint64)
+        o = self._opts(out_form=out_form, scalars_plain=scalars_plain, stream=stream)
+        self._check(self.lib.amdmsm_batch_exp_device(self.h, curve, group, ctypes.c_size_t(scalar_size), ctypes.c_size_t(window),
+                                                     _opt_ptr(g), _opt_dev(d_scalars), ctypes.c_size_t(n), _opt_ptr(cf),
+                                                     _opt_dev(d_out_xyz), ctypes.byref(o)), "amdmsm_batch_exp_device")
 
     def multi_exp_stream_with_precompute_file(self, curve, group, path, scalars, precompute_c, offset_bytes=0,
                                               chunk_points=0, out_form=OUT_AFFINE, scalars_plain=False):
@@ -1338,7 +1430,9 @@ class Engine:
                                                       ctypes.byref(o), _opt_dev(d_out)), "amdmsm_fr_lincomb_device")
 
     def batch_exp_timings(self):
-        """device times (ms) of the last batch_exp: inputs H2D, window table (0 = reused), exponentiations, results D2H"""
+        """device times (ms) of the last batch_exp: inputs H2D, window table (0 = reused), exponentiations, results D2H.
+        After ``batch_exp_device`` the call is waited for; ``h2d_ms`` is then the upload of g / coeff and ``d2h_ms`` the
+        normalisation (0 for ``OUT_LIBFF``)."""
         ms = (ctypes.c_float * 4)()
         self._check(self.lib.amdmsm_get_batch_exp_timings(self.h, ms), "amdmsm_get_batch_exp_timings")
         return {"h2d_ms": ms[0], "table_ms": ms[1], "exp_ms": ms[2], "d2h_ms": ms[3]}
