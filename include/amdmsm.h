@@ -121,6 +121,8 @@ int amdmsm_device_count(void);
 int amdmsm_ctx_create(int device, amdmsm_ctx **out);
 void amdmsm_ctx_destroy(amdmsm_ctx *ctx);
 const char *amdmsm_strerror(int code);
+/* the message of the context's last refusal; with a NULL context, of the calling thread's last refusal that had none
+   (an entry refuses its arguments before it looks at the context) */
 const char *amdmsm_last_error(const amdmsm_ctx *ctx);
 
 /* out[0] = sizeof(Fr), out[1] = sizeof(G) (X,Y,Z), out[2] = compact affine bytes, out[3] = Fr bits */
@@ -321,6 +323,34 @@ int amdmsm_fr_fft_device(amdmsm_ctx *ctx, int curve, const void *d_values, size_
    call with pre and post given.  AMDMSM_ERR_BAD_ARG for n not a power of two or a tile out of range,
    AMDMSM_ERR_TOO_LARGE above 2^28 */
 int amdmsm_plan_fr_fft(int curve, size_t n, int tile_log2, size_t out[6]);
+/* The same transform over `batch` vectors of n records with one set of parameters: the A, B and C of a witness map, the
+ * columns of a trace, the rows of a two-dimensional transform.  Every vector gets exactly the records amdmsm_fr_fft_device
+ * gives it alone, bit for bit, in both record forms and with pre / post / scale; the batch goes through one chain of
+ * passes (k_fr_fft_pass_batch) whose grid covers all vectors: batch * n / 2^10 workgroups from
+ * n = 2^10 on, and below that ceil(batch / V) workgroups that hold V = 2^10 / n whole vectors each.
+ *   d_values, d_out   vector v starts in_stride * v records into d_values and out_stride * v records into d_out; the
+ *                     records between the vectors are neither read nor written.  d_out == d_values with equal strides
+ *                     runs in place; any other overlap of the ranges [d, d + ((batch - 1) * stride + n) records) is
+ *                     AMDMSM_ERR_BAD_ARG.  Alignment as for amdmsm_fr_fft_device (a stride in records keeps it).  The
+ *                     host entry takes and gives packed vectors (stride n)
+ *   batch * n         at most 2^28; batch = 0 and n = 0 succeed and write nothing
+ * Workspace, from the context's slots: batch vectors of n records (two such sets for an in-place call of an odd number
+ * of passes above one; the host entry adds the uploaded set), one copy of the powers of pre and post, and the n / 2
+ * powers of omega from the context's cache.
+ * Refused before anything is launched or written and before the context is looked at, amdmsm_last_error naming the
+ * argument: everything amdmsm_fr_fft_device refuses, with its code and message; AMDMSM_ERR_TOO_LARGE for batch * n > 2^28
+ * and for a stride with which the batch does not fit size_t; AMDMSM_ERR_BAD_ARG for a stride below n with batch > 1,
+ * overlapping ranges and misaligned vectors.  Timing phases as for amdmsm_fr_fft_device. */
+int amdmsm_fr_fft_batch_device(amdmsm_ctx *ctx, int curve, const void *d_values, size_t n, size_t batch, size_t in_stride,
+                               size_t out_stride, const void *omega, const void *pre, const void *post, const void *scale,
+                               int tile_log2, const amdmsm_opts *opts, void *d_out);
+int amdmsm_fr_fft_batch(amdmsm_ctx *ctx, int curve, const void *values, size_t n, size_t batch, const void *omega, const void *pre,
+                        const void *post, const void *scale, int tile_log2, const amdmsm_opts *opts, void *out);
+/* read-only, no context: out[0] = tile (log2) in use, out[1] = global passes, out[2] = vectors of one workgroup (2^10 / n
+   below 2^10 records, else 1), out[3] = workgroups of a pass, out[4] = launches of the pass kernel, out[5] = butterflies,
+   out[6] / out[7] = workspace bytes of an out-of-place / in-place device call with pre and post given.  Codes as
+   amdmsm_plan_fr_fft, AMDMSM_ERR_TOO_LARGE also for batch * n > 2^28 */
+int amdmsm_plan_fr_fft_batch(int curve, size_t n, size_t batch, int tile_log2, size_t out[8]);
 /* libff's get_root_of_unity<Fr>(2^log2_n) -- Fr::root_of_unity squared s - log2_n times, s the 2-adicity of r - 1 -- as
    a plain integer of fr_bytes; no context.  AMDMSM_ERR_BAD_ARG beyond s */
 int amdmsm_fr_root_of_unity(int curve, int log2_n, void *r_plain_out);
@@ -490,6 +520,44 @@ int amdmsm_fr_domain_divide_by_z_device(amdmsm_ctx *ctx, int curve, size_t m, co
  * [AMDMSM_PH_TOTAL] the call. */
 int amdmsm_fr_domain_lagrange_device(amdmsm_ctx *ctx, int curve, size_t m, const void *t, const amdmsm_opts *opts, void *d_out);
 int amdmsm_fr_domain_lagrange(amdmsm_ctx *ctx, int curve, size_t m, const void *t, const amdmsm_opts *opts, void *out);
+/* amdmsm_fr_domain_fft_device over `batch` vectors of m records, laid out and refused as the vectors of
+ * amdmsm_fr_fft_batch_device (a stride below m is refused); every vector gets what the single entry gives it, bit for
+ * bit.  On a step domain the radix-2 transforms of B and of S records go through the batched passes; the fold, merge and
+ * combine sweeps are enqueued vector by vector.  batch = 0 succeeds and writes nothing. */
+int amdmsm_fr_domain_fft_batch_device(amdmsm_ctx *ctx, int curve, const void *d_values, size_t m, size_t batch, size_t in_stride,
+                                      size_t out_stride, int flags, const void *coset, int tile_log2, const amdmsm_opts *opts,
+                                      void *d_out);
+
+/* libsnark's r1cs_to_qap_witness_map as one call: from the full assignment z and the three constraint matrices, kept on
+ * the device by amdmsm_fr_matrix_load (below; the input-consistency rows are rows of A that the caller adds), the
+ * m + 1 coefficients of H.  With aA, aB, aC the applies of the three handles on z, zero-filled to m records, A, B, C
+ * the polynomials of degree < m with those values on the domain of m points, Z its vanishing polynomial:
+ *     (A + d1 Z) (B + d2 Z) - (C + d3 Z) = H Z,    H = (A B - C) / Z + d2 A + d1 B + d1 d2 Z - d3
+ *   m       a size amdmsm_fr_domain answers with, at most 2^28; every handle has at most m rows
+ *   d_z     n_z records, n_z at least the columns of every handle;  d_h  m + 1 records, not overlapping d_z
+ *   blind   d1, d2, d3: three packed records in host memory, or NULL for none (libsnark's Groth16 prover); then
+ *           h[m - 1] = h[m] = 0
+ * Records -- z, h and the blinding -- in the form opts->scalars_plain says.  One slot of workspace (three vectors of m
+ * records, the batched transform's and the division's workspace; amdmsm_plan_fr_qap_witness_map reports it without the
+ * applies' partial sums) and this chain on one stream: three applies, one batch of three inverse transforms, with
+ * blinding d2 A + d1 B, one batch of three coset transforms by amdmsm_fr_multiplicative_generator, a b - c, the division
+ * by Z, one inverse coset transform, and the few terms of d1 d2 Z - d3.  The records are those of the twelve single calls.
+ * The device entry is enqueued on opts->stream (or the context's) and not synchronised; the host entry uploads z, runs,
+ * downloads h and synchronises.
+ * Refused before anything is launched or written: AMDMSM_ERR_UNSUPPORTED for an unknown curve and the domains left out;
+ * AMDMSM_ERR_TOO_LARGE for m or n_z above 2^28; AMDMSM_ERR_BAD_ARG, amdmsm_last_error naming the argument, for an m that
+ * is no domain size, a null or misaligned vector, d_h overlapping d_z, a blinding record not below r, a wrong
+ * opts->struct_size -- these before the context is looked at -- and for a handle that is not a live handle of this
+ * context or belongs to another curve, a handle with more than m rows, n_z below a handle's columns.
+ * With timing enabled: [0] the tables of powers (host entry: with the upload), [1] the kernels, [2] the download (host
+ * entry), [AMDMSM_PH_TOTAL] the call.
+ * amdmsm_plan_fr_qap_witness_map, read-only and without a context: out[0] = the domain's kind, out[1] = m, out[2] = B,
+ * out[3] = S, out[4] = workspace bytes, out[5] = launches of the batched pass kernel. */
+int amdmsm_fr_qap_witness_map_device(amdmsm_ctx *ctx, int curve, uint64_t mat_a, uint64_t mat_b, uint64_t mat_c, const void *d_z,
+                                     size_t n_z, size_t m, const void *blind, const amdmsm_opts *opts, void *d_h);
+int amdmsm_fr_qap_witness_map(amdmsm_ctx *ctx, int curve, uint64_t mat_a, uint64_t mat_b, uint64_t mat_c, const void *z, size_t n_z,
+                              size_t m, const void *blind, const amdmsm_opts *opts, void *h);
+int amdmsm_plan_fr_qap_witness_map(int curve, size_t m, size_t out[6]);
 
 /* Sparse matrix times Fr vector -- the rows <A_i, z>, <B_i, z>, <C_i, z> of a constraint system on a resident
  * assignment, the vectors the transforms above start from -- and any other sparse linear map over Fr:

@@ -205,8 +205,10 @@ const group_vtable *find_vt(int curve, int group) {
 // alignment of a libff record stride: the device loads coordinates 16 bytes at a time, 8 for the 10-word fields
 size_t rec_align(const group_vtable *vt) { return vt->fq_words % 4 ? 8 : 16; }
 
+thread_local std::string g_err_no_ctx;   // the last refusal of a call that was given no context
 int fail(amdmsm_ctx *ctx, int code, const std::string &msg) {
     if (ctx) ctx->err = msg;
+    else g_err_no_ctx = msg;
     return code;
 }
 
@@ -1103,7 +1105,7 @@ const char *amdmsm_strerror(int code) {
     }
 }
 
-const char *amdmsm_last_error(const amdmsm_ctx *ctx) { return ctx ? ctx->err.c_str() : ""; }
+const char *amdmsm_last_error(const amdmsm_ctx *ctx) { return ctx ? ctx->err.c_str() : g_err_no_ctx.c_str(); }
 
 int amdmsm_ctx_create(int device, amdmsm_ctx **out) {
     if (!out) return AMDMSM_ERR_BAD_ARG;
@@ -4231,14 +4233,14 @@ struct frfft_params {
 // The argument rules both entries share; no device is needed and nothing is launched or written before they hold.
 int frfft_check(amdmsm_ctx *ctx, const fr_vtable *f, const void *values, size_t n, const void *omega, const void *pre,
                 const void *post, const void *scale, int tile_log2, const amdmsm_opts *opts, const void *out, frfft_plan &plan,
-                frfft_params &pr) {
+                frfft_params &pr, bool need_vectors = true) {
     if (n & (n - 1)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "n = " + std::to_string(n) + " is not a power of two");
     if (n > FR_FFT_MAX_N) return fail(ctx, AMDMSM_ERR_TOO_LARGE, "n = " + std::to_string(n) + ": at most 2^28 records");
     if (frfft_make_plan(f, n, tile_log2, plan))
         return fail(ctx, AMDMSM_ERR_BAD_ARG, "tile_log2 = " + std::to_string(tile_log2) + ": 0 or " + std::to_string(FR_TILE_MIN) +
                                                  " .. " + std::to_string(FR_TILE_MAX));
-    if (n && !values) return fail(ctx, AMDMSM_ERR_BAD_ARG, "values: null pointer");
-    if (n && !out) return fail(ctx, AMDMSM_ERR_BAD_ARG, "output: null pointer");
+    if (n && need_vectors && !values) return fail(ctx, AMDMSM_ERR_BAD_ARG, "values: null pointer");
+    if (n && need_vectors && !out) return fail(ctx, AMDMSM_ERR_BAD_ARG, "output: null pointer");
     if (n > 1 && !omega) return fail(ctx, AMDMSM_ERR_BAD_ARG, "omega: null pointer");
     pr.plain = opts && opts->scalars_plain;
     if (n > 1) {
@@ -4286,6 +4288,45 @@ int frfft_twiddles(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, size_t n
     return AMDMSM_OK;
 }
 
+// the four vectors of powers of pre and post, laid out as frfft_plan has them behind its first vector; tab: where
+// off_pre_col lies
+struct frfft_tables {
+    uint32_t *pre_col, *pre_row, *post_col, *post_row;
+};
+frfft_tables frfft_build_tables(const fr_vtable *f, hipStream_t st, const frfft_plan &p, const frfft_params &pr, size_t n, char *tab) {
+    const frfft_tables tb = {(uint32_t *)tab, (uint32_t *)(tab + (p.off_pre_row - p.off_pre_col)),
+                             (uint32_t *)(tab + (p.off_post_col - p.off_pre_col)), (uint32_t *)(tab + (p.off_post_row - p.off_pre_col))};
+    if (pr.has_pre) {   // pre^c, c < n >> t_first, and pre^((n >> t_first) k), k < 2^t_first
+        f->powers(st, fr_pow_table(f, pr.pre, 0).data(), nullptr, 0, n >> p.t_first, tb.pre_col);
+        f->powers(st, fr_pow_table(f, pr.pre, p.log_n - p.t_first).data(), nullptr, 0, (size_t)1 << p.t_first, tb.pre_row);
+    }
+    if (pr.has_post) {   // post^q, q < n >> t_last, and scale post^((n >> t_last) k), k < 2^t_last
+        f->powers(st, fr_pow_table(f, pr.post, 0).data(), nullptr, 0, n >> p.t_last, tb.post_col);
+        f->powers(st, fr_pow_table(f, pr.post, p.log_n - p.t_last).data(), pr.scale.v, 0, (size_t)1 << p.t_last, tb.post_row);
+    }
+    return tb;
+}
+// pass k of the plan, log_s stages done before it; in and out are the caller's to fill
+fr_pass frfft_pass_of(const frfft_plan &p, const frfft_params &pr, const frfft_tables &tb, const fr_tw_entry *tw, int k, int log_s) {
+    const bool first = k == 0, last = k == p.passes - 1;
+    const int t = last ? p.t_last : p.tile;
+    fr_pass a = {};
+    a.tw = tw ? (const uint32_t *)tw->buf.p : nullptr;
+    a.pre_col = first && pr.has_pre ? tb.pre_col : nullptr;
+    a.pre_row = tb.pre_row;
+    a.post_col = last && pr.has_post ? tb.post_col : nullptr;
+    a.post_row = tb.post_row;
+    a.log_n = p.log_n;
+    a.log_r = t;
+    a.log_s = log_s;
+    a.log_c = std::min(FR_LDS_LOG2 - t, p.log_n - t);
+    a.in_plain = first && pr.plain && !pr.mont_in;
+    a.out_plain = last && pr.plain && !pr.mont_out;
+    a.has_scale = last && pr.has_scale && !pr.has_post;
+    memcpy(a.scale, pr.scale.v, sizeof(a.scale));
+    return a;
+}
+
 // The transform on device-resident vectors, n >= 1; ws: frfft_plan's workspace.  Marks the phases of a timed call.
 int frfft_run(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, const frfft_plan &p, const frfft_params &pr,
               const uint32_t *d_in, uint32_t *d_out, size_t n, char *ws) {
@@ -4294,16 +4335,7 @@ int frfft_run(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, const frfft_p
         const int rc = frfft_twiddles(ctx, f, st, n, pr, tw);
         if (rc) return rc;
     }
-    uint32_t *pre_col = (uint32_t *)(ws + p.off_pre_col), *pre_row = (uint32_t *)(ws + p.off_pre_row);
-    uint32_t *post_col = (uint32_t *)(ws + p.off_post_col), *post_row = (uint32_t *)(ws + p.off_post_row);
-    if (pr.has_pre) {   // pre^c, c < n >> t_first, and pre^((n >> t_first) k), k < 2^t_first
-        f->powers(st, fr_pow_table(f, pr.pre, 0).data(), nullptr, 0, n >> p.t_first, pre_col);
-        f->powers(st, fr_pow_table(f, pr.pre, p.log_n - p.t_first).data(), nullptr, 0, (size_t)1 << p.t_first, pre_row);
-    }
-    if (pr.has_post) {   // post^q, q < n >> t_last, and scale post^((n >> t_last) k), k < 2^t_last
-        f->powers(st, fr_pow_table(f, pr.post, 0).data(), nullptr, 0, n >> p.t_last, post_col);
-        f->powers(st, fr_pow_table(f, pr.post, p.log_n - p.t_last).data(), pr.scale.v, 0, (size_t)1 << p.t_last, post_row);
-    }
+    const frfft_tables tb = frfft_build_tables(f, st, p, pr, n, ws + p.off_pre_col);
     HIP_TRY(ctx, hipGetLastError());
     call_mark(ctx, st, 1);
     // pass k of P reads what pass k - 1 wrote; the last one writes d_out, and no pass reads and writes one vector --
@@ -4313,28 +4345,14 @@ int frfft_run(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, const frfft_p
     const uint32_t *src = d_in;
     int log_s = 0;
     for (int k = 0; k < p.passes; ++k) {
-        const bool first = k == 0, last = k == p.passes - 1;
-        const int t = last ? p.t_last : p.tile;
+        const bool last = k == p.passes - 1;
         uint32_t *dst = last ? d_out : ((p.passes - 1 - k) % 2 == 1 ? w1 : (third ? w2 : d_out));
-        fr_pass a = {};
+        fr_pass a = frfft_pass_of(p, pr, tb, tw, k, log_s);
         a.in = src;
         a.out = dst;
-        a.tw = tw ? (const uint32_t *)tw->buf.p : nullptr;
-        a.pre_col = first && pr.has_pre ? pre_col : nullptr;
-        a.pre_row = pre_row;
-        a.post_col = last && pr.has_post ? post_col : nullptr;
-        a.post_row = post_row;
-        a.log_n = p.log_n;
-        a.log_r = t;
-        a.log_s = log_s;
-        a.log_c = std::min(FR_LDS_LOG2 - t, p.log_n - t);
-        a.in_plain = first && pr.plain && !pr.mont_in;
-        a.out_plain = last && pr.plain && !pr.mont_out;
-        a.has_scale = last && pr.has_scale && !pr.has_post;
-        memcpy(a.scale, pr.scale.v, sizeof(a.scale));
         f->pass(st, a);
         src = dst;
-        log_s += t;
+        log_s += a.log_r;
     }
     HIP_TRY(ctx, hipGetLastError());
     if (tw) HIP_TRY(ctx, hipEventRecord(tw->ev, st));
@@ -4506,6 +4524,160 @@ int amdmsm_fr_muladd_device(amdmsm_ctx *ctx, int curve, size_t n, const void *d_
               plain ? 1 : 0, (uint32_t *)d_out);
     HIP_TRY(ctx, hipGetLastError());
     return AMDMSM_OK;
+}
+
+}  // extern "C"
+
+// ---- batched transforms: `batch` vectors of one size and one set of parameters through one chain of passes ----
+namespace {
+
+// The plan of one vector and what the batch adds: a set is `batch` packed vectors of n records; the workspace is one set,
+// one copy of the tables of powers, and the second set that an in-place call of an odd number of passes above one needs.
+struct frfft_batch_plan {
+    frfft_plan p;
+    size_t batch = 0, set = 0, off_tab = 0, off_w2 = 0, ws_plain = 0, ws_all = 0, groups = 0;
+    int log_v = 0, log_tiles = 0;   // vectors of a workgroup below 2^10 records, tiles of a vector from there on (log2)
+};
+void frfft_make_batch_plan(const frfft_plan &p, size_t n, size_t batch, frfft_batch_plan &b) {
+    b.p = p;
+    b.batch = batch;
+    b.set = align_up(std::max<size_t>(1, batch * n) * p.rec, 256);
+    b.off_tab = b.set;
+    b.off_w2 = b.set + (p.off_w2 - p.off_pre_col);
+    b.ws_plain = b.off_w2;
+    b.ws_all = b.off_w2 + b.set;
+    b.log_v = std::max(0, FR_LDS_LOG2 - p.log_n);
+    b.log_tiles = std::max(0, p.log_n - FR_LDS_LOG2);
+    b.groups = ((batch + ((size_t)1 << b.log_v) - 1) >> b.log_v) << b.log_tiles;
+}
+size_t frfft_batch_ws_bytes(const frfft_batch_plan &b, bool in_place) { return frfft_third(b.p, in_place) ? b.ws_all : b.ws_plain; }
+
+// What a batch adds to the rules of one vector of n records (`what`: "n" or "m"): the sizes, the strides (records), and for
+// device vectors the ranges [d, d + ((batch - 1) stride + n) rec), which may be one range with one stride or lie apart
+int fr_check_batch(amdmsm_ctx *ctx, const fr_vtable *f, const char *what, size_t n, size_t batch, size_t in_stride, size_t out_stride,
+                   const void *d_in, const void *d_out, bool device) {
+    const size_t rec = (size_t)f->words * 4;
+    if (n && batch > FR_FFT_MAX_N / n)
+        return fail(ctx, AMDMSM_ERR_TOO_LARGE, "batch = " + std::to_string(batch) + ": batch * " + what + " is at most 2^28 records");
+    if (!device || !batch || !n) return AMDMSM_OK;
+    const size_t strides[2] = {in_stride, out_stride};
+    const char *names[2] = {"in_stride", "out_stride"};
+    for (int k = 0; k < 2 && batch > 1; ++k) {
+        if (strides[k] > (SIZE_MAX / rec - n) / (batch - 1))
+            return fail(ctx, AMDMSM_ERR_TOO_LARGE, std::string(names[k]) + " = " + std::to_string(strides[k]) + ": batch * " + names[k] + " is beyond size_t");
+        if (strides[k] < n)
+            return fail(ctx, AMDMSM_ERR_BAD_ARG, std::string(names[k]) + " = " + std::to_string(strides[k]) + " < " + what + " = " + std::to_string(n) +
+                                                     ": the vectors of a batch do not overlap");
+    }
+    const int rc = fr_check_aligned(ctx, f, "d_values / d_out", {d_in, d_out});
+    if (rc) return rc;
+    return fr_check_apart(ctx, "d_values", d_in, ((batch - 1) * in_stride + n) * rec, "d_out", d_out, ((batch - 1) * out_stride + n) * rec,
+                          batch < 2 || in_stride == out_stride);
+}
+
+// frfft_run over a batch: vector v at d_in + v in_stride records and d_out + v out_stride records; the vectors of the
+// workspace's sets are packed.  ws: frfft_batch_plan's workspace
+int frfft_run_batch(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, const frfft_batch_plan &b, const frfft_params &pr,
+                    const uint32_t *d_in, size_t in_stride, uint32_t *d_out, size_t out_stride, size_t n, char *ws) {
+    const frfft_plan &p = b.p;
+    fr_tw_entry *tw = nullptr;
+    if (n > 1) {
+        const int rc = frfft_twiddles(ctx, f, st, n, pr, tw);
+        if (rc) return rc;
+    }
+    const frfft_tables tb = frfft_build_tables(f, st, p, pr, n, ws + b.off_tab);
+    HIP_TRY(ctx, hipGetLastError());
+    call_mark(ctx, st, 1);
+    // the order of the buffers is frfft_run's
+    uint32_t *w1 = (uint32_t *)ws, *w2 = (uint32_t *)(ws + b.off_w2);
+    const bool third = frfft_third(p, d_in == d_out);
+    const uint32_t *src = d_in;
+    size_t src_stride = in_stride;
+    int log_s = 0;
+    for (int k = 0; k < p.passes; ++k) {
+        const bool last = k == p.passes - 1;
+        uint32_t *dst = last ? d_out : ((p.passes - 1 - k) % 2 == 1 ? w1 : (third ? w2 : d_out));
+        fr_pass_batch a = {};
+        a.p = frfft_pass_of(p, pr, tb, tw, k, log_s);
+        a.p.in = src;
+        a.p.out = dst;
+        a.in_stride = src_stride;
+        a.out_stride = dst == d_out ? out_stride : n;
+        a.batch = (uint32_t)b.batch;
+        a.log_v = b.log_v;
+        a.log_tiles = b.log_tiles;
+        f->pass_batch(st, a);
+        src = dst;
+        src_stride = a.out_stride;
+        log_s += a.p.log_r;
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    if (tw) HIP_TRY(ctx, hipEventRecord(tw->ev, st));
+    return AMDMSM_OK;
+}
+
+}   // namespace
+
+extern "C" {
+
+int amdmsm_plan_fr_fft_batch(int curve, size_t n, size_t batch, int tile_log2, size_t out[8]) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return AMDMSM_ERR_UNSUPPORTED;
+    if (!out || (n & (n - 1))) return AMDMSM_ERR_BAD_ARG;
+    if (n > FR_FFT_MAX_N || (n && batch > FR_FFT_MAX_N / n)) return AMDMSM_ERR_TOO_LARGE;
+    frfft_batch_plan b;
+    if (frfft_make_plan(f, n, tile_log2, b.p)) return AMDMSM_ERR_BAD_ARG;
+    frfft_make_batch_plan(b.p, n, batch, b);
+    out[0] = (size_t)b.p.tile;
+    out[1] = (size_t)b.p.passes;
+    out[2] = (size_t)1 << b.log_v;
+    out[3] = n ? b.groups : 0;
+    out[4] = n && batch ? (size_t)b.p.passes : 0;
+    out[5] = batch * (n / 2 * (size_t)b.p.log_n);
+    out[6] = b.ws_plain;
+    out[7] = frfft_batch_ws_bytes(b, true);
+    return AMDMSM_OK;
+}
+
+int amdmsm_fr_fft_batch_device(amdmsm_ctx *ctx, int curve, const void *d_values, size_t n, size_t batch, size_t in_stride,
+                               size_t out_stride, const void *omega, const void *pre, const void *post, const void *scale, int tile_log2,
+                               const amdmsm_opts *opts, void *d_out) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
+    CHECK_OPTS(ctx, opts);
+    frfft_batch_plan b;
+    frfft_params pr;
+    int rc = frfft_check(ctx, f, d_values, n, omega, pre, post, scale, tile_log2, opts, d_out, b.p, pr, batch != 0);
+    if (!rc) rc = fr_check_batch(ctx, f, "n", n, batch, in_stride, out_stride, d_values, d_out, true);
+    if (rc) return rc;
+    FR_ENTER(ctx);
+    if (!n || !batch) return AMDMSM_OK;
+    frfft_make_batch_plan(b.p, n, batch, b);
+    hipStream_t st = stream_of(ctx, opts);
+    return fr_call(ctx, st, 0, frfft_batch_ws_bytes(b, d_values == d_out), {}, {}, [&](char *, char *ws) {
+        return frfft_run_batch(ctx, f, st, b, pr, (const uint32_t *)d_values, in_stride, (uint32_t *)d_out, out_stride, n, ws);
+    });
+}
+
+int amdmsm_fr_fft_batch(amdmsm_ctx *ctx, int curve, const void *values, size_t n, size_t batch, const void *omega, const void *pre,
+                        const void *post, const void *scale, int tile_log2, const amdmsm_opts *opts, void *out) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
+    CHECK_OPTS(ctx, opts);
+    frfft_batch_plan b;
+    frfft_params pr;
+    int rc = frfft_check(ctx, f, values, n, omega, pre, post, scale, tile_log2, opts, out, b.p, pr, batch != 0);
+    if (!rc) rc = fr_check_batch(ctx, f, "n", n, batch, n, n, values, out, false);
+    if (rc) return rc;
+    FR_ENTER(ctx);
+    if (!n || !batch) return AMDMSM_OK;
+    frfft_make_batch_plan(b.p, n, batch, b);
+    hipStream_t st = ctx->stream;
+    // one staged set of packed vectors; the transforms run in place on it
+    const size_t bytes = batch * n * b.p.rec;
+    return fr_call(ctx, st, b.set, frfft_batch_ws_bytes(b, true), {{values, 0, bytes}}, {{out, 0, bytes}}, [&](char *set, char *ws) {
+        return frfft_run_batch(ctx, f, st, b, pr, (const uint32_t *)set, n, (uint32_t *)set, n, n, ws);
+    });
 }
 
 }  // extern "C"
@@ -5164,7 +5336,7 @@ struct frdom_params {
 // The argument rules of both transform entries; nothing is launched or written and the context is not looked at before
 // they hold.  device: the vectors are HBM addresses
 int frdom_check(amdmsm_ctx *ctx, const fr_vtable *f, const void *values, size_t m, int flags, const void *coset, int tile_log2,
-                const amdmsm_opts *opts, const void *out, bool device, frdom_plan &p, frdom_params &q) {
+                const amdmsm_opts *opts, const void *out, bool device, frdom_plan &p, frdom_params &q, bool need_vectors = true) {
     frdom d;
     std::string why;
     int rc = frdom_exact(f, m, d, why);
@@ -5173,8 +5345,8 @@ int frdom_check(amdmsm_ctx *ctx, const fr_vtable *f, const void *values, size_t 
     if (frdom_make_plan(f, d, tile_log2, p))
         return fail(ctx, AMDMSM_ERR_BAD_ARG, "tile_log2 = " + std::to_string(tile_log2) + ": 0 or " + std::to_string(FR_TILE_MIN) +
                                                  " .. " + std::to_string(FR_TILE_MAX));
-    if (!values) return fail(ctx, AMDMSM_ERR_BAD_ARG, "values: null pointer");
-    if (!out) return fail(ctx, AMDMSM_ERR_BAD_ARG, "output: null pointer");
+    if (need_vectors && !values) return fail(ctx, AMDMSM_ERR_BAD_ARG, "values: null pointer");
+    if (need_vectors && !out) return fail(ctx, AMDMSM_ERR_BAD_ARG, "output: null pointer");
     if (device) {
         rc = fr_check_aligned(ctx, f, "d_values / d_out", {values, out});
         if (!rc) rc = fr_check_apart(ctx, "d_values", values, m * p.rec, "d_out", out, m * p.rec);
@@ -5696,6 +5868,314 @@ int amdmsm_fr_lincomb_device(amdmsm_ctx *ctx, int curve, size_t n, int k, const 
         f->lincomb(st, n, k, (const uint32_t *const *)d_v, s, (uint32_t *)d_out);
         HIP_TRY(ctx, hipGetLastError());
         return AMDMSM_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---- batched transforms over a domain, and the R1CS-to-QAP witness map as one call -----------------------------
+namespace {
+
+// A batch over one domain.  Basic: the batched passes.  Step: the radix-2 transforms of B and of S records go through the
+// batched passes -- vector v's B records at v stride, its S records B records further on -- and the fold, merge and
+// combine sweeps run vector by vector with the kernels of one vector, in stream order on one set of partial sums.
+// Workspace: the passes' (in place, the larger of the two batches), then the sweeps' regions of frdom_plan, `shift`
+// bytes further on than one vector has them.
+struct frdom_batch_plan {
+    frdom_plan p;
+    frfft_batch_plan bb, bs;
+    size_t batch = 0, shift = 0, ws_bytes = 0;
+};
+void frdom_make_batch_plan(const frdom_plan &p, size_t batch, frdom_batch_plan &b) {
+    b.p = p;
+    b.batch = batch;
+    frfft_make_batch_plan(p.pb, p.d.B, batch, b.bb);
+    if (!p.d.step) {
+        b.ws_bytes = frfft_batch_ws_bytes(b.bb, true);
+        return;
+    }
+    frfft_make_batch_plan(p.ps, p.d.S, batch, b.bs);
+    b.shift = std::max(frfft_batch_ws_bytes(b.bb, true), frfft_batch_ws_bytes(b.bs, true)) - p.off_pa;
+    b.ws_bytes = p.ws_bytes + b.shift;
+}
+
+// frdom_run over a batch, batch >= 1: vector v at d_in + v in_stride records and d_out + v out_stride records
+int frdom_run_batch(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, const frdom_batch_plan &b, const frdom_params &q,
+                    const uint32_t *d_in, size_t in_stride, uint32_t *d_out, size_t out_stride, char *ws) {
+    const frdom_plan &p = b.p;
+    const frdom &d = p.d;
+    if (!d.step) return frfft_run_batch(ctx, f, st, b.bb, q.prb, d_in, in_stride, d_out, out_stride, d.m, ws);
+    const size_t nw = (size_t)f->words;
+    fr_tw_entry *tw = nullptr, *pre = nullptr;
+    frfft_params pw;
+    pw.omega = q.w;
+    int rc = frfft_twiddles(ctx, f, st, 2 * d.B, pw, tw);
+    if (!rc && d.B > 1) rc = frfft_twiddles(ctx, f, st, d.B, q.prb, pre);
+    if (!rc && d.S > 1) rc = frfft_twiddles(ctx, f, st, d.S, q.prs, pre);
+    if (rc) return rc;
+    char *sweeps = ws + b.shift;   // where the sweeps find frdom_plan's regions
+    uint32_t *g_lo = nullptr, *g_hi = nullptr;
+    if (q.has_g) {
+        g_lo = (uint32_t *)(sweeps + p.off_glo);
+        g_hi = (uint32_t *)(sweeps + p.off_ghi);
+        f->powers(st, fr_pow_table(f, q.g, 0).data(), nullptr, 0, (size_t)1 << FRD_LO_LOG2, g_lo);
+        f->powers(st, fr_pow_table(f, q.g, FRD_LO_LOG2).data(), nullptr, 0, (d.m >> FRD_LO_LOG2) + 1, g_hi);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    call_mark(ctx, st, 1);
+    frd_sweep a = {};
+    a.tw = (const uint32_t *)tw->buf.p;
+    a.g_lo = g_lo;
+    a.g_hi = g_hi;
+    a.plain = q.plain ? 1 : 0;
+    uint32_t *hi = d_out + d.B * nw;
+    if (!q.inverse) {
+        a.mode = FRD_FOLD;
+        a.store = (d_in != d_out || q.plain || q.has_g) ? 1 : 0;
+        for (size_t v = 0; v < b.batch; ++v) {
+            a.in = d_in + v * in_stride * nw;
+            a.out = d_out + v * out_stride * nw;
+            frdom_sweeps(f, st, p, a, hi + v * out_stride * nw, sweeps);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+        rc = frfft_run_batch(ctx, f, st, b.bb, q.prb, d_out, out_stride, d_out, out_stride, d.B, ws);
+        if (!rc) rc = frfft_run_batch(ctx, f, st, b.bs, q.prs, hi, out_stride, hi, out_stride, d.S, ws);
+        if (rc) return rc;
+    } else {
+        rc = frfft_run_batch(ctx, f, st, b.bb, q.prb, d_in, in_stride, d_out, out_stride, d.B, ws);
+        if (!rc) rc = frfft_run_batch(ctx, f, st, b.bs, q.prs, d_in + d.B * nw, in_stride, hi, out_stride, d.S, ws);
+        if (rc) return rc;
+        uint32_t *sums = (uint32_t *)(sweeps + p.off_sums);
+        a.mode = FRD_MERGE;
+        a.store = (q.plain || q.has_g) ? 1 : 0;
+        frd_combine c = {};
+        c.sums = sums;
+        c.tw = a.tw;
+        c.g_lo = g_lo;
+        c.g_hi = g_hi;
+        c.log_b = d.log_b;
+        c.log_s = d.log_s;
+        c.plain = a.plain;
+        memcpy(c.half, q.half.v, sizeof(c.half));
+        for (size_t v = 0; v < b.batch; ++v) {
+            a.in = a.out = c.out = d_out + v * out_stride * nw;
+            frdom_sweeps(f, st, p, a, sums, sweeps);
+            f->domain_combine(st, c);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(tw->ev, st));
+    return AMDMSM_OK;
+}
+
+// What a witness map runs with.  The workspace: the three vectors aA, aB, aC of m records, packed; the partial sums of an
+// apply; the batch transform's workspace, which serves the single inverse coset transform too; the division's.
+struct frqap_call {
+    frdom_plan dp;
+    frdom_batch_plan bp;
+    frdom_params inv, cos, icos;   // the inverse transform, the coset transform, the inverse coset transform
+    frdiv_call div;
+    fr_matrix *mat[3] = {};
+    bool plain = false, blind = false;
+    fr_rec d1, d2;                 // Montgomery
+    fr_terms terms = {};           // h[m], and with blinding d1 d2 Z - d3
+    size_t rec = 0, off_part = 0, off_tr = 0, off_div = 0, ws_bytes = 0;
+};
+
+// The rules that need no context: the domain, the vectors, the blinding.  z and h are HBM addresses with `device`.
+int frqap_check(amdmsm_ctx *ctx, const fr_vtable *f, const void *z, size_t n_z, size_t m, const void *blind, const amdmsm_opts *opts,
+                const void *h, bool device, frqap_call &c) {
+    c.rec = (size_t)f->words * 4;
+    c.plain = opts && opts->scalars_plain;
+    c.blind = blind != nullptr;
+    // the coset of the quotient in the caller's form; the three transforms' own rules give the domain's refusals
+    uint32_t g[FR_MAX_WORDS] = {};
+    fr_write(f, g, fr_from_words(f, f->generator), c.plain);
+    int rc = frdom_check(ctx, f, nullptr, m, AMDMSM_DOMAIN_INVERSE, nullptr, 0, opts, nullptr, false, c.dp, c.inv, false);
+    if (rc) return rc;
+    if (n_z > FRM_MAX_DIM) return fail(ctx, AMDMSM_ERR_TOO_LARGE, "n_z = " + std::to_string(n_z) + ": at most 2^28 records");
+    if (n_z && !z) return fail(ctx, AMDMSM_ERR_BAD_ARG, device ? "d_z: null pointer" : "z: null pointer");
+    if (!h) return fail(ctx, AMDMSM_ERR_BAD_ARG, device ? "d_h: null pointer" : "h: null pointer");
+    if (device) {
+        rc = fr_check_aligned(ctx, f, "d_z / d_h", {z, h});
+        if (!rc) rc = fr_check_apart(ctx, "d_z", z, n_z * c.rec, "d_h", h, (m + 1) * c.rec, false);
+        if (rc) return rc;
+    }
+    fr_rec d3;
+    if (c.blind) {
+        for (int k = 0; k < 3; ++k)
+            if (!fr_below_modulus(f, (const uint32_t *)((const char *)blind + k * c.rec)))
+                return fail(ctx, AMDMSM_ERR_BAD_ARG, "blind[" + std::to_string(k) + "]: not below r");
+        c.d1 = fr_read(f, blind, c.plain);
+        c.d2 = fr_read(f, (const char *)blind + c.rec, c.plain);
+        d3 = fr_read(f, (const char *)blind + 2 * c.rec, c.plain);
+    }
+    rc = frdom_check(ctx, f, nullptr, m, 0, g, 0, opts, nullptr, false, c.dp, c.cos, false);
+    if (!rc) rc = frdom_check(ctx, f, nullptr, m, AMDMSM_DOMAIN_INVERSE, g, 0, opts, nullptr, false, c.dp, c.icos, false);
+    if (!rc) rc = frdiv_check(ctx, f, m, g, g, opts, g, false, c.div);   // no vectors yet: any non-null address
+    if (rc) return rc;
+    frdom_make_batch_plan(c.dp, 3, c.bp);
+    // h[m] = d1 d2 (0 without blinding), stored; with blinding the other terms of d1 d2 Z, and -d3 with the constant one
+    c.terms.idx[0] = m;
+    c.terms.count = 1;
+    c.terms.set = 1;
+    if (c.blind) {
+        uint32_t coef[FR_TERMS_MAX][FR_MAX_WORDS] = {};
+        std::vector<uint32_t> packed((size_t)FR_TERMS_MAX * f->words);
+        if (amdmsm_fr_domain_z_terms(f->curve, m, 0, c.terms.idx, packed.data(), &c.terms.count)) return AMDMSM_ERR_BAD_ARG;
+        const fr_rec dd = fr_mul(f, c.d1, c.d2);
+        for (int k = 0; k < c.terms.count; ++k) {
+            fr_rec t = fr_mul(f, dd, fr_from_words(f, &packed[(size_t)k * f->words]));
+            if (c.terms.idx[k] == 0) t = fr_sub_host(f, t, d3);
+            fr_write(f, coef[k], t, c.plain);
+        }
+        memcpy(c.terms.c, coef, sizeof(coef));
+    }
+    return AMDMSM_OK;
+}
+
+// The rules of the three handles, with the context held, and the workspace
+int frqap_handles(amdmsm_ctx *ctx, const fr_vtable *f, const uint64_t mats[3], size_t n_z, size_t m, frqap_call &c) {
+    const char *names[3] = {"mat_a", "mat_b", "mat_c"};
+    size_t part = 256;
+    for (int j = 0; j < 3; ++j) {
+        fr_matrix *mt = frm_find(ctx, mats[j]);
+        if (!mt)
+            return fail(ctx, AMDMSM_ERR_BAD_ARG, std::string(names[j]) + ": matrix handle " + std::to_string(mats[j]) + ": not a live handle of this context");
+        if (mt->curve != f->curve) return fail(ctx, AMDMSM_ERR_BAD_ARG, std::string(names[j]) + ": a matrix of another curve");
+        if (mt->n_rows > m)
+            return fail(ctx, AMDMSM_ERR_BAD_ARG, std::string(names[j]) + ": n_rows = " + std::to_string(mt->n_rows) + " > m = " + std::to_string(m));
+        if (n_z < mt->n_cols)
+            return fail(ctx, AMDMSM_ERR_BAD_ARG, std::string(names[j]) + ": n_z = " + std::to_string(n_z) + " < n_cols = " + std::to_string(mt->n_cols));
+        c.mat[j] = mt;
+        part = std::max(part, frm_ws_bytes(f, mt));
+    }
+    c.off_part = align_up(3 * m * c.rec, 256);
+    c.off_tr = c.off_part + part;
+    c.off_div = c.off_tr + c.bp.ws_bytes;
+    c.ws_bytes = c.off_div + std::max<size_t>(c.div.ws_bytes, 256);
+    return AMDMSM_OK;
+}
+
+// every kernel of the map, in stream order; ws: frqap_call's workspace
+int frqap_run(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, const frqap_call &c, const uint32_t *d_z, uint32_t *d_h, char *ws) {
+    const size_t m = c.dp.d.m, nw = (size_t)f->words;
+    uint32_t *v[3] = {(uint32_t *)ws, (uint32_t *)ws + m * nw, (uint32_t *)ws + 2 * m * nw};
+    char *tr = ws + c.off_tr;
+    int rc = AMDMSM_OK;
+    for (int j = 0; j < 3 && !rc; ++j) rc = frm_run(ctx, f, st, c.mat[j], d_z, v[j], m, (uint32_t *)(ws + c.off_part));
+    if (rc) return rc;
+    call_mark(ctx, st, 0);   // the tables of a transform belong to phase 0, here and below
+    rc = frdom_run_batch(ctx, f, st, c.bp, c.inv, v[0], m, v[0], m, tr);
+    if (rc) return rc;
+    const fr_rec one = fr_one(f);
+    uint32_t s[2 * FR_MAX_WORDS] = {};
+    if (c.blind) {   // d2 A + d1 B, while A and B are coefficients
+        memcpy(s, c.d2.v, nw * 4);
+        memcpy(s + nw, c.d1.v, nw * 4);
+        const uint32_t *ab[2] = {v[0], v[1]};
+        f->lincomb(st, m, 2, ab, s, d_h);
+    }
+    call_mark(ctx, st, 0);
+    rc = frdom_run_batch(ctx, f, st, c.bp, c.cos, v[0], m, v[0], m, tr);
+    if (rc) return rc;
+    f->muladd(st, m, v[0], v[1], v[2], nullptr, c.plain ? 1 : 0, v[0]);
+    HIP_TRY(ctx, hipGetLastError());
+    call_mark(ctx, st, 0);
+    rc = frdiv_run(ctx, f, st, c.div, v[0], v[0], ws + c.off_div);
+    if (rc) return rc;
+    call_mark(ctx, st, 0);
+    rc = frdom_run(ctx, f, st, c.dp, c.icos, v[0], c.blind ? v[0] : d_h, tr);
+    if (rc) return rc;
+    if (c.blind) {
+        memcpy(s, one.v, nw * 4);
+        memcpy(s + nw, one.v, nw * 4);
+        const uint32_t *qh[2] = {v[0], d_h};
+        f->lincomb(st, m, 2, qh, s, d_h);
+    }
+    f->add_terms(st, c.terms, d_h);
+    HIP_TRY(ctx, hipGetLastError());
+    return AMDMSM_OK;
+}
+
+}   // namespace
+
+extern "C" {
+
+int amdmsm_fr_domain_fft_batch_device(amdmsm_ctx *ctx, int curve, const void *d_values, size_t m, size_t batch, size_t in_stride,
+                                      size_t out_stride, int flags, const void *coset, int tile_log2, const amdmsm_opts *opts,
+                                      void *d_out) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
+    CHECK_OPTS(ctx, opts);
+    frdom_batch_plan b;
+    frdom_params q;
+    // the batch's own alignment and overlap rules stand in for those of one vector
+    int rc = frdom_check(ctx, f, d_values, m, flags, coset, tile_log2, opts, d_out, false, b.p, q, batch != 0);
+    if (!rc) rc = fr_check_batch(ctx, f, "m", m, batch, in_stride, out_stride, d_values, d_out, true);
+    if (rc) return rc;
+    FR_ENTER(ctx);
+    if (!batch) return AMDMSM_OK;
+    frdom_make_batch_plan(b.p, batch, b);
+    hipStream_t st = stream_of(ctx, opts);
+    return fr_call(ctx, st, 0, b.ws_bytes, {}, {}, [&](char *, char *ws) {
+        return frdom_run_batch(ctx, f, st, b, q, (const uint32_t *)d_values, in_stride, (uint32_t *)d_out, out_stride, ws);
+    });
+}
+
+int amdmsm_plan_fr_qap_witness_map(int curve, size_t m, size_t out[6]) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return AMDMSM_ERR_UNSUPPORTED;
+    if (!out) return AMDMSM_ERR_BAD_ARG;
+    frqap_call c;
+    const int rc = frqap_check(nullptr, f, nullptr, 0, m, nullptr, nullptr, out, false, c);
+    if (rc) return rc;
+    const frdom &d = c.dp.d;
+    out[0] = d.step ? AMDMSM_DOMAIN_STEP_RADIX2 : AMDMSM_DOMAIN_BASIC_RADIX2;
+    out[1] = d.m;
+    out[2] = d.B;
+    out[3] = d.S;
+    // without the partial sums of the applies, which belong to the handles
+    out[4] = align_up(3 * m * c.rec, 256) + c.bp.ws_bytes + std::max<size_t>(c.div.ws_bytes, 256);
+    out[5] = 2 * ((size_t)c.bp.bb.p.passes + (d.step ? (size_t)c.bp.bs.p.passes : 0));
+    return AMDMSM_OK;
+}
+
+int amdmsm_fr_qap_witness_map_device(amdmsm_ctx *ctx, int curve, uint64_t mat_a, uint64_t mat_b, uint64_t mat_c, const void *d_z,
+                                     size_t n_z, size_t m, const void *blind, const amdmsm_opts *opts, void *d_h) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
+    CHECK_OPTS(ctx, opts);
+    frqap_call c;
+    int rc = frqap_check(ctx, f, d_z, n_z, m, blind, opts, d_h, true, c);
+    if (rc) return rc;
+    FR_ENTER(ctx);
+    const uint64_t mats[3] = {mat_a, mat_b, mat_c};
+    rc = frqap_handles(ctx, f, mats, n_z, m, c);
+    if (rc) return rc;
+    hipStream_t st = stream_of(ctx, opts);
+    return fr_call(ctx, st, 0, c.ws_bytes, {}, {}, [&](char *, char *ws) {
+        return frqap_run(ctx, f, st, c, (const uint32_t *)d_z, (uint32_t *)d_h, ws);
+    });
+}
+
+int amdmsm_fr_qap_witness_map(amdmsm_ctx *ctx, int curve, uint64_t mat_a, uint64_t mat_b, uint64_t mat_c, const void *z, size_t n_z,
+                              size_t m, const void *blind, const amdmsm_opts *opts, void *h) {
+    const fr_vtable *f = find_frvt(curve);
+    if (!f) return fail(ctx, AMDMSM_ERR_UNSUPPORTED, "unknown curve");
+    CHECK_OPTS(ctx, opts);
+    frqap_call c;
+    int rc = frqap_check(ctx, f, z, n_z, m, blind, opts, h, false, c);
+    if (rc) return rc;
+    FR_ENTER(ctx);
+    const uint64_t mats[3] = {mat_a, mat_b, mat_c};
+    rc = frqap_handles(ctx, f, mats, n_z, m, c);
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    // staged: z and h, in that order
+    const size_t z_bytes = align_up((n_z ? n_z : 1) * c.rec, 256), h_bytes = align_up((m + 1) * c.rec, 256);
+    return fr_call(ctx, st, z_bytes + h_bytes, c.ws_bytes, {{z, 0, n_z * c.rec}}, {{h, z_bytes, (m + 1) * c.rec}}, [&](char *vecs, char *ws) {
+        return frqap_run(ctx, f, st, c, (const uint32_t *)vecs, (uint32_t *)(vecs + z_bytes), ws);
     });
 }
 

@@ -226,6 +226,110 @@ __global__ void __launch_bounds__(TPB) k_fr_lincomb(size_t n, int k, const fr_li
 // ---- step radix-2 domains: the fold in front of the passes, the merge behind them, the division by Z ----------------
 #include "fr_domain.inc"
 
+// ---- one global pass over a batch of vectors ------------------------------------------------------------------------
+// k_fr_fft_pass for `batch` vectors of n records that share twiddles and tables; its own copy of the body, so that the
+// single-vector kernel stays as the compiler had it (as k_sort_digits_sel).  The LDS tile always holds
+// 2^10 records, 2^le of them (le = log_r + log_c) of one vector:
+//   n >= 2^10   le = 10.  Workgroup g serves tile g mod 2^log_tiles of vector g >> log_tiles.
+//   n <  2^10   le = log_n, c0 = 0.  Workgroup g holds the V = 2^log_v = 2^10 / n vectors g V .. g V + V - 1, vector vl of
+//               them in the records vl 2^le .. of the tile; the last workgroup may hold fewer.
+// Record e of the tile belongs to vector v0 + (e >> le) and is record e mod 2^le of that vector's tile in k_fr_fft_pass;
+// the stage loop and the store order are that kernel's on the low le bits.  A butterfly pairs two records of one vector,
+// so the lanes of a vector >= batch skip loads, butterflies and stores alike and still reach every barrier.  Every
+// index comes from log_n, the strides, batch and blockIdx: a lane touches records [v stride, v stride + n) of a vector
+// v < batch, and twiddle indices stay below n / 2 as in k_fr_fft_pass.
+__global__ void __launch_bounds__(TPB) k_fr_fft_pass_batch(const fr_pass_batch b) {
+    __shared__ uint2 tile[N / 2][E];
+    const uint32_t tid = threadIdx.x;
+    const int ln = b.p.log_n, t = b.p.log_r, ls = b.p.log_s, lc = b.p.log_c;
+    const int lm = ln - ls - t, le = t + lc;
+    const uint32_t C = 1u << lc, R = 1u << t, Em = (1u << le) - 1;
+    const uint32_t c0 = (blockIdx.x & ((1u << b.log_tiles) - 1)) << lc;
+    const uint32_t v0 = (blockIdx.x >> b.log_tiles) << b.log_v;
+
+    for (uint32_t e = tid; e < E; e += TPB) {
+        const uint32_t vec = v0 + (e >> le), ee = e & Em;
+        if (vec >= b.batch) continue;
+        const uint32_t k = ee >> lc, c = c0 + (ee & (C - 1));
+        F v;
+        rec_load(v, b.p.in, (size_t)vec * b.in_stride + c + ((size_t)k << (ln - t)));
+        if (b.p.in_plain) fp_to_mont(v, v);
+        if (b.p.pre_col) {
+            F f;
+            rec_load(f, b.p.pre_row, k);
+            fp_mul(v, v, f);
+            rec_load(f, b.p.pre_col, c);
+            fp_mul(v, v, f);
+        }
+        tile_put(tile, e, v);
+    }
+    __syncthreads();
+
+    for (int j = 0; j < t; ++j) {
+        const int lh = t - 1 - j;
+        const uint32_t h = 1u << lh;
+        for (uint32_t bf = tid; bf < E / 2; bf += TPB) {
+            const uint32_t vl = bf >> (le - 1), bb = bf & (Em >> 1);
+            if (v0 + vl < b.batch) {
+                const uint32_t cc = bb & (C - 1), x = bb >> lc, i = x & (h - 1), blk = x >> lh;
+                const uint32_t lo = (vl << le) | ((((blk << (lh + 1)) + i) << lc) | cc), hi = lo + (h << lc);
+                const uint32_t p = (c0 + cc) >> ls;
+                const size_t tw = ((size_t)p + ((size_t)i << lm)) << (ls + j);
+                F u, v, w, d;
+                rec_load(w, b.p.tw, tw);
+                tile_get(u, tile, lo);
+                tile_get(v, tile, hi);
+                fp_sub(d, u, v);
+                fp_add(u, u, v);
+                fp_mul(d, d, w);
+                tile_put(tile, lo, u);
+                tile_put(tile, hi, d);
+            }
+        }
+        __syncthreads();
+    }
+
+    const int lsp = ls < lc ? ls : lc;
+    F scale;
+    rec_copy(scale, b.p.scale);
+    for (uint32_t e = tid; e < E; e += TPB) {
+        const uint32_t vl = e >> le, vec = v0 + vl, ee = e & Em;
+        if (vec >= b.batch) continue;
+        const uint32_t ql = ee & ((1u << lsp) - 1), k2 = (ee >> lsp) & (R - 1), pl = ee >> (lsp + t);
+        const uint32_t cc = (pl << lsp) + ql, c = c0 + cc;
+        const uint32_t q = c & ((1u << ls) - 1), p = c >> ls;
+        const uint32_t k = t ? __brev(k2) >> (32 - t) : 0u;
+        F v;
+        tile_get(v, tile, (vl << le) | (k << lc) | cc);
+        if (b.p.post_col) {   // last pass: p = 0, the output index is q + s k2
+            F f;
+            rec_load(f, b.p.post_row, k2);
+            fp_mul(v, v, f);
+            rec_load(f, b.p.post_col, q);
+            fp_mul(v, v, f);
+        } else if (b.p.has_scale) {
+            fp_mul(v, v, scale);
+        }
+        if (b.p.out_plain) fp_from_mont(v, v);
+        rec_store(b.p.out, (size_t)vec * b.out_stride + q + ((((size_t)p << t) + k2) << ls), v);
+    }
+}
+
+// ---- h[idx[k]] += c[k]: the few terms of a constant times Z, added to a coefficient vector -----------------------------
+__global__ void __launch_bounds__(64) k_fr_add_terms(const fr_terms a, uint32_t* h) {
+    const int k = (int)threadIdx.x;
+    if (k >= a.count) return;
+    F x, c;
+    rec_copy(c, a.c[k]);
+    if (k == 0 && a.set) {
+        x = c;
+    } else {
+        rec_load(x, h, a.idx[k]);
+        fp_add(x, x, c);
+    }
+    rec_store(h, a.idx[k], x);
+}
+
 // ---- launchers ------------------------------------------------------------------------------------------------------
 void l_pass(hipStream_t st, const fr_pass& a) {
     const unsigned tiles = 1u << (a.log_n - a.log_r - a.log_c);
@@ -264,6 +368,17 @@ void l_lincomb(hipStream_t st, size_t n, int k, const uint32_t* const* d_v, cons
     hipLaunchKernelGGL(k_fr_lincomb, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, st, n, k, a, d_out);
 }
 
+// ceil(batch / V) workgroups of whole vectors below 2^10 records, batch * n / 2^10 tiles from there on: a grid of at most
+// 2^18 workgroups in x (batch * n <= 2^28)
+void l_pass_batch(hipStream_t st, const fr_pass_batch& a) {
+    const unsigned groups = ((a.batch + (1u << a.log_v) - 1) >> a.log_v) << a.log_tiles;
+    hipLaunchKernelGGL(k_fr_fft_pass_batch, dim3(groups), dim3(TPB), 0, st, a);
+}
+
+void l_add_terms(hipStream_t st, const fr_terms& a, uint32_t* d_h) {
+    if (a.count) hipLaunchKernelGGL(k_fr_add_terms, dim3(1), dim3(64), 0, st, a, d_h);
+}
+
 const fr_vtable g_frvt = {
     .curve = AMDMSM_FR_CURVE,
     .words = N,
@@ -288,6 +403,8 @@ const fr_vtable g_frvt = {
     .domain_den = l_domain_den,
     .domain_divide = l_domain_divide,
     .domain_lagrange = l_domain_lagrange,
+    .pass_batch = l_pass_batch,
+    .add_terms = l_add_terms,
 };
 
 }  // namespace

@@ -32,6 +32,26 @@ struct fr_pass {
     uint32_t scale[FR_MAX_WORDS];
 };
 
+// the same pass over `batch` vectors of one size (k_fr_fft_pass_batch): vector v starts at record v * in_stride of
+// p.in and v * out_stride of p.out; the twiddles and the pre / post tables serve every vector.  A workgroup's tile is
+// always 2^FR_LDS_LOG2 records: from n = 2^FR_LDS_LOG2 on it is one of the 2^log_tiles tiles of one vector (log_v = 0),
+// below that the whole of 2^log_v = 2^FR_LDS_LOG2 / n vectors (log_tiles = 0), the vector index in the tile's upper bits
+struct fr_pass_batch {
+    fr_pass p;
+    size_t in_stride, out_stride;   // records
+    uint32_t batch;
+    int log_v, log_tiles;
+};
+
+// terms added to single records of a vector (k_fr_add_terms): h[idx[k]] += c[k], k < count; with `set`, term 0 is
+// stored instead -- the record behind a vector that nothing has written yet.  The indices differ from one another
+constexpr int FR_TERMS_MAX = 4;
+struct fr_terms {
+    size_t idx[FR_TERMS_MAX];
+    uint32_t c[FR_TERMS_MAX][FR_MAX_WORDS];   // in the form of the vector's records
+    int count, set;
+};
+
 // one apply of a resident sparse matrix (k_frm_apply, k_frm_combine; fr_matrix_layout.h has the arrays' meaning)
 struct frm_args {
     const uint32_t* words;
@@ -139,6 +159,10 @@ struct fr_vtable {
                           uint32_t* d_out);
     // record j of the domain's Lagrange vector at t, as its denominator or, on a point of the domain, as it is
     void (*domain_lagrange)(hipStream_t, const frd_lagrange&);
+    // one pass over a batch of vectors of one size; batch >= 1
+    void (*pass_batch)(hipStream_t, const fr_pass_batch&);
+    // d_h[idx[k]] += c[k] (term 0 stored with `set`): the Z terms behind a quotient
+    void (*add_terms)(hipStream_t, const fr_terms&, uint32_t* d_h);
 };
 
 const fr_vtable* frvt_alt_bn128() __attribute__((weak));

@@ -79,6 +79,8 @@ EXPORTED_SYMBOLS = [
     "amdmsm_fr_matrix_load_transposed", "amdmsm_plan_fr_matrix_transposed", "amdmsm_fr_lincomb_device",
     "amdmsm_batch_exp_device", "amdmsm_disk_encode_device", "amdmsm_write_points_stream", "amdmsm_write_points_file",
     "amdmsm_plan_write_points",
+    "amdmsm_fr_fft_batch", "amdmsm_fr_fft_batch_device", "amdmsm_plan_fr_fft_batch", "amdmsm_fr_domain_fft_batch_device",
+    "amdmsm_fr_qap_witness_map", "amdmsm_fr_qap_witness_map_device", "amdmsm_plan_fr_qap_witness_map",
 ]
 SEG_SHARED_BASES = 1            # include/amdmsm.h AMDMSM_SEG_SHARED_BASES
 SEG_LONG_NEVER = 2 ** 64 - 1    # long_from = SIZE_MAX: no segment takes the single-MSM route
@@ -300,6 +302,29 @@ def plan_fr_fft(curve, n, tile_log2=0):
         raise AmdMsmError(f"amdmsm_plan_fr_fft: {rc}")
     return {"tile_log2": out[0], "tile_min": out[1], "tile_max": out[2], "passes": out[3], "butterflies": out[4],
             "workspace_bytes": out[5]}
+
+
+def plan_fr_fft_batch(curve, n, batch, tile_log2=0):
+    """What ``Engine.fr_fft_batch`` runs for ``batch`` vectors of ``n`` scalars (``amdmsm_plan_fr_fft_batch``, read-only):
+    the tile, the global passes, the vectors one workgroup holds, the workgroups and launches of the pass kernel, the
+    butterflies, and the workspace bytes of an out-of-place and of an in-place device call."""
+    out = (ctypes.c_size_t * 8)()
+    rc = load_library().amdmsm_plan_fr_fft_batch(curve, ctypes.c_size_t(n), ctypes.c_size_t(batch), int(tile_log2), out)
+    if rc:
+        raise AmdMsmError(f"amdmsm_plan_fr_fft_batch: {rc}")
+    return {"tile_log2": out[0], "passes": out[1], "vectors_per_workgroup": out[2], "workgroups": out[3], "launches": out[4],
+            "butterflies": out[5], "workspace_bytes": out[6], "workspace_bytes_in_place": out[7]}
+
+
+def plan_fr_qap_witness_map(curve, m):
+    """What ``Engine.qap_witness_map`` runs on the domain of ``m`` points (``amdmsm_plan_fr_qap_witness_map``, read-only):
+    the domain's kind, m, B, S, the workspace bytes (without the applies' partial sums) and the launches of the batched
+    pass kernel."""
+    out = (ctypes.c_size_t * 6)()
+    rc = load_library().amdmsm_plan_fr_qap_witness_map(curve, ctypes.c_size_t(m), out)
+    if rc:
+        raise _domain_error("amdmsm_plan_fr_qap_witness_map", rc)
+    return {"kind": out[0], "m": out[1], "B": out[2], "S": out[3], "workspace_bytes": out[4], "batch_pass_launches": out[5]}
 
 
 def fr_root_of_unity(curve, n):
@@ -1368,6 +1393,84 @@ class Engine:
         self._check(self.lib.amdmsm_fr_domain_fft_device(self.h, curve, _opt_dev(d_values), ctypes.c_size_t(m),
                                                          DOMAIN_INVERSE if inverse else 0, _opt_ptr(g), int(tile_log2),
                                                          ctypes.byref(o), _opt_dev(d_out)), "amdmsm_fr_domain_fft_device")
+
+    def fr_domain_fft_batch_device(self, curve, d_values, m, batch, d_out, in_stride=None, out_stride=None, inverse=False,
+                                   coset=None, plain=False, tile_log2=0, stream=None):
+        """``fr_domain_fft_device`` over ``batch`` vectors of ``m`` records (``amdmsm_fr_domain_fft_batch_device``), vector
+        v at ``v * in_stride`` / ``v * out_stride`` records (None = m: packed); every vector gets what the single call
+        gives it."""
+        g = self._coset_record(curve, coset, plain)
+        o = self._opts(scalars_plain=plain, stream=stream)
+        self._check(self.lib.amdmsm_fr_domain_fft_batch_device(
+            self.h, curve, _opt_dev(d_values), ctypes.c_size_t(m), ctypes.c_size_t(batch),
+            ctypes.c_size_t(m if in_stride is None else in_stride), ctypes.c_size_t(m if out_stride is None else out_stride),
+            DOMAIN_INVERSE if inverse else 0, _opt_ptr(g), int(tile_log2), ctypes.byref(o), _opt_dev(d_out)),
+            "amdmsm_fr_domain_fft_batch_device")
+
+    def fr_fft_batch(self, curve, values, omega=None, inverse=False, coset=None, plain=False, tile_log2=0, out=None, *,
+                     pre=None, post=None, scale=None):
+        """``fr_fft`` of every row of ``values``, a (batch, n, fr_limbs) uint64 array, with one set of parameters
+        (``amdmsm_fr_fft_batch``): one chain of passes whose grid covers the whole batch.  Returns an array of the same
+        shape; row v is what ``fr_fft(values[v], ...)`` gives, bit for bit."""
+        limbs = _fr_limbs(curve)
+        values = np.ascontiguousarray(values, dtype=np.uint64)
+        assert values.ndim == 3 and values.shape[2] == limbs, "values must be (batch, n, fr_limbs) uint64"
+        batch, n = int(values.shape[0]), int(values.shape[1])
+        if out is None:
+            out = np.zeros((batch, n, limbs), dtype=np.uint64)
+        assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape == (batch, n, limbs)
+        w, pre, post, scale = self._fr_params(curve, n, omega, inverse, coset, plain, (pre, post, scale))
+        o = self._opts(scalars_plain=plain)
+        rc = self.lib.amdmsm_fr_fft_batch(self.h, curve, _np_ptr(values) if values.size else None, ctypes.c_size_t(n),
+                                          ctypes.c_size_t(batch), _opt_ptr(w), _opt_ptr(pre), _opt_ptr(post), _opt_ptr(scale),
+                                          int(tile_log2), ctypes.byref(o), _np_ptr(out) if out.size else None)
+        self._check(rc, "amdmsm_fr_fft_batch")
+        return out
+
+    def fr_fft_batch_device(self, curve, d_values, n, batch, d_out, in_stride=None, out_stride=None, omega=None, inverse=False,
+                            coset=None, plain=False, tile_log2=0, stream=None, *, pre=None, post=None, scale=None):
+        """``fr_fft_batch`` on device-resident records (``amdmsm_fr_fft_batch_device``): vector v starts ``v * in_stride``
+        records into ``d_values`` and ``v * out_stride`` records into ``d_out`` (None = n: packed); ``d_out`` may be
+        ``d_values`` with equal strides; enqueued on ``stream``, not synchronised."""
+        w, pre, post, scale = self._fr_params(curve, n, omega, inverse, coset, plain, (pre, post, scale))
+        o = self._opts(scalars_plain=plain, stream=stream)
+        self._check(self.lib.amdmsm_fr_fft_batch_device(
+            self.h, curve, _opt_dev(d_values), ctypes.c_size_t(n), ctypes.c_size_t(batch),
+            ctypes.c_size_t(n if in_stride is None else in_stride), ctypes.c_size_t(n if out_stride is None else out_stride),
+            _opt_ptr(w), _opt_ptr(pre), _opt_ptr(post), _opt_ptr(scale), int(tile_log2), ctypes.byref(o), _opt_dev(d_out)),
+            "amdmsm_fr_fft_batch_device")
+
+    def _blind_records(self, curve, blind, plain):
+        if blind is None:
+            return None
+        assert len(blind) == 3, "blind: d1, d2, d3"
+        limbs, r = _fr_limbs(curve), fr_modulus(curve, G1)
+        return np.array([_fr_record(x, limbs, r, plain) for x in blind], dtype=np.uint64).reshape(3, limbs)
+
+    def qap_witness_map(self, curve, mat_a, mat_b, mat_c, z, m, blind=None, plain=False):
+        """libsnark's ``r1cs_to_qap_witness_map`` as one call (``amdmsm_fr_qap_witness_map``): the ``m + 1`` coefficients of
+        H with ``(A + d1 Z)(B + d2 Z) - (C + d3 Z) = H Z`` on the domain of ``m`` points (a size ``fr_domain`` answers
+        with), A, B, C interpolating the applies of the three ``FrMatrix`` handles on ``z`` (an (n_z, fr_limbs) uint64
+        array), zero-filled to m.  ``blind``: the ints (d1, d2, d3), None for none.  Records in the form ``plain`` says."""
+        z, n_z = _fr_array(curve, z)
+        h = np.zeros((m + 1, _fr_limbs(curve)), dtype=np.uint64)
+        b = self._blind_records(curve, blind, plain)
+        o = self._opts(scalars_plain=plain)
+        rc = self.lib.amdmsm_fr_qap_witness_map(self.h, curve, ctypes.c_uint64(mat_a.handle), ctypes.c_uint64(mat_b.handle),
+                                                ctypes.c_uint64(mat_c.handle), _np_ptr(z) if n_z else None, ctypes.c_size_t(n_z),
+                                                ctypes.c_size_t(m), _opt_ptr(b), ctypes.byref(o), _np_ptr(h))
+        self._check(rc, "amdmsm_fr_qap_witness_map")
+        return h
+
+    def qap_witness_map_device(self, curve, mat_a, mat_b, mat_c, d_z, n_z, m, d_h, blind=None, plain=False, stream=None):
+        """``qap_witness_map`` from ``n_z`` device-resident records into the ``m + 1`` records of ``d_h``
+        (``amdmsm_fr_qap_witness_map_device``); enqueued on ``stream``, not synchronised."""
+        b = self._blind_records(curve, blind, plain)
+        o = self._opts(scalars_plain=plain, stream=stream)
+        self._check(self.lib.amdmsm_fr_qap_witness_map_device(
+            self.h, curve, ctypes.c_uint64(mat_a.handle), ctypes.c_uint64(mat_b.handle), ctypes.c_uint64(mat_c.handle),
+            _opt_dev(d_z), ctypes.c_size_t(n_z), ctypes.c_size_t(m), _opt_ptr(b), ctypes.byref(o), _opt_dev(d_h)),
+            "amdmsm_fr_qap_witness_map_device")
 
     def fr_domain_divide_by_z(self, curve, values, coset, plain=False, out=None):
         """``out[j] = values[j] / Z(g x_j)`` over the domain of ``len(values)`` points (``amdmsm_fr_domain_divide_by_z``),

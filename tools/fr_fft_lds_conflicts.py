@@ -8,7 +8,11 @@ conflict-free when its 16 slots differ mod 16.  Per access the script prints the
 share a bank (1 = conflict-free) with the swizzle and, for comparison, with the plain layout.
 
     python tools/fr_fft_lds_conflicts.py
+    python tools/fr_fft_lds_conflicts.py --batch     k_fr_fft_pass_batch below 2^10 records: several whole vectors in a
+                                                     tile, the vector index in the upper bits of the tile index
 """
+import sys
+
 LDS_LOG2, TPB = 10, 256
 
 
@@ -58,7 +62,60 @@ def pass_accesses(t, ls):
     yield "store: get", out
 
 
+def batch_accesses(log_n, t, ls):
+    """the same for k_fr_fft_pass_batch below 2^10 records: the tile holds 2^(10 - log_n) whole vectors of 2^log_n records,
+    the vector index in the upper bits of the tile index, and the pass does t of a vector's stages on 2^(log_n - t) columns"""
+    le, lc = log_n, log_n - t
+    C, R, Et = 1 << lc, 1 << t, 1 << LDS_LOG2
+    yield "load: put", list(range(Et))
+    for j in range(t):
+        lh = t - 1 - j
+        h = 1 << lh
+        lo = []
+        for bf in range(Et // 2):
+            vl, bb = bf >> (le - 1), bf & ((1 << (le - 1)) - 1)
+            cc, x = bb & (C - 1), bb >> lc
+            i, blk = x & (h - 1), x >> lh
+            lo.append((vl << le) | ((((blk << (lh + 1)) + i) << lc) | cc))
+        for half, rec in (("lo", lo), ("hi", [L + (h << lc) for L in lo])):
+            yield f"stage {j}: get {half}", rec
+            yield f"stage {j}: put {half}", rec
+    lsp = min(ls, lc)
+    out = []
+    for e in range(Et):
+        vl, ee = e >> le, e & ((1 << le) - 1)
+        ql, k2, pl = ee & ((1 << lsp) - 1), (ee >> lsp) & (R - 1), ee >> (lsp + t)
+        out.append((vl << le) | (brev(k2, t) << lc) | ((pl << lsp) + ql))
+    yield "store: get", out
+
+
+def batch_shapes():
+    """(log_n, t, ls) of every pass of a transform of fewer than 2^10 records, for every tile the plan allows"""
+    seen = set()
+    for log_n in range(1, LDS_LOG2):
+        for tile in range(4, 9):
+            passes = (log_n + tile - 1) // tile
+            for k in range(passes):
+                seen.add((log_n, tile if k < passes - 1 else log_n - (passes - 1) * tile, k * tile))
+    return sorted(seen)
+
+
+def main_batch():
+    total = 0
+    for log_n, t, ls in batch_shapes():
+        rows = [(name, worst(rec, sw, "put" in name), worst(rec, None, "put" in name)) for name, rec in batch_accesses(log_n, t, ls)]
+        bad = [(n, a, b) for n, a, b in rows if a > 1]
+        total += len(bad)
+        print(f"n = 2^{log_n} ({1 << (LDS_LOG2 - log_n)} vectors a tile), stages {t}, stride 2^{ls}: {len(rows)} accesses, "
+              f"{len(bad)} with conflicts; without the swizzle {sum(1 for r in rows if r[2] > 1)} (worst {max(r[2] for r in rows)}-way)")
+        for n, a, b in bad:
+            print(f"    {n}: {a}-way (plain layout {b}-way)")
+    print("accesses with conflicts:", total)
+
+
 def main():
+    if "--batch" in sys.argv[1:]:
+        return main_batch()
     total = 0
     for t in range(4, 9):
         for ls in sorted({0, t, 2 * t}):
