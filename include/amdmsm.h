@@ -998,6 +998,37 @@ int amdmsm_field_probe_device(amdmsm_ctx *ctx, int curve, int group, int impl, i
  * d_pt: n compact affine records (ops 0, 1, 4) or n more (X, Y, ZZ, ZZZ) records (op 2), else null. */
 int amdmsm_xyzz_probe_device(amdmsm_ctx *ctx, int curve, int group, int impl, int op, const void *d_acc,
                              const void *d_pt, void *d_out, size_t n);
+/* The reduced-radix layer (signed limbs of B = 28 / 29 bits, L per Fq component; rho = 2^(B L) = 2^D 2^(32 fq_words))
+ * that the bucket accumulation of the pairing-friendly groups runs on: one function per element on RAW limbs, taken and
+ * stored as they are.  AMDMSM_ERR_UNSUPPORTED, with amdmsm_last_error naming the group and nothing written, for the
+ * MNT groups, which do not use it.  Arrays hold one row per Fq component: n rows for an Fq group, 2 n for an Fq2 group
+ * (element i = rows 2 i and 2 i + 1 = c0, c1).  d_a .. d_d: rows of L int32 limbs (null where the op takes fewer);
+ * d_w: rows of fq_words words (ops that start from words); d_out: rows of L limbs; d_outw: rows of fq_words words, zero
+ * where the op yields none; d_flag: one word per ELEMENT (an Fq2 element: the test holds in both components).
+ * Products: 0 a b, 1 a b + c d, 2 a^2 -- each per component -- 3 element product, 4 element square, 5 element a b - c d
+ * (Fq2: fused over the pair), 6 a 2^(32 fq_words) / rho, 7 a 2^(32 fq_words - D) / rho, 8 words -> limbs with the factor
+ * rho, 9 / 10 export of a component with the factor rho / rho 2^D to canonical words (d_outw).
+ * Others: 16 one parallel carry step, 17 full carry propagation, 18 k a and a carry step (k = 2, 3, 4), 19 negation of
+ * the elements of odd index, 20 / 21 limbs of the words / of the words shifted by D, 22 the words 2^D less a multiple of
+ * p (first point, reduced; AMDMSM_ERR_UNSUPPORTED for bw6_761, whose table of 2^16 multiples is not built), 23 the first-point coordinate of the group (22 or 21), 24 canonical limbs -> words (d_outw),
+ * 25 a product's output in (-p, 2p) -> [0, p), 26 flag: a = 0 mod p exactly, 27 / 28 flag: the one-limb filter for
+ * |j| < 2^D + 64 / < 64 (necessary for a = j p, not sufficient), 29 / 30 the constants 2^(B L), 2^(B L + D) mod p. */
+int amdmsm_rr_probe_device(amdmsm_ctx *ctx, int curve, int group, int op, int k, const void *d_a, const void *d_b,
+                           const void *d_c, const void *d_d, const void *d_w, void *d_out, void *d_outw,
+                           uint32_t *d_flag, size_t n);
+/* One step of one reduced-radix point function per element.  d_acc, d_sec, d_out: rows of 4 L limbs (X, Y, ZZ, ZZZ as a
+ * lane of the accumulation holds them; the Jacobian ops: X, Y, Z, 0); d_pt: rows of 2 fq_words words, an affine point in
+ * canonical Montgomery words, (0, 0) = infinity; d_fin (null: zeros) / d_fout: one word per element -- in: bit 0 the
+ * accumulator is infinity, bit 1 the second operand is, bit 2 subtract the point; out: bit 0 the result is infinity,
+ * bit 1 the answer of op 18.  d_outw: rows of 4 fq_words words, the result exported to canonical words as the readers of
+ * a bucket record do it (zeros for infinity).
+ * 0 mixed addition acc += pt, 1 first point of a bucket, 2 ZZ / ZZZ from the factor rho 2^D to rho, 3 / 4 the
+ * accumulator unchanged, exported as a bucket record (ZZ, ZZZ with rho 2^D) / as a sum (rho), 8 doubling and 9 general
+ * addition acc += sec on the factor rho, 16 Jacobian doubling, 17 Jacobian mixed addition of (sec.X, sec.Y), 18 Jacobian
+ * infinity test. */
+int amdmsm_xyzz_rr_probe_device(amdmsm_ctx *ctx, int curve, int group, int op, const void *d_acc, const void *d_sec,
+                                const void *d_pt, const uint32_t *d_fin, void *d_out, void *d_outw, uint32_t *d_fout,
+                                size_t n);
 int amdmsm_digits_device(amdmsm_ctx *ctx, int curve, int group, const void *d_scalars, size_t n,
                          int scalars_plain, int c, int num_windows, int32_t *d_out);
 /* throughput probes (2*iters dependent Fq products / iters mixed additions per lane);

@@ -1656,6 +1656,55 @@ int amdmsm_xyzz_probe_device(amdmsm_ctx *ctx, int curve, int group, int impl, in
     return AMDMSM_OK;
 }
 
+// "<curve>_g<group>" for the message of a probe the group's unit does not carry
+static std::string probe_group_name(int curve, int group) {
+    static const char *const names[] = {"alt_bn128", "bls12_377", "bw6_761", "bls12_381", "mnt4", "mnt6"};
+    const std::string c = curve >= 0 && curve < 6 ? names[curve] : "curve " + std::to_string(curve);
+    return c + "_g" + std::to_string(group);
+}
+
+int amdmsm_rr_probe_device(amdmsm_ctx *ctx, int curve, int group, int op, int k, const void *d_a, const void *d_b,
+                           const void *d_c, const void *d_d, const void *d_w, void *d_out, void *d_outw, uint32_t *d_flag,
+                           size_t n) {
+    GET_VT(ctx, curve, group);
+    if (!vt->rr_probe)
+        return fail(ctx, AMDMSM_ERR_UNSUPPORTED, probe_group_name(curve, group) + " does not use the reduced-radix layer");
+    const bool known = (op >= RRPROBE_MUL && op <= RRPROBE_EXPORT_D) || (op >= RRPROBE_NORM && op <= RRPROBE_SET_POW2_BL_D);
+    if (!known) return fail(ctx, AMDMSM_ERR_BAD_ARG, "op");
+    if (!d_out || !d_outw || !d_flag) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null output");
+    if (op == RRPROBE_SMALL_TIMES && (k < 2 || k > 4)) return fail(ctx, AMDMSM_ERR_BAD_ARG, "k");
+    if (op == RRPROBE_FIRST_REDUCED && !vt->rr_probe_first_reduced)
+        return fail(ctx, AMDMSM_ERR_UNSUPPORTED, probe_group_name(curve, group) + " has no table for the reduced first point");
+    const bool words_in = op == RRPROBE_FROM_WORDS_RHO || (op >= RRPROBE_FROM_WORDS_0 && op <= RRPROBE_FIRST_COORD);
+    const bool none_in = op == RRPROBE_SET_POW2_BL || op == RRPROBE_SET_POW2_BL_D;
+    const int arity = (op == RRPROBE_MUL2 || op == RRPROBE_RE_MUL_SUB_MUL) ? 4 : (op == RRPROBE_MUL || op == RRPROBE_RE_MUL) ? 2 : 1;
+    if (words_in ? !d_w : (!none_in && (!d_a || (arity >= 2 && !d_b) || (arity == 4 && (!d_c || !d_d)))))
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "missing operand");
+    vt->rr_probe(ctx->stream, op, k, (const int32_t *)d_a, (const int32_t *)d_b, (const int32_t *)d_c, (const int32_t *)d_d,
+                 (const uint32_t *)d_w, (int32_t *)d_out, (uint32_t *)d_outw, d_flag, n);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return AMDMSM_OK;
+}
+
+int amdmsm_xyzz_rr_probe_device(amdmsm_ctx *ctx, int curve, int group, int op, const void *d_acc, const void *d_sec,
+                                const void *d_pt, const uint32_t *d_fin, void *d_out, void *d_outw, uint32_t *d_fout, size_t n) {
+    GET_VT(ctx, curve, group);
+    if (!vt->xyzz_rr_probe)
+        return fail(ctx, AMDMSM_ERR_UNSUPPORTED, probe_group_name(curve, group) + " does not use the reduced-radix layer");
+    const bool known = (op >= XRRPROBE_MADD && op <= XRRPROBE_EXPORT_RHO) || op == XRRPROBE_DBL_RHO || op == XRRPROBE_ADD_RHO ||
+                       (op >= XRRPROBE_JAC_DBL && op <= XRRPROBE_JAC_IS_INF);
+    if (!known) return fail(ctx, AMDMSM_ERR_BAD_ARG, "op");
+    if (!d_acc || !d_out || !d_outw || !d_fout) return fail(ctx, AMDMSM_ERR_BAD_ARG, "null accumulator / output");
+    if (((op == XRRPROBE_MADD || op == XRRPROBE_FIRST) && !d_pt) || ((op == XRRPROBE_ADD_RHO || op == XRRPROBE_JAC_MADD) && !d_sec))
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "missing operand");
+    vt->xyzz_rr_probe(ctx->stream, op, (const int32_t *)d_acc, (const int32_t *)d_sec, (const uint32_t *)d_pt, d_fin,
+                      (int32_t *)d_out, (uint32_t *)d_outw, d_fout, n);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return AMDMSM_OK;
+}
+
 int amdmsm_group_op_device(amdmsm_ctx *ctx, int curve, int group, int op, const void *d_a, const void *d_b,
                            void *d_out, size_t n, int out_form) {
     GET_VT(ctx, curve, group);

@@ -382,6 +382,21 @@ struct group_vtable {
     // One extended-Jacobian function (XPROBE_*) per lane: acc and out are n (X, Y, ZZ, ZZZ) records of 4 * el_words
     // words; pt: n compact affine records, or n more (X, Y, ZZ, ZZZ) records for XPROBE_ADD (null where unused)
     void (*xyzz_probe)(hipStream_t, int impl, int op, const uint32_t* acc, const uint32_t* pt, uint32_t* out, size_t n);
+    // ---- probes of the reduced-radix layer, rr.cuh (tests/test_gpu_rr_probe.py); null where the group does not
+    // accumulate on it (the MNT units) ----------
+    // One function (RRPROBE_*) per element on RAW limbs.  Rows: one per Fq component, n rows for an Fq group, 2 n for an
+    // Fq2 group (element i = rows 2 i, 2 i + 1 = c0, c1, served by a lane pair).  a, b, c, d: rows of L limbs (null:
+    // zeros); w: rows of fq_words words (null: zeros); out: rows of L limbs; outw: rows of fq_words words; flag: one word
+    // per ELEMENT; k: the factor of RRPROBE_SMALL_TIMES.
+    void (*rr_probe)(hipStream_t, int op, int k, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d,
+                     const uint32_t* w, int32_t* out, uint32_t* outw, uint32_t* flag, size_t n);
+    // One step of one point function (XRRPROBE_*) per element.  acc, sec (null: zeros), out: rows of 4 L limbs (x, y, zz,
+    // zzz; the Jacobian ops: x, y, z, 0); pt (null: zeros): rows of 2 fq_words words (affine x, y); fin (null: zeros), fout:
+    // one word per element -- fin bit 0: acc is infinity, bit 1: sec is, bit 2: subtract; fout bit 0: the result is
+    // infinity, bit 1: jac_is_inf_rr; outw: rows of 4 fq_words words, the result exported (zeros for infinity).
+    void (*xyzz_rr_probe)(hipStream_t, int op, const int32_t* acc, const int32_t* sec, const uint32_t* pt, const uint32_t* fin,
+                          int32_t* out, uint32_t* outw, uint32_t* fout, size_t n);
+    int rr_probe_first_reduced;   // the unit carries RRPROBE_FIRST_REDUCED (the table of multiples of p is built: D <= 8)
 };
 constexpr int FOLD_MAX_K = 8;
 constexpr size_t FOLD_DIGIT_BYTES = 2048;   // 2 FOLD_MAX_K rows of at most 100 bytes
@@ -399,6 +414,45 @@ enum {
     FPROBE_CANON = 23,
 };
 enum { XPROBE_MADD_LZ = 0, XPROBE_MADD = 1, XPROBE_ADD = 2, XPROBE_DBL = 3, XPROBE_DBL_AFFINE = 4, XPROBE_TO_JAC = 5 };
+// op codes of rr_probe (include/amdmsm.h amdmsm_rr_probe_device): the products ...
+enum {
+    RRPROBE_MUL = 0,             // rr_mul(a, b), per component
+    RRPROBE_MUL2 = 1,            // rr_mul2: a b + c d
+    RRPROBE_SQR = 2,             // rr_sqr(a)
+    RRPROBE_RE_MUL = 3,          // re_mul on the element (Fq2: over the lane pair)
+    RRPROBE_RE_SQR = 4,
+    RRPROBE_RE_MUL_SUB_MUL = 5,  // a b - c d
+    RRPROBE_MUL_POW2_32N = 6,    // rr_mul_pow2<32 N>
+    RRPROBE_MUL_POW2_32N_D = 7,  // rr_mul_pow2<32 N - D>
+    RRPROBE_FROM_WORDS_RHO = 8,  // re_from_words_rho(w)
+    RRPROBE_EXPORT_0 = 9,        // rr_export_component<0>(a) -> outw
+    RRPROBE_EXPORT_D = 10,       // rr_export_component<D>(a) -> outw
+    // ... and everything else
+    RRPROBE_NORM = 16, RRPROBE_RIPPLE = 17,
+    RRPROBE_SMALL_TIMES = 18,    // re_small_times(a, k), k = 2, 3, 4
+    RRPROBE_CNEG = 19,           // rr_cneg(a, odd element index)
+    RRPROBE_FROM_WORDS_0 = 20, RRPROBE_FROM_WORDS_D = 21,   // rr_from_words<0 / D>(w)
+    RRPROBE_FIRST_REDUCED = 22,  // rr_first_reduced(w)
+    RRPROBE_FIRST_COORD = 23,    // re_first_coord(w)
+    RRPROBE_TO_WORDS = 24,       // rr_to_words(a) -> outw
+    RRPROBE_CANON_PRODUCT = 25,
+    RRPROBE_IS_ZERO_EXACT = 26,  // flag: re_is_zero_exact(a)
+    RRPROBE_MAYBE_ZERO_K = 27,   // flag: re_maybe_zero<rr_filter_k>(a)
+    RRPROBE_MAYBE_ZERO_64 = 28,  // flag: re_maybe_zero<64>(a)
+    RRPROBE_SET_POW2_BL = 29, RRPROBE_SET_POW2_BL_D = 30,   // re_set_pow2<B L>, <B L + D>
+};
+enum {
+    XRRPROBE_MADD = 0,           // xyzz_madd_rr(acc, inf, pt, neg)
+    XRRPROBE_FIRST = 1,          // xyzz_rr_first(pt, neg)
+    XRRPROBE_REC_TO_RHO = 2,     // xyzz_rec_to_rho(acc)
+    XRRPROBE_EXPORT = 3,         // acc as it is; outw: the export of a record of k_accumulate (zz, zzz with rho 2^D)
+    XRRPROBE_EXPORT_RHO = 4,     // ... of a sum (every coordinate with rho)
+    XRRPROBE_DBL_RHO = 8,        // xyzz_dbl_rho(acc, inf)
+    XRRPROBE_ADD_RHO = 9,        // xyzz_add_rho(acc, inf, sec, sec_inf)
+    XRRPROBE_JAC_DBL = 16,       // jac_dbl_rr(acc, inf)
+    XRRPROBE_JAC_MADD = 17,      // jac_madd_rr(acc, inf, sec.x, sec.y)
+    XRRPROBE_JAC_IS_INF = 18,    // fout bit 1: jac_is_inf_rr(acc, inf)
+};
 
 const group_vtable* vt_alt_bn128_g1() __attribute__((weak));
 const group_vtable* vt_alt_bn128_g2() __attribute__((weak));

@@ -3405,6 +3405,229 @@ __global__ void __launch_bounds__(TPB) k_xyzz_probe(int op, const uint32_t* __re
     store_xyzz(out + i * ZZW, r);
 }
 
+#if AMDMSM_ACC_RR
+// Probes of the reduced-radix layer (rr.cuh; group_vtable::rr_probe / xyzz_rr_probe, tests/test_gpu_rr_probe.py).  Operands
+// and results are RAW limbs: L int32 per Fq component, taken and stored as they are -- nothing is carried, reduced or
+// range-checked on the way in or out, so a test chooses the representative and the spread over the limbs that a function
+// meets and sees the ones it leaves.  One Fq component per lane: row t of every array belongs to lane t.  For the Fq2
+// groups (ERR = Rr2H) element i is the lane pair (2 i, 2 i + 1) = (c0, c1); both lanes of a pair take the same branches
+// and leave together, and flags are per pair.  No address depends on an operand's value.
+constexpr int RRP_LANES = re_info<ERR>::PAIR ? 2 : 1;
+// rr_first_reduced reads a table of 2^D + 1 multiples of p, which the library builds only where the first point needs the
+// reduction (D = 5); the probe runs the function on every field whose table is as small (D <= 8: all but bw6_761, D = 16)
+constexpr bool RRP_FIRST_REDUCED = rr_shape<FQ>::D <= 8;
+AMDMSM_DEV void rrp_load(Rr<FQ>& r, const int32_t* q) {
+#pragma unroll
+    for (int i = 0; i < RRL; ++i) r.v[i] = q ? q[i] : 0;
+}
+AMDMSM_DEV void rrp_store(int32_t* q, const Rr<FQ>& r) {
+#pragma unroll
+    for (int i = 0; i < RRL; ++i) q[i] = r.v[i];
+}
+AMDMSM_DEV void rrp_load_words(uint32_t (&w)[FQ::N], const uint32_t* q) {
+#pragma unroll
+    for (int i = 0; i < FQ::N; ++i) w[i] = q ? q[i] : 0u;
+}
+AMDMSM_DEV void rrp_store_words(uint32_t* q, const uint32_t (&w)[FQ::N]) {
+#pragma unroll
+    for (int i = 0; i < FQ::N; ++i) q[i] = w[i];
+}
+// SET 0: the products (RRPROBE_MUL .. RRPROBE_EXPORT_D); SET 1: linear operations, conversions, constants and residue
+// tests -- two kernels, so that no single one inlines every product of the widest field.
+// a, b, c, d: n * RRP_LANES rows of L limbs (null: zeros); w: as many rows of N words (null: zeros); out: rows of L limbs;
+// outw: rows of N words (zero where the op yields none); flag: one word per element.
+template <int SET>
+__global__ void __launch_bounds__(TPB) k_rr_probe(int op, int k, const int32_t* __restrict__ a, const int32_t* __restrict__ b,
+                                                  const int32_t* __restrict__ c, const int32_t* __restrict__ d,
+                                                  const uint32_t* __restrict__ w, int32_t* __restrict__ out,
+                                                  uint32_t* __restrict__ outw, uint32_t* __restrict__ flag, size_t n) {
+    constexpr int D = rr_shape<FQ>::D;
+    constexpr int BL = rr_shape<FQ>::B * rr_shape<FQ>::L;
+    const size_t t = gtid();
+    const size_t i = t / RRP_LANES;
+    if (i >= n) return;
+    ERR x, y, z, u, r;
+    rrp_load(re_comp(x), a ? a + t * RRL : nullptr);
+    rrp_load(re_comp(y), b ? b + t * RRL : nullptr);
+    rrp_load(re_comp(z), c ? c + t * RRL : nullptr);
+    rrp_load(re_comp(u), d ? d + t * RRL : nullptr);
+    uint32_t ww[FQ::N], ow[FQ::N];
+    rrp_load_words(ww, w ? w + t * FQ::N : nullptr);
+#pragma unroll
+    for (int j = 0; j < FQ::N; ++j) ow[j] = 0;
+    re_zero(r);
+    bool f = false;
+    if constexpr (SET == 0) {
+        switch (op) {
+        case RRPROBE_MUL: rr_mul(re_comp(r), re_comp(x), re_comp(y)); break;
+        case RRPROBE_MUL2: rr_mul2(re_comp(r), re_comp(x), re_comp(y), re_comp(z), re_comp(u)); break;
+        case RRPROBE_SQR: rr_sqr(re_comp(r), re_comp(x)); break;
+        case RRPROBE_RE_MUL: re_mul(r, x, y); break;
+        case RRPROBE_RE_SQR: re_sqr(r, x); break;
+        case RRPROBE_RE_MUL_SUB_MUL: re_mul_sub_mul(r, x, y, z, u); break;
+        case RRPROBE_MUL_POW2_32N: rr_mul_pow2<FQ, 32 * FQ::N>(re_comp(r), re_comp(x)); break;
+        case RRPROBE_MUL_POW2_32N_D: rr_mul_pow2<FQ, 32 * FQ::N - D>(re_comp(r), re_comp(x)); break;
+        case RRPROBE_FROM_WORDS_RHO: re_from_words_rho(r, ww); break;
+        case RRPROBE_EXPORT_0:
+            r = x;
+            rr_export_component<FQ, 0>(ow, re_comp(x));
+            break;
+        case RRPROBE_EXPORT_D:
+            r = x;
+            rr_export_component<FQ, D>(ow, re_comp(x));
+            break;
+        default: break;
+        }
+    } else {
+        switch (op) {
+        case RRPROBE_NORM: rr_norm(re_comp(r), re_comp(x)); break;
+        case RRPROBE_RIPPLE:
+            r = x;
+            rr_ripple(re_comp(r));
+            break;
+        case RRPROBE_SMALL_TIMES:
+            if (k == 2) re_small_times(r, x, 2);
+            else if (k == 3) re_small_times(r, x, 3);
+            else re_small_times(r, x, 4);
+            break;
+        case RRPROBE_CNEG: rr_cneg(re_comp(r), re_comp(x), (i & 1u) != 0); break;   // negates the odd elements
+        case RRPROBE_FROM_WORDS_0: rr_from_words<FQ, 0>(re_comp(r), ww); break;
+        case RRPROBE_FROM_WORDS_D: rr_from_words<FQ, D>(re_comp(r), ww); break;
+        case RRPROBE_FIRST_REDUCED:
+            if constexpr (RRP_FIRST_REDUCED) rr_first_reduced<FQ>(re_comp(r), ww);
+            break;
+        case RRPROBE_FIRST_COORD: re_first_coord(r, ww); break;
+        case RRPROBE_TO_WORDS:
+            r = x;
+            rr_to_words<FQ>(ow, re_comp(x));
+            break;
+        case RRPROBE_CANON_PRODUCT:
+            r = x;
+            rr_canon_product(re_comp(r));
+            break;
+        case RRPROBE_IS_ZERO_EXACT:
+            r = x;
+            f = re_is_zero_exact(x);
+            break;
+        case RRPROBE_MAYBE_ZERO_K:
+            r = x;
+            f = re_maybe_zero<rr_filter_k<FQ>()>(x);
+            break;
+        case RRPROBE_MAYBE_ZERO_64:
+            r = x;
+            f = re_maybe_zero<64>(x);
+            break;
+        case RRPROBE_SET_POW2_BL: re_set_pow2<BL>(r); break;
+        case RRPROBE_SET_POW2_BL_D: re_set_pow2<BL + D>(r); break;
+        default: break;
+        }
+    }
+    rrp_store(out + t * RRL, re_comp(r));
+    rrp_store_words(outw + t * FQ::N, ow);
+    if (t % RRP_LANES == 0) flag[i] = f ? 1u : 0u;
+}
+
+// Point-level probe: one step of one point function of rr.cuh per element.  acc, sec, out: n * RRP_LANES rows of 4 L limbs
+// (x, y, zz, zzz as a lane of k_accumulate holds them; the Jacobian ops read x, y, z from the first three and leave the
+// fourth zero); pt: rows of 2 N words (this lane's component of an affine point); fin: one word per element -- bit 0 the
+// accumulator is infinity, bit 1 the second operand is, bit 2 subtract (neg); fout: bit 0 the result is infinity, bit 1
+// jac_is_inf_rr.  outw: rows of 4 N words, the result exported as the consumers of a record do it (rr_export_component on
+// every coordinate: zz / zzz with the factor rho 2^D behind XRRPROBE_MADD / FIRST / EXPORT, rho behind every other op),
+// zero for infinity.  SET 0: mixed addition, first point, conversions; SET 1: the general addition and doubling; SET 2:
+// the Jacobian functions.
+template <int SET>
+__global__ void __launch_bounds__(TPB) k_xyzz_rr_probe(int op, const int32_t* __restrict__ acc, const int32_t* __restrict__ sec,
+                                                       const uint32_t* __restrict__ pt, const uint32_t* __restrict__ fin,
+                                                       int32_t* __restrict__ out, uint32_t* __restrict__ outw,
+                                                       uint32_t* __restrict__ fout, size_t n) {
+    constexpr int D = rr_shape<FQ>::D;
+    const size_t t = gtid();
+    const size_t i = t / RRP_LANES;
+    if (i >= n) return;
+    XyzzRr<ERR> p, q;
+    const int32_t* pa = acc + t * 4 * RRL;
+    rrp_load(re_comp(p.x), pa);
+    rrp_load(re_comp(p.y), pa + RRL);
+    rrp_load(re_comp(p.zz), pa + 2 * RRL);
+    rrp_load(re_comp(p.zzz), pa + 3 * RRL);
+    const int32_t* ps = sec ? sec + t * 4 * RRL : nullptr;
+    rrp_load(re_comp(q.x), ps);
+    rrp_load(re_comp(q.y), ps ? ps + RRL : nullptr);
+    rrp_load(re_comp(q.zz), ps ? ps + 2 * RRL : nullptr);
+    rrp_load(re_comp(q.zzz), ps ? ps + 3 * RRL : nullptr);
+    uint32_t wx[FQ::N], wy[FQ::N];
+    rrp_load_words(wx, pt ? pt + t * 2 * FQ::N : nullptr);
+    rrp_load_words(wy, pt ? pt + t * 2 * FQ::N + FQ::N : nullptr);
+    const uint32_t fi = fin ? fin[i] : 0u;
+    bool inf = (fi & 1u) != 0;
+    const bool q_inf = (fi & 2u) != 0, neg = (fi & 4u) != 0;
+    bool is_inf = false;
+    bool rho = true;   // zz / zzz of the result carry the factor rho (else rho 2^D)
+    if constexpr (SET == 0) {
+        switch (op) {
+        case XRRPROBE_MADD:
+            xyzz_madd_rr(p, inf, wx, wy, neg);
+            rho = false;
+            break;
+        case XRRPROBE_FIRST:
+            xyzz_rr_first(p, wx, wy, neg);
+            inf = false;
+            rho = false;
+            break;
+        case XRRPROBE_REC_TO_RHO: xyzz_rec_to_rho(p); break;
+        case XRRPROBE_EXPORT: rho = false; break;
+        default: break;
+        }
+    } else if constexpr (SET == 1) {
+        switch (op) {
+        case XRRPROBE_DBL_RHO: xyzz_dbl_rho(p, inf); break;
+        case XRRPROBE_ADD_RHO: xyzz_add_rho(p, inf, q, q_inf); break;
+        default: break;
+        }
+    } else {
+        JacRr<ERR> j;
+        j.x = p.x;
+        j.y = p.y;
+        j.z = p.zz;
+        switch (op) {
+        case XRRPROBE_JAC_DBL: jac_dbl_rr(j, inf); break;
+        case XRRPROBE_JAC_MADD: jac_madd_rr(j, inf, q.x, q.y); break;
+        case XRRPROBE_JAC_IS_INF: is_inf = jac_is_inf_rr(j, inf); break;
+        default: break;
+        }
+        p.x = j.x;
+        p.y = j.y;
+        p.zz = j.z;
+        re_zero(p.zzz);
+    }
+    int32_t* po = out + t * 4 * RRL;
+    rrp_store(po, re_comp(p.x));
+    rrp_store(po + RRL, re_comp(p.y));
+    rrp_store(po + 2 * RRL, re_comp(p.zz));
+    rrp_store(po + 3 * RRL, re_comp(p.zzz));
+    uint32_t ow[4][FQ::N];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int j = 0; j < FQ::N; ++j) ow[c][j] = 0;
+    if (!inf) {
+        rr_export_component<FQ, 0>(ow[0], re_comp(p.x));
+        rr_export_component<FQ, 0>(ow[1], re_comp(p.y));
+        if (rho) {
+            rr_export_component<FQ, 0>(ow[2], re_comp(p.zz));
+            rr_export_component<FQ, 0>(ow[3], re_comp(p.zzz));
+        } else {
+            rr_export_component<FQ, D>(ow[2], re_comp(p.zz));
+            rr_export_component<FQ, D>(ow[3], re_comp(p.zzz));
+        }
+    }
+    uint32_t* pw = outw + t * 4 * FQ::N;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) rrp_store_words(pw + c * FQ::N, ow[c]);
+    if (t % RRP_LANES == 0) fout[i] = (inf ? 1u : 0u) | (is_inf ? 2u : 0u);
+}
+#endif
+
 // Throughput probes: a dependent chain of Montgomery products / mixed additions per lane,
 // operands in registers, no memory traffic inside the loop.
 template <bool I>
@@ -4325,6 +4548,26 @@ void l_xyzz_probe(hipStream_t st, int impl, int op, const uint32_t* acc, const u
     if (impl) hipLaunchKernelGGL(k_xyzz_probe<EI>, dim3(blocks_for(n)), dim3(TPB), 0, st, op, acc, pt, out, n);
     else hipLaunchKernelGGL(k_xyzz_probe<E>, dim3(blocks_for(n)), dim3(TPB), 0, st, op, acc, pt, out, n);
 }
+#if AMDMSM_ACC_RR
+void l_rr_probe(hipStream_t st, int op, int k, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d,
+                const uint32_t* w, int32_t* out, uint32_t* outw, uint32_t* flag, size_t n) {
+    if (!n) return;
+    const dim3 grid(blocks_for(n * RRP_LANES));
+    if (op < RRPROBE_NORM) hipLaunchKernelGGL(k_rr_probe<0>, grid, dim3(TPB), 0, st, op, k, a, b, c, d, w, out, outw, flag, n);
+    else hipLaunchKernelGGL(k_rr_probe<1>, grid, dim3(TPB), 0, st, op, k, a, b, c, d, w, out, outw, flag, n);
+}
+void l_xyzz_rr_probe(hipStream_t st, int op, const int32_t* acc, const int32_t* sec, const uint32_t* pt, const uint32_t* fin,
+                     int32_t* out, uint32_t* outw, uint32_t* fout, size_t n) {
+    if (!n) return;
+    const dim3 grid(blocks_for(n * RRP_LANES));
+    if (op < XRRPROBE_DBL_RHO)
+        hipLaunchKernelGGL(k_xyzz_rr_probe<0>, grid, dim3(TPB), 0, st, op, acc, sec, pt, fin, out, outw, fout, n);
+    else if (op < XRRPROBE_JAC_DBL)
+        hipLaunchKernelGGL(k_xyzz_rr_probe<1>, grid, dim3(TPB), 0, st, op, acc, sec, pt, fin, out, outw, fout, n);
+    else
+        hipLaunchKernelGGL(k_xyzz_rr_probe<2>, grid, dim3(TPB), 0, st, op, acc, sec, pt, fin, out, outw, fout, n);
+}
+#endif
 void l_group_op(hipStream_t st, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n, int form) {
     if (!n) return;
     hipLaunchKernelGGL(k_group_op, dim3(blocks_for(n)), dim3(TPB), 0, st, op, a, b, out, n, form);
@@ -4445,6 +4688,9 @@ const group_vtable g_vt = {
     // test hooks and probes
     .field_op = l_field_op, .group_op = l_group_op, .digits = l_digits, .glv_digits = l_glv_digits,
     .mul_bench = l_mul_bench, .madd_bench = l_madd_bench, .field_probe = l_field_probe, .xyzz_probe = l_xyzz_probe,
+#if AMDMSM_ACC_RR
+    .rr_probe = l_rr_probe, .xyzz_rr_probe = l_xyzz_rr_probe, .rr_probe_first_reduced = RRP_FIRST_REDUCED ? 1 : 0,
+#endif
 };
 
 }  // namespace

@@ -269,7 +269,8 @@ AMDMSM_DEV void rr_zero(Rr<P>& r) {
     for (int i = 0; i < Rr<P>::L; ++i) r.v[i] = 0;
 }
 
-// one parallel carry step: limbs 0..L-2 back into [-4, 2^B + 4) for inputs below 2^31 in magnitude
+// one parallel carry step: limbs 0..L-2 back into [-C, 2^B + C), C = 2^(31 - B), for inputs below 2^31 in magnitude --
+// [-4, 2^B + 4) with 29-bit limbs, [-8, 2^B + 8) with 28-bit ones, the factor invariant below; limb 0 into [0, 2^B)
 template <class P>
 AMDMSM_DEV void rr_norm(Rr<P>& r, const Rr<P>& a) {
     constexpr int L = rr_shape<P>::L;

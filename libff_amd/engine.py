@@ -58,7 +58,7 @@ EXPORTED_SYMBOLS = [
     "amdmsm_set_timing", "amdmsm_get_timings", "amdmsm_last_timing_ticket", "amdmsm_get_timings_by_ticket",
     "amdmsm_set_pipeline_depth", "amdmsm_last_slot",
     "amdmsm_get_slot_timings", "amdmsm_field_op_device", "amdmsm_group_op_device",
-    "amdmsm_field_probe_device", "amdmsm_xyzz_probe_device",
+    "amdmsm_field_probe_device", "amdmsm_xyzz_probe_device", "amdmsm_rr_probe_device", "amdmsm_xyzz_rr_probe_device",
     "amdmsm_digits_device", "amdmsm_mul_bench_device", "amdmsm_madd_bench_device", "amdmsm_malloc", "amdmsm_free",
     "amdmsm_memcpy_h2d", "amdmsm_memcpy_d2h", "amdmsm_synchronize",
     "amdmsm_plan_short", "amdmsm_scalar_bits_device", "amdmsm_multi_exp_short", "amdmsm_msm_device_short",
@@ -1839,6 +1839,65 @@ class Engine:
                 if p is not None:
                     self.free(p)
         return out
+
+    def rr_probe(self, curve, group, op, limbs, words_per_row, a=None, b=None, c=None, d=None, w=None, k=0, rows_per_element=1):
+        """one reduced-radix function per element on raw limbs (op: include/amdmsm.h amdmsm_rr_probe_device).  a .. d:
+        (rows, limbs) int32 arrays, w: (rows, words_per_row) uint32, one row per Fq component (rows_per_element = 2 for
+        the Fq2 groups).  Returns (out limbs, out words, flag per element)."""
+        a, b, c, d = (None if x is None else np.ascontiguousarray(x, dtype=np.int32) for x in (a, b, c, d))
+        w = None if w is None else np.ascontiguousarray(w, dtype=np.uint32)
+        given = [x for x in (a, b, c, d, w) if x is not None]
+        if not given:
+            raise ValueError("no operand array: the ops without an input (the constants) still take a, rows of zero limbs, for the count")
+        rows = given[0].shape[0]
+        if any(x.shape[0] != rows for x in given) or rows % rows_per_element:
+            raise ValueError("operand arrays must have one length, a multiple of rows_per_element")
+        if any(x is not None and x.shape != (rows, limbs) for x in (a, b, c, d)) or (w is not None and w.shape != (rows, words_per_row)):
+            raise ValueError("operand rows of the wrong width")
+        out = np.zeros((rows, limbs), dtype=np.int32)
+        outw = np.zeros((rows, words_per_row), dtype=np.uint32)
+        flag = np.zeros(rows // rows_per_element, dtype=np.uint32)
+        ptrs = self._dev_arrays(a, b, c, d, w, out, outw, flag)
+        try:
+            self._check(self.lib.amdmsm_rr_probe_device(self.h, curve, group, int(op), int(k), *ptrs,
+                                                        ctypes.c_size_t(rows // rows_per_element)), "amdmsm_rr_probe_device")
+            self.d2h(out, ptrs[5])
+            self.d2h(outw, ptrs[6])
+            self.d2h(flag, ptrs[7])
+        finally:
+            for p in ptrs:
+                if p is not None:
+                    self.free(p)
+        return out, outw, flag
+
+    def xyzz_rr_probe(self, curve, group, op, words_per_row, acc, sec=None, pt=None, fin=None, rows_per_element=1):
+        """one step of one reduced-radix point function per element (op: include/amdmsm.h amdmsm_xyzz_rr_probe_device).
+        acc, sec: (rows, 4 * limbs) int32; pt: (rows, 2 * words_per_row) uint32; fin: one uint32 per element.  Returns
+        (out limbs, out words (rows, 4 * words_per_row), flag per element)."""
+        acc = np.ascontiguousarray(acc, dtype=np.int32)
+        sec = None if sec is None else np.ascontiguousarray(sec, dtype=np.int32)
+        pt = None if pt is None else np.ascontiguousarray(pt, dtype=np.uint32)
+        rows = acc.shape[0]
+        n = rows // rows_per_element
+        fin = None if fin is None else np.ascontiguousarray(fin, dtype=np.uint32)
+        if rows % rows_per_element or (sec is not None and sec.shape != acc.shape) or \
+                (pt is not None and pt.shape != (rows, 2 * words_per_row)) or (fin is not None and fin.shape != (n,)):
+            raise ValueError("operand arrays of the wrong shape")
+        out = np.zeros_like(acc)
+        outw = np.zeros((rows, 4 * words_per_row), dtype=np.uint32)
+        fout = np.zeros(n, dtype=np.uint32)
+        ptrs = self._dev_arrays(acc, sec, pt, fin, out, outw, fout)
+        try:
+            self._check(self.lib.amdmsm_xyzz_rr_probe_device(self.h, curve, group, int(op), *ptrs, ctypes.c_size_t(n)),
+                        "amdmsm_xyzz_rr_probe_device")
+            self.d2h(out, ptrs[4])
+            self.d2h(outw, ptrs[5])
+            self.d2h(fout, ptrs[6])
+        finally:
+            for p in ptrs:
+                if p is not None:
+                    self.free(p)
+        return out, outw, fout
 
     def group_op(self, curve, group, op, a, b=None, out_form=OUT_LIBFF):
         """group op over arrays of libff records: 0 add 1 mixed_add 2 dbl"""

@@ -11,25 +11,7 @@ import math
 
 import pytest
 
-MODULI = {
-    "alt_bn128": (0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47, 8),
-    "bls12_377": (0x01AE3A4617C510EAC63B05C06CA1493B1A22D9F300F5138F1EF3622FBA094800170B5D44300000008508C00000000001, 12),
-    "bls12_381": (0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB, 12),
-    "bw6_761": (0x122E824FB83CE0AD187C94004FAFF3EB926186A81D14688528275EF8087BE41707BA638E584E91903CEBAFF25B423048689C8ED12F9FD9071DCD3DC73EBFF2E98A116C25667A8F8160CF8AEEAF0A437E6913E6870000082F49D00000000008B, 24),
-}
-FQ2_NR = {"alt_bn128": -1, "bls12_377": -5, "bls12_381": -1}
-
-
-class Shape:
-    def __init__(self, name):
-        self.p, self.N = MODULI[name]
-        bits = self.p.bit_length()
-        self.B = 29 if bits + 6 <= 9 * 29 else 28           # rr_shape<P>::B
-        self.L = (bits + 6 + self.B - 1) // self.B           # rr_shape<P>::L
-        self.D = self.B * self.L - 32 * self.N               # rho = 2^D 2^(32N)
-        self.rho = 1 << (self.B * self.L)
-        self.ratio = self.p / self.rho                       # p / rho
-        assert 0 <= self.D < self.B
+from rr_model import FQ2_NR, MODULI, Shape   # the moduli, the non-residues and rr_shape<P>, shared with the integer model
 
 
 class El:
@@ -292,50 +274,61 @@ def test_bucket_loop_bounds_fq2(name):
             acc = madd(ch, acc, fq2_nr=FQ2_NR[name])
 
 
+# ---- Jacobian chain steps (jac_dbl_rr / jac_madd_rr), at module level so that tests/test_gpu_rr_probe.py can ask for the
+# interval of one step ----
+def jac_operands(ch):
+    """an affine point brought to the factor rho (re_from_words_rho), y of either sign, and the constant one"""
+    one = one_el(ch)
+    px = ch.mul(canonical(ch), one)   # re_from_words_rho
+    py = ch.norm(ch.lin([(-1, px)]))  # +-y: the negated copy is carried once
+    return px, hull(px, py), one
+
+
+def jac_dbl(ch, p):
+    x, y, z = p
+    for e in (x, y, z):
+        ch.factor_ok(e)
+    assert y.val < 64
+    a, b = ch.sqr(x), ch.sqr(y)
+    c = ch.sqr(b)
+    yz = ch.mul(y, z)
+    t = ch.norm(ch.lin([(1, x), (1, b)]))
+    d = ch.small_times(ch.lin([(1, ch.sqr(t)), (-1, a), (-1, c)]), 2)
+    e = ch.small_times(a, 3)
+    f = ch.sqr(e)
+    x3 = ch.norm(ch.lin([(1, f), (-1, ch.small_times(d, 2))]))
+    g = ch.mul(e, ch.factor_ok(ch.lin([(1, d), (-1, x3)])))
+    c8 = ch.small_times(ch.small_times(c, 4), 2)
+    return x3, ch.norm(ch.lin([(1, g), (-1, c8)])), ch.small_times(yz, 2)
+
+
+def jac_madd(ch, p, px, py):
+    x, y, z = p
+    z1z1 = ch.sqr(z)
+    u2 = ch.mul(px, z1z1)
+    s2 = ch.mul(py, ch.mul(z, z1z1))
+    h = ch.factor_ok(ch.lin([(1, u2), (-1, x)]))
+    r = ch.lin([(1, s2), (-1, y)])
+    assert h.val < 64
+    hh = ch.sqr(h)
+    i4 = ch.small_times(hh, 4)
+    j = ch.mul(h, i4)
+    r = ch.small_times(r, 2)
+    v = ch.mul(x, i4)
+    z3 = ch.small_times(ch.mul(z, h), 2)
+    x3 = ch.norm(ch.lin([(1, ch.sqr(r)), (-1, j), (-1, ch.small_times(v, 2))]))
+    y1j = ch.mul(y, j)
+    g = ch.mul(r, ch.factor_ok(ch.lin([(1, v), (-1, x3)])))
+    return x3, ch.norm(ch.lin([(1, g), (-1, ch.small_times(y1j, 2))])), z3
+
+
 @pytest.mark.parametrize("name", ["alt_bn128", "bls12_377", "bls12_381", "bw6_761"])
 def test_jacobian_chain_bounds(name):
     """jac_dbl_rr / jac_madd_rr (the decoder's subgroup tests): a point and its images under repeated steps"""
     ch = Checker(Shape(name))
-    one = one_el(ch)
-    px = ch.mul(canonical(ch), one)   # re_from_words_rho
-    py = ch.norm(ch.lin([(-1, px)]))  # +-y: the negated copy is carried once
-    py = hull(px, py)
-
-    def dbl(p):
-        x, y, z = p
-        for e in (x, y, z):
-            ch.factor_ok(e)
-        assert y.val < 64
-        a, b = ch.sqr(x), ch.sqr(y)
-        c = ch.sqr(b)
-        yz = ch.mul(y, z)
-        t = ch.norm(ch.lin([(1, x), (1, b)]))
-        d = ch.small_times(ch.lin([(1, ch.sqr(t)), (-1, a), (-1, c)]), 2)
-        e = ch.small_times(a, 3)
-        f = ch.sqr(e)
-        x3 = ch.norm(ch.lin([(1, f), (-1, ch.small_times(d, 2))]))
-        g = ch.mul(e, ch.factor_ok(ch.lin([(1, d), (-1, x3)])))
-        c8 = ch.small_times(ch.small_times(c, 4), 2)
-        return x3, ch.norm(ch.lin([(1, g), (-1, c8)])), ch.small_times(yz, 2)
-
-    def madd_j(p):
-        x, y, z = p
-        z1z1 = ch.sqr(z)
-        u2 = ch.mul(px, z1z1)
-        s2 = ch.mul(py, ch.mul(z, z1z1))
-        h = ch.factor_ok(ch.lin([(1, u2), (-1, x)]))
-        r = ch.lin([(1, s2), (-1, y)])
-        assert h.val < 64
-        hh = ch.sqr(h)
-        i4 = ch.small_times(hh, 4)
-        j = ch.mul(h, i4)
-        r = ch.small_times(r, 2)
-        v = ch.mul(x, i4)
-        z3 = ch.small_times(ch.mul(z, h), 2)
-        x3 = ch.norm(ch.lin([(1, ch.sqr(r)), (-1, j), (-1, ch.small_times(v, 2))]))
-        y1j = ch.mul(y, j)
-        g = ch.mul(r, ch.factor_ok(ch.lin([(1, v), (-1, x3)])))
-        return x3, ch.norm(ch.lin([(1, g), (-1, ch.small_times(y1j, 2))])), z3
+    px, py, one = jac_operands(ch)
+    dbl = lambda p: jac_dbl(ch, p)
+    madd_j = lambda p: jac_madd(ch, p, px, py)
 
     p = (px, py, one)
     for step in range(12):   # doublings with an addition behind every second one (the decoder's chains)
