@@ -626,6 +626,43 @@ int amdmsm_fr_matrix_load_transposed(amdmsm_ctx *ctx, int curve, size_t n_rows, 
 int amdmsm_plan_fr_matrix_transposed(int curve, size_t n_rows, size_t n_cols, const uint64_t *offsets, const uint32_t *cols,
                                      const void *coeffs, int coeffs_plain, size_t out[AMDMSM_FR_MATRIX_PLAN_WORDS]);
 
+/* Sparse matrix times point vector, on the handle of an Fr matrix as it stands:
+ *     out[i] = sum over the kept entries k of row i of the handle of  coeff[k] * P[col[k]],   i < n_rows
+ * a row without kept entries gives the group's zero.  With the transposed handle of a constraint matrix and P the
+ * Lagrange form [L_i(tau)]G of a ceremony's powers (amdmsm_group_fft, inverse) this is a Groth16 query of a phase-2
+ * setup, A_query[c] = sum over the entries (i, c) of A of A[i][c] * [L_i(tau)]G -- the map amdmsm_fr_matrix_apply runs
+ * over Fr when the trapdoor is known.  DESIGN section 28.
+ *   mat      any live handle of this context (amdmsm_fr_matrix_load or _load_transposed) of the curve `curve`; it keeps
+ *            serving amdmsm_fr_matrix_apply*, before and after and on other streams, and amdmsm_fr_matrix_free waits for
+ *            the applies of this entry too.  A handle loaded under AMDMSM_FR_MATRIX_NAIVE=1 has no resident form and is
+ *            refused.
+ *   chunk_entries  general-coefficient entries worked through at a time (each costs one ladder of amdmsm_scalar_mul_vec
+ *            and its table in the workspace); 0 = as many as fit that entry's 1 GiB budget.  Chunks are cut between wave
+ *            jobs, so a job with more general entries than this still runs whole.  The results do not depend on it,
+ *            bit for bit.
+ * amdmsm_group_matrix_apply_device: n_points >= n_cols compact affine records (amdmsm_import_bases_device) in, n_rows
+ * records in opts->out_form (AMDMSM_OUT_LIBFF by default; AMDMSM_OUT_AFFINE is normalised in batch) out, both in HBM and
+ * not overlapping; nothing at or beyond record n_rows is touched.  Enqueued on opts->stream (or the context's), not
+ * synchronised.  Entries of coefficient 1 and r - 1 cost one mixed addition each.
+ * amdmsm_group_matrix_apply: records, stride and base_form as for amdmsm_multi_exp, out_xyz n_rows packed records in host
+ * memory; uploads, applies, downloads and synchronises.
+ * Refused before anything is launched or written, in this order: AMDMSM_ERR_UNSUPPORTED for (MNT6, G2) or an unknown
+ * curve or group (before the context is looked at); AMDMSM_ERR_BAD_ARG, with amdmsm_last_error naming the argument, for a
+ * null context, a wrong opts->struct_size, a handle that is freed, foreign, of another curve or naive, n_points < n_cols,
+ * a null pointer with work to do, a bad stride or alignment, an output overlapping the input; AMDMSM_ERR_TOO_LARGE for
+ * n_points above 2^28.  A handle with 0 rows succeeds and writes nothing.
+ * amdmsm_plan_group_matrix, read-only: out[0] / out[1] general / +-1 entries kept, out[2] wave jobs, out[3] partial sums,
+ * out[4] chunks for this chunk_entries, out[5] workspace bytes, out[6] launches (AMDMSM_OUT_LIBFF), out[7] 0.
+ * With timing enabled (amdmsm_get_timings): [0] import with upload (host entry), [1] the general pass -- gather, table,
+ * ladder, normalisation -- [2] accumulation and combine, [3] normalisation / export of the output (host entry: with the
+ * download), [AMDMSM_PH_TOTAL] the call. */
+int amdmsm_group_matrix_apply_device(amdmsm_ctx *ctx, int curve, int group, uint64_t mat, const void *d_points_affine,
+                                     size_t n_points, void *d_out_xyz, size_t chunk_entries, const amdmsm_opts *opts);
+int amdmsm_group_matrix_apply(amdmsm_ctx *ctx, int curve, int group, uint64_t mat, const void *points_xyz,
+                              size_t stride_bytes, int base_form, size_t n_points, void *out_xyz, size_t chunk_entries,
+                              const amdmsm_opts *opts);
+int amdmsm_plan_group_matrix(amdmsm_ctx *ctx, int curve, int group, uint64_t mat, size_t chunk_entries, size_t out[8]);
+
 /* Segmented MSM: m sums in one call, out[j] = sum of scalars[i] * base(i) over offsets[j] <= i < offsets[j + 1] -- the
  * shape of k proofs verified as a batch (sum of input_i * IC_i per proof), of row or column commitments, of the cross
  * terms of an inner-product argument.  A single MSM per segment would pay the fixed cost of its launch chain m times;

@@ -66,7 +66,7 @@ FR_UNITS = {"alt_bn128": 0, "bls12_377": 1, "bw6_761": 2, "bls12_381": 3, "mnt4"
 ARCH = "gfx950"
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I" + INCLUDE, "-I" + CSRC,
           "-Wno-unused-result"]
-DEVICE_DEPS = ["msm_group.hip", "rr.cuh", "rr_chain.inc", "fp.cuh", "fp2.cuh", "fp2h.cuh", "ec.cuh", "wide.cuh", "wide28.cuh", "mac_chain.inc", "curve_params.h", "group_vtable.h", os.path.join(HERE, "build.py")]
+DEVICE_DEPS = ["msm_group.hip", "group_matrix.inc", "fr_matrix_layout.h", "rr.cuh", "rr_chain.inc", "fp.cuh", "fp2.cuh", "fp2h.cuh", "ec.cuh", "wide.cuh", "wide28.cuh", "mac_chain.inc", "curve_params.h", "group_vtable.h", os.path.join(HERE, "build.py")]
 FR_DEPS = ["fr_ntt.hip", "fr_matrix.inc", "fr_matrix_layout.h", "fr_scan.inc", "fr_scan_layout.h", "fr_domain.inc", "mac_chain.inc", "fp.cuh", "curve_params.h", "fr_vtable.h", os.path.join(HERE, "build.py")]
 HOST_DEPS = ["engine.cpp", "ffi.cpp", "engine_internal.h", "group_vtable.h", "fr_vtable.h", "fr_matrix_layout.h", "fr_scan_layout.h", "write_plan.h", os.path.join(INCLUDE, "amdmsm.h"),
              os.path.join(INCLUDE, "libff_amd_ffi.h")]

@@ -126,6 +126,9 @@ struct fr_matrix {
     void *words = nullptr, *coef = nullptr, *desc = nullptr, *lane_rows = nullptr, *comb = nullptr;   // resident form
     void *offsets = nullptr, *cols = nullptr;                                                         // naive: with coef
     uint32_t n_desc = 0, n_comb = 0, n_partials = 0;
+    // host copy of every job's gen_base and, behind the last, the count of general entries: where
+    // amdmsm_group_matrix_apply cuts its chunks
+    std::vector<uint32_t> job_gen;
     // behind the last apply on every stream that has used the handle: what amdmsm_fr_matrix_free waits for
     std::vector<std::pair<hipStream_t, hipEvent_t>> users;
 };
@@ -4838,6 +4841,8 @@ int frm_check_apply(amdmsm_ctx *ctx, uint64_t mat, const void *x, size_t n_x, co
 // the workspace of an apply: the partial sums
 size_t frm_ws_bytes(const fr_vtable *f, const fr_matrix *m) { return align_up(((size_t)m->n_partials + 1) * f->words * 4, 256); }
 
+int frm_record_user(amdmsm_ctx *ctx, hipStream_t st, fr_matrix *m);
+
 // the kernels of one apply on device vectors, behind mark 1; partial: room for n_partials records
 int frm_run(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, fr_matrix *m, const uint32_t *d_x, uint32_t *d_out, size_t n_out,
             uint32_t *partial) {
@@ -4862,7 +4867,11 @@ int frm_run(amdmsm_ctx *ctx, const fr_vtable *f, hipStream_t st, fr_matrix *m, c
         f->matrix_apply(st, a);
     }
     HIP_TRY(ctx, hipGetLastError());
-    // behind this user of the handle
+    return frm_record_user(ctx, st, m);
+}
+
+// behind this user of the handle: what amdmsm_fr_matrix_free waits for
+int frm_record_user(amdmsm_ctx *ctx, hipStream_t st, fr_matrix *m) {
     hipEvent_t *ev = nullptr;
     for (auto &u : m->users)
         if (u.first == st) ev = &u.second;
@@ -4950,6 +4959,9 @@ int frm_load(amdmsm_ctx *ctx, int curve, size_t n_rows, size_t n_cols, const uin
         m->n_desc = (uint32_t)L.desc.size();
         m->n_comb = (uint32_t)L.comb.size();
         m->n_partials = L.n_partials;
+        m->job_gen.reserve(L.desc.size() + 1);
+        for (const frm_desc &d : L.desc) m->job_gen.push_back(d.gen_base);
+        m->job_gen.push_back((uint32_t)L.gen_src.size());
         rc = frm_upload(ctx, m->words, L.words.data(), L.words.size() * 4);
         if (!rc) rc = frm_upload(ctx, m->desc, L.desc.data(), L.desc.size() * sizeof(frm_desc));
         if (!rc) rc = frm_upload(ctx, m->lane_rows, L.lane_rows.data(), L.lane_rows.size() * 4);
@@ -5030,6 +5042,209 @@ int amdmsm_fr_matrix_apply(amdmsm_ctx *ctx, uint64_t mat, const void *x, size_t 
                    [&](char *vecs, char *ws) {
                        return frm_run(ctx, f, st, m, (const uint32_t *)vecs, (uint32_t *)(vecs + x_bytes), n_out, (uint32_t *)ws);
                    });
+}
+
+}  // extern "C"
+
+// ---- sparse matrix times point vector: out[i] = sum_k coeff[k] P[col[k]] over the kept entries of row i --------------------
+namespace {
+
+// The wave jobs of the handle are worked through in chunks [job0, job1): first the general entries of the chunk --
+// gm_gather, smv_table, smv_ladder with the handle's coefficients, import_bases in normal form -- then gm_apply over
+// the same jobs.  rank0, cnt: the chunk's general entries in the handle's side array.
+struct gm_chunk {
+    uint32_t job0, job1, rank0, cnt;
+};
+// Workspace of the call's slot: gathered points (the products as compact affine records once the table is built) |
+// table and its scratch | products as libff records | partial sums.  The normalisation of an AMDMSM_OUT_AFFINE output
+// runs behind everything else and takes its n_rows compact affine records from the start of the slot.
+struct gm_plan {
+    std::vector<gm_chunk> chunks;
+    size_t cn = 0;   // the most general entries of a chunk
+    size_t off_table = 0, off_tmp = 0, off_prod = 0, off_part = 0, ws_bytes = 0, launches = 0;
+};
+gm_plan gm_make_plan(const group_vtable *vt, const fr_matrix *m, size_t chunk_entries) {
+    gm_plan p;
+    const size_t aff = (size_t)vt->el_words * 8, xyz = (size_t)vt->el_words * 12, zz = (size_t)vt->el_words * 16;
+    const size_t part = align_up(((size_t)m->n_partials + 1) * zz, 256);
+    const size_t per = aff + 2 * smv_table_bytes(vt, 1) + xyz, n_gen = m->job_gen.empty() ? 0 : m->job_gen.back();
+    const size_t want = vec_chunk_points(per, part < SMV_WS_BUDGET / 2 ? part : SMV_WS_BUDGET / 2, n_gen ? n_gen : 1, chunk_entries);
+    for (uint32_t j = 0; j < m->n_desc;) {
+        gm_chunk c = {j, j + 1, m->job_gen[j], 0};
+        while (c.job1 < m->n_desc && (size_t)m->job_gen[c.job1 + 1] - c.rank0 <= want) ++c.job1;   // a job is never split
+        c.cnt = m->job_gen[c.job1] - c.rank0;
+        if (c.cnt > p.cn) p.cn = c.cnt;
+        p.launches += c.cnt ? 5 : 1;
+        p.chunks.push_back(c);
+        j = c.job1;
+    }
+    if (m->n_comb) ++p.launches;
+    p.off_table = align_up(p.cn * aff, 256);
+    p.off_tmp = p.off_table + align_up(smv_table_bytes(vt, p.cn), 256);
+    p.off_prod = p.off_tmp + align_up(smv_table_bytes(vt, p.cn), 256);
+    p.off_part = p.off_prod + align_up(p.cn * xyz, 256);
+    p.ws_bytes = std::max(p.off_part + part, align_up(m->n_rows * aff, 256));
+    return p;
+}
+
+// The argument rules of the three entries up to the handle, in the order the header gives; the caller has refused an
+// unknown group already.
+int gm_check_handle(amdmsm_ctx *ctx, int curve, uint64_t mat, fr_matrix *&m) {
+    m = frm_find(ctx, mat);
+    if (!m) return fail(ctx, AMDMSM_ERR_BAD_ARG, "mat: handle " + std::to_string(mat) + " is not a live handle of this context");
+    if (m->curve != curve)
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "mat: handle " + std::to_string(mat) + " belongs to curve " + std::to_string(m->curve) +
+                                                 ", not " + std::to_string(curve));
+    if (m->naive) return fail(ctx, AMDMSM_ERR_BAD_ARG, "mat: handle " + std::to_string(mat) + " was loaded under AMDMSM_FR_MATRIX_NAIVE and has no resident form");
+    return AMDMSM_OK;
+}
+// ... and of both apply entries behind it.  device: points and out are HBM addresses, compact affine records in and
+// packed libff records out; else host vectors, the points stride_bytes apart.
+int gm_check(amdmsm_ctx *ctx, const group_vtable *vt, int curve, uint64_t mat, const void *points, size_t n_points, const void *out,
+             bool device, size_t &stride_bytes, fr_matrix *&m) {
+    int rc = gm_check_handle(ctx, curve, mat, m);
+    if (rc) return rc;
+    if (n_points < m->n_cols)
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "n_points = " + std::to_string(n_points) + " < n_cols = " + std::to_string(m->n_cols));
+    if (m->n_rows && !out) return fail(ctx, AMDMSM_ERR_BAD_ARG, device ? "d_out_xyz: null pointer" : "out_xyz: null pointer");
+    if (m->n_rows && m->kept && !points)
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, device ? "d_points_affine: null pointer" : "points_xyz: null pointer");
+    const size_t aff = (size_t)vt->el_words * 8, xyz = (size_t)vt->el_words * 12;
+    if (device) {
+        rc = dev_check_aligned(ctx, "d_points_affine", points, rec_align(vt));
+        if (!rc) rc = dev_check_aligned(ctx, "d_out_xyz", out, rec_align(vt));
+        if (!rc) rc = fr_check_apart(ctx, "d_points_affine", points, n_points * aff, "d_out_xyz", out, m->n_rows * xyz, false);
+    } else {
+        rc = vec_check_stride(ctx, vt, stride_bytes, "stride_bytes: not a stride of libff records");
+        if (!rc && n_points)
+            rc = fr_check_apart(ctx, "points_xyz", points, (n_points - 1) * stride_bytes + xyz, "out_xyz", out, m->n_rows * xyz, false);
+    }
+    if (rc) return rc;
+    if (n_points > FRM_MAX_DIM) return fail(ctx, AMDMSM_ERR_TOO_LARGE, "n_points = " + std::to_string(n_points) + ": at most 2^28 points");
+    return AMDMSM_OK;
+}
+
+// the kernels of one apply on device-resident points, between the call's first mark and its last; n_rows > 0
+int gm_run(amdmsm_ctx *ctx, const group_vtable *vt, hipStream_t st, fr_matrix *m, const gm_plan &p, const uint32_t *d_points,
+           uint32_t *d_out, const vec_opts &vo, char *ws) {
+    gm_args a = {};
+    a.words = (const uint32_t *)m->words;
+    a.desc = (const frm_desc *)m->desc;
+    a.lane_rows = (const uint32_t *)m->lane_rows;
+    a.points = d_points;
+    a.prod = (uint32_t *)ws;
+    a.out = d_out;
+    a.partial = (uint32_t *)(ws + p.off_part);
+    a.form = vo.kernel_form;
+    uint32_t *table = (uint32_t *)(ws + p.off_table), *tmp = (uint32_t *)(ws + p.off_tmp), *prod_xyz = (uint32_t *)(ws + p.off_prod);
+    for (const gm_chunk &c : p.chunks) {
+        a.job0 = c.job0;
+        a.n_jobs = c.job1 - c.job0;
+        a.first_rank = c.rank0;
+        if (c.cnt) {
+            call_mark(ctx, st, 1);
+            vt->gm_gather(st, a);
+            vt->smv_table(st, a.prod, c.cnt, tmp, table);
+            vt->smv_ladder(st, table, c.cnt, (const uint32_t *)m->coef + (size_t)c.rank0 * vt->fr_words, 1, AMDMSM_OUT_LIBFF, prod_xyz);
+            // the gathered points are dead behind the table: the products take their place, the group's zero as (0, 0)
+            vt->import_bases(st, prod_xyz, (size_t)vt->el_words * 3, 0, c.cnt, a.prod);
+        }
+        call_mark(ctx, st, 2);
+        vt->gm_apply(st, a);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    vt->gm_combine(st, (const frm_comb *)m->comb, m->n_comb, a.partial, a.form, d_out);
+    call_mark(ctx, st, 3);
+    vec_finish(vt, st, vo, d_out, m->n_rows, (uint32_t *)ws);
+    HIP_TRY(ctx, hipGetLastError());
+    return frm_record_user(ctx, st, m);
+}
+
+int gm_check_form(amdmsm_ctx *ctx, const vec_opts &vo) {
+    if (vo.form != AMDMSM_OUT_LIBFF && vo.form != AMDMSM_OUT_AFFINE)
+        return fail(ctx, AMDMSM_ERR_BAD_ARG, "opts->out_form: AMDMSM_OUT_LIBFF or AMDMSM_OUT_AFFINE");
+    return AMDMSM_OK;
+}
+
+}   // namespace
+
+extern "C" {
+
+#define GM_ENTER(ctx, curve, group)                                                \
+    SMV_REFUSE_UNKNOWN(ctx, curve, group);                                         \
+    if (!ctx) return fail(ctx, AMDMSM_ERR_BAD_ARG, "ctx: null pointer");           \
+    GET_VT(ctx, curve, group)
+
+int amdmsm_plan_group_matrix(amdmsm_ctx *ctx, int curve, int group, uint64_t mat, size_t chunk_entries, size_t out[8]) {
+    GM_ENTER(ctx, curve, group);
+    fr_matrix *m = nullptr;
+    const int rc = gm_check_handle(ctx, curve, mat, m);
+    if (rc) return rc;
+    if (!out) return fail(ctx, AMDMSM_ERR_BAD_ARG, "out: null pointer");
+    const gm_plan p = gm_make_plan(vt, m, chunk_entries);
+    const size_t n_gen = m->job_gen.empty() ? 0 : m->job_gen.back();
+    out[0] = n_gen;
+    out[1] = m->kept - n_gen;
+    out[2] = m->n_desc;
+    out[3] = m->n_partials;
+    out[4] = p.chunks.size();
+    out[5] = p.ws_bytes;
+    out[6] = p.launches;
+    out[7] = 0;
+    return AMDMSM_OK;
+}
+
+int amdmsm_group_matrix_apply_device(amdmsm_ctx *ctx, int curve, int group, uint64_t mat, const void *d_points_affine,
+                                     size_t n_points, void *d_out_xyz, size_t chunk_entries, const amdmsm_opts *opts) {
+    GM_ENTER(ctx, curve, group);
+    CHECK_OPTS(ctx, opts);
+    const vec_opts vo = vec_opts_of(opts);
+    int rc = gm_check_form(ctx, vo);
+    if (rc) return rc;
+    fr_matrix *m = nullptr;
+    size_t stride = 0;
+    rc = gm_check(ctx, vt, curve, mat, d_points_affine, n_points, d_out_xyz, true, stride, m);
+    if (rc || !m->n_rows) return rc;
+    hipStream_t st = stream_of(ctx, opts);
+    const gm_plan p = gm_make_plan(vt, m, chunk_entries);
+    ws_slot *sl = nullptr;
+    rc = call_begin(ctx, st, p.ws_bytes, sl);
+    if (rc) return rc;
+    rc = gm_run(ctx, vt, st, m, p, (const uint32_t *)d_points_affine, (uint32_t *)d_out_xyz, vo, (char *)sl->ws);
+    if (rc) return rc;
+    return call_end(ctx, st, *sl);
+}
+
+int amdmsm_group_matrix_apply(amdmsm_ctx *ctx, int curve, int group, uint64_t mat, const void *points_xyz, size_t stride_bytes,
+                              int base_form, size_t n_points, void *out_xyz, size_t chunk_entries, const amdmsm_opts *opts) {
+    GM_ENTER(ctx, curve, group);
+    CHECK_OPTS(ctx, opts);
+    const vec_opts vo = vec_opts_of(opts);
+    int rc = gm_check_form(ctx, vo);
+    if (rc) return rc;
+    fr_matrix *m = nullptr;
+    rc = gm_check(ctx, vt, curve, mat, points_xyz, n_points, out_xyz, false, stride_bytes, m);
+    if (rc || !m->n_rows) return rc;
+    hipStream_t st = ctx->stream;
+    const size_t xyz_bytes = (size_t)vt->el_words * 12, aff_bytes = (size_t)vt->el_words * 8;
+    const size_t n_up = points_xyz ? n_points : 0;   // a matrix without kept entries reads no point
+    const gm_plan p = gm_make_plan(vt, m, chunk_entries);
+    rc = ensure_buf(ctx, ctx->hb_src, n_up * stride_bytes);
+    if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->hb_aff, n_up * aff_bytes);
+    if (rc == AMDMSM_OK) rc = ensure_buf(ctx, ctx->fb.out, m->n_rows * xyz_bytes);
+    ws_slot *sl = nullptr;
+    if (rc == AMDMSM_OK) rc = call_begin(ctx, st, p.ws_bytes, sl);
+    if (rc) return rc;
+    if (n_up) rc = vec_upload(ctx, vt, st, points_xyz, stride_bytes, base_form, 0, n_up, ctx->hb_aff.p);
+    if (!rc) rc = gm_run(ctx, vt, st, m, p, (const uint32_t *)ctx->hb_aff.p, (uint32_t *)ctx->fb.out.p, vo, (char *)sl->ws);
+    if (rc) {
+        (void)hipDeviceSynchronize();   // nothing of this call may still touch the staging buffers
+        return rc;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(out_xyz, ctx->fb.out.p, m->n_rows * xyz_bytes, hipMemcpyDeviceToHost, st));
+    rc = call_end(ctx, st, *sl);
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return rc;
 }
 
 }  // extern "C"

@@ -7,6 +7,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "fr_matrix_layout.h"
+
 namespace amdmsm {
 
 // output coordinate conventions for the final kernels
@@ -166,8 +168,25 @@ struct sort_src {
     }
 };
 
+// One pass of amdmsm_group_matrix_apply over the wave jobs job0 .. job0 + n_jobs - 1 of a resident Fr matrix
+// (fr_matrix_layout.h; group_matrix.inc).  words, desc, lane_rows: the handle's arrays.  points: at least n_cols compact
+// affine records.  prod: the records of the general entries of these jobs, record (rank - first_rank) for the entry of
+// rank `rank` in the handle's side array -- gm_gather writes the entry's point there, gm_apply reads its product.
+// out: libff records in `form`, one per row; partial: (X, Y, ZZ, ZZZ) records, 4 * el_words words each.
+struct gm_args {
+    const uint32_t* words;
+    const frm_desc* desc;
+    const uint32_t* lane_rows;
+    const uint32_t* points;
+    uint32_t* prod;
+    uint32_t* out;
+    uint32_t* partial;
+    uint32_t job0, n_jobs, first_rank;
+    int form;
+};
+
 // Members by stage: constants of the group; import / export / codecs; digits and sort; accumulate and fix-up; reduction
-// and Horner; fixed-base; point-vector entries (smv, seg, fold, fft); test hooks and probes.  msm_group.hip fills the
+// and Horner; fixed-base; point-vector entries (smv, seg, fold, fft, gm); test hooks and probes.  msm_group.hip fills the
 // table by member name.
 struct group_vtable {
     // ---- constants of the group ----------
@@ -356,6 +375,15 @@ struct group_vtable {
     void (*fft_gather)(hipStream_t, const uint32_t* in_affine, size_t b0, size_t cn, int rsh, uint32_t* dst_affine);
     void (*fft_butterfly)(hipStream_t, const uint32_t* table, size_t cn, const uint32_t* in_affine, size_t b0, int rsh,
                           const uint32_t* twiddles, int mont, size_t half, uint32_t* out);
+
+    // Sparse matrix times point vector over the resident form of an Fr matrix (amdmsm_group_matrix_apply), one wave per
+    // job.  gm_gather: the points of the jobs' general entries into a.prod, in rank order -- the base vector of
+    // smv_table, whose ladder runs with the handle's coefficients.  gm_apply: the row sums of the jobs -- +-points[col]
+    // for the entries of coefficient 1 and r - 1, a.prod[rank - first_rank] (compact affine again) for a general one.
+    // gm_combine: out[comb[i].row] = the sum of its partials, one lane per split row.
+    void (*gm_gather)(hipStream_t, const gm_args& a);
+    void (*gm_apply)(hipStream_t, const gm_args& a);
+    void (*gm_combine)(hipStream_t, const frm_comb* comb, uint32_t n_comb, const uint32_t* partial, int form, uint32_t* out);
 
     // ---- test hooks (parity of the primitives against the oracle) ----------
     // coordinate-field op over arrays: 0 mul 1 sqr 2 add 3 sub 4 neg 5 inverse

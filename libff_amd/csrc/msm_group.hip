@@ -4655,6 +4655,8 @@ void l_fft_butterfly(hipStream_t st, const uint32_t* table, size_t cn, const uin
                            half, out);
 }
 
+#include "group_matrix.inc"
+
 const group_vtable g_vt = {
     // constants of the group
     .curve = GP::CURVE, .group = GP::GROUP, .fr_words = FRW, .el_words = EW, .fq_words = FQ::N, .fr_bits = FR::BITS,
@@ -4685,6 +4687,7 @@ const group_vtable g_vt = {
     .seg_fold = l_seg_fold, .seg_horner = l_seg_horner,
     .fold_digit_stride = SMV_DS, .fold_digits = l_fold_digits, .fold_ladder = l_fold_ladder,
     .fft_gather = l_fft_gather, .fft_butterfly = l_fft_butterfly,
+    .gm_gather = l_gm_gather, .gm_apply = l_gm_apply, .gm_combine = l_gm_combine,
     // test hooks and probes
     .field_op = l_field_op, .group_op = l_group_op, .digits = l_digits, .glv_digits = l_glv_digits,
     .mul_bench = l_mul_bench, .madd_bench = l_madd_bench, .field_probe = l_field_probe, .xyzz_probe = l_xyzz_probe,

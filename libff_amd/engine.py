@@ -81,6 +81,7 @@ EXPORTED_SYMBOLS = [
     "amdmsm_plan_write_points",
     "amdmsm_fr_fft_batch", "amdmsm_fr_fft_batch_device", "amdmsm_plan_fr_fft_batch", "amdmsm_fr_domain_fft_batch_device",
     "amdmsm_fr_qap_witness_map", "amdmsm_fr_qap_witness_map_device", "amdmsm_plan_fr_qap_witness_map",
+    "amdmsm_group_matrix_apply", "amdmsm_group_matrix_apply_device", "amdmsm_plan_group_matrix",
 ]
 SEG_SHARED_BASES = 1            # include/amdmsm.h AMDMSM_SEG_SHARED_BASES
 SEG_LONG_NEVER = 2 ** 64 - 1    # long_from = SIZE_MAX: no segment takes the single-MSM route
@@ -1311,6 +1312,49 @@ class Engine:
         self._check(self.lib.amdmsm_fr_matrix_apply_device(self.h, ctypes.c_uint64(mat.handle),
                                                            _opt_dev(d_x), ctypes.c_size_t(n_x), _opt_dev(d_out), ctypes.c_size_t(n_out),
                                                            ctypes.byref(o)), "amdmsm_fr_matrix_apply_device")
+
+    def group_matrix_apply(self, mat, group, points, *, base_form=multi_exp_base_form_normal, out_form=OUT_LIBFF,
+                           chunk_entries=0, stride_bytes=None, out=None):
+        """Sparse matrix times point vector on the handle of an Fr matrix (``amdmsm_group_matrix_apply``):
+        ``out[i] = sum_k coeff[k] * points[col[k]]`` over the kept entries of row i of ``mat``, the group's zero for a row
+        without any.  ``points``: (n >= mat.n_cols, 3 * coordinate limbs) libff records of ``group`` of the matrix's curve
+        in ``base_form``; the result is ``mat.n_rows`` records in ``out_form``.  ``chunk_entries``: general-coefficient
+        entries worked through at a time, 0 = automatic (``plan_group_matrix`` tells); the results do not depend on it.
+        ``stride_bytes``: bytes between two records of ``points`` (default: packed).  ``out``: result array to fill."""
+        s = sizes(mat.curve, group)
+        points = np.ascontiguousarray(points, dtype=np.uint64)
+        n = _records(points, stride_bytes, s["g_bytes"])
+        if n and stride_bytes is None:
+            assert points.shape == (n, s["g_bytes"] // 8), "points must be (n, 3*coord_limbs) uint64"
+        out = _result_array(out, mat.n_rows, s["g_bytes"])
+        o = self._opts(out_form=out_form)
+        rc = self.lib.amdmsm_group_matrix_apply(self.h, mat.curve, group, ctypes.c_uint64(mat.handle), _np_ptr(points) if n else None,
+                                                ctypes.c_size_t(s["g_bytes"] if stride_bytes is None else stride_bytes), base_form,
+                                                ctypes.c_size_t(n), _np_ptr(out) if mat.n_rows else None,
+                                                ctypes.c_size_t(chunk_entries), ctypes.byref(o))
+        self._check(rc, "amdmsm_group_matrix_apply")
+        return out
+
+    def group_matrix_apply_device(self, mat, group, d_points_affine, n_points, d_out_xyz, *, out_form=OUT_LIBFF, chunk_entries=0,
+                                  stream=None):
+        """``group_matrix_apply`` on device-resident inputs (``amdmsm_group_matrix_apply_device``): ``n_points`` compact
+        affine records (``import_bases_device``) in, ``mat.n_rows`` records written to ``d_out_xyz``; enqueued on
+        ``stream``, not synchronised.  The chain of a phase-2 setup: ``group_fft_device`` with the inverse twiddles and
+        ``fold_vec_device`` by n^-1, ``import_bases_device``, this entry, ``write_points_file``."""
+        o = self._opts(out_form=out_form, stream=stream)
+        self._check(self.lib.amdmsm_group_matrix_apply_device(self.h, mat.curve, group, ctypes.c_uint64(mat.handle),
+                                                              _opt_dev(d_points_affine), ctypes.c_size_t(n_points),
+                                                              _opt_dev(d_out_xyz), ctypes.c_size_t(chunk_entries),
+                                                              ctypes.byref(o)), "amdmsm_group_matrix_apply_device")
+
+    def plan_group_matrix(self, mat, group, chunk_entries=0):
+        """What ``group_matrix_apply`` runs for the handle ``mat`` (``amdmsm_plan_group_matrix``, read-only): entries kept
+        by kind, wave jobs, partial sums, chunks for this ``chunk_entries``, workspace bytes and launches."""
+        out = (ctypes.c_size_t * 8)()
+        self._check(self.lib.amdmsm_plan_group_matrix(self.h, mat.curve, group, ctypes.c_uint64(mat.handle),
+                                                      ctypes.c_size_t(chunk_entries), out), "amdmsm_plan_group_matrix")
+        return {"general": out[0], "plus_minus_one": out[1], "wave_jobs": out[2], "partials": out[3], "chunks": out[4],
+                "workspace_bytes": out[5], "launches": out[6]}
 
     def _scan_flags(self, reverse, exclusive):
         return (SCAN_REVERSE if reverse else 0) | (SCAN_EXCLUSIVE if exclusive else 0)
